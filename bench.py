@@ -3,7 +3,7 @@
 512x512, 99-step DPM-Encoder inversion + 99-step coupled decode with decoder CFG 3 (BASELINE.json
 metric; SURVEY.md §8d "C2 headline"), synthetic weights / images / contexts (no checkpoints here).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
   (N > 1: one rank per GPU, RCCL for the output gather. Either the caller starts the ranks - `python -m
   torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`,
   RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env - or the plain command is given and bench.py starts them
@@ -259,6 +259,38 @@ def pmc_traffic_per_launch(steps_per_set=16):
     return None, None
 
 
+DUMP_BUDGET = 64 << 20  # bytes of array data --dump-outputs may write, all files together
+
+
+def last_step_outputs(out):
+    """what a caller of the timed path received in its last step - ((original_image, image), loss) after the per-step
+    gather - as host tensors, copied at once (later launch sets may reuse the engine's buffers)"""
+    (orig, img), loss = out[0], out[1]
+    return {name: t.detach().to("cpu", copy=True) for name, t in
+            (("original_image", orig), ("image", img), ("loss", loss)) if t is not None}
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET, seed=0):
+    """--dump-outputs: every array as <path>/<name>.npy, float64 if it is float64, else float32. When they exceed `budget`
+    together, each keeps the same fraction of its elements: a fixed, seeded sample of the flattened array (the same indices
+    for the same shape on every run). Returns {name: {shape, saved_elements, sampled}} for the JSON line."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {k: (v.double() if v.dtype == torch.float64 else v.float()).numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    frac = min(1.0, (budget - 4096 * len(host)) / total) if total else 1.0  # 4 KiB per file for the .npy header
+    info = {}
+    for name, a in host.items():
+        keep = max(1, int(a.size * frac))
+        sampled = keep < a.size
+        if sampled:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        info[name] = {"shape": list(host[name].shape), "saved_elements": int(a.size), "sampled": sampled}
+    return info
+
+
 def launch_sets(steps, cap):
     """K queued steps as launch sets of `cap` steps plus one smaller tail set. (Round 5 measured the alternative - sets of equal
     size, 20 steps = 10 + 10 instead of 16 + 4: 3.16 against 3.35-3.44 images/s, GEMM family 833 against 897-929 TFLOP/s. At
@@ -400,6 +432,8 @@ def dry_main(a, wl, rank, world):
                "config": {"workload": wl["name"], "batch_per_gpu": B, "global_batch": B * world,
                           "parallelism": "dp%d" % world, "steps_per_launch_set": C,
                           "distributed": "gloo process group" if dist.is_initialized() else "single process"}}
+        if a.dump_outputs:
+            res["outputs"] = {"dir": a.dump_outputs, "arrays": dump_outputs(a.dump_outputs, last_step_outputs(out))}
         print(json.dumps(res), flush=True)
     if dist.is_initialized():
         dist.barrier()
@@ -441,11 +475,18 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="host plumbing only (ranks, sharding, gathers, timing, the JSON line) over gloo on CPU tensors, "
                          "no engine call: the CPU tests of the N > 1 launch path")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step (original_image, "
+                         "image, loss) as DIR/<name>.npy, float32, at most 64 MB in all (a seeded sample beyond that); "
+                         "the same arguments give the same inputs on every run")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
     wl = WORKLOADS[a.workload]
+    a.dump_outputs = os.path.abspath(a.dump_outputs) if a.dump_outputs else ""  # the ranks below run in ROOT
 
     if (a.gpus > 1 or a.self_launch) and "WORLD_SIZE" not in os.environ:
-        sys.exit(self_launch(a.gpus, sys.argv[1:]))
+        sys.exit(self_launch(a.gpus, sys.argv[1:] + (["--dump-outputs", a.dump_outputs] if a.dump_outputs else [])))
     a.force_dist = a.force_dist or a.self_launch
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -604,6 +645,7 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     assert torch.isfinite(out[0][1]).all()
+    last = last_step_outputs(out) if rank == 0 and a.dump_outputs else None  # written after the measurements below
     ranks_seen = ranks_seen_by_gather(rank, world, dev)
 
     # BASELINE's literal operating point beside the folded one: launch sets of ONE step (a batch of B triplets per
@@ -743,6 +785,8 @@ def main():
                 res["cpu_baseline"] = ref
             else:
                 res["cpu_baseline"] = cpu_baseline(eng, wrapper.unet, wrapper.vae)
+        if last is not None:
+            res["outputs"] = {"dir": a.dump_outputs, "arrays": dump_outputs(a.dump_outputs, last)}
         print(json.dumps(res), flush=True)
     if dist.is_initialized():
         dist.barrier()

@@ -328,12 +328,82 @@ def gen_xtr_text():
     save("xtr_text_tiny", y=y, ids=ids, wseed=17, width=cfg.width, layers=cfg.layers, vocab=cfg.vocab)
 
 
+# ---- tests/test_oracle_vs_reference.py and test_oracle_xtr.py: their reference runs, live or as committed records ----------
+SECOND_DRAW_FILES = ("model/lib/stable_diffusion/ldm/modules/diffusionmodules/openaimodel.py",
+                     "model/lib/stable_diffusion/ldm/modules/diffusionmodules/model.py",
+                     "model/lib/ddpm_ddim/models/improved_ddpm/unet.py", "model/lib/ddpm_ddim/models/ddpm/diffusion.py")
+XTR_FILES = ("model/lib/stable_diffusion/ldm/modules/x_transformer.py",)
+
+
+def reference_has(files):
+    """every module file a live run imports is in the reference tree (the copy staged for the GPU box holds fewer)"""
+    return ref_import.available() and all(os.path.exists(os.path.join(ref_import.REF, f)) for f in files)
+
+
+def second_draw():
+    """The reference networks on a second draw of weights and inputs (per-sample timesteps, batch > 1 VAE): the arrays of
+    tests/golden/reference_second_draw.npz - each network's (name, shape) list and weight seed beside its outputs."""
+    out = {}
+
+    def record(key, module, wseed):
+        ns, _sd = load_synth(module, wseed)
+        out[key + "_names"], out[key + "_wseed"] = np.asarray(json.dumps(ns)), np.asarray(wseed)
+        return module
+
+    with torch.no_grad():
+        u = record("sd", build_ref_sd_unet(), 901)
+        out["sd_y"] = u(rnd((3, 4, 16, 16), 31), torch.tensor([1, 501, 981]), context=rnd((3, 77, 64), 32)).numpy()
+        u = record("iddpm", build_ref_iddpm(), 902)
+        out["iddpm_y"] = u(rnd((2, 3, 32, 32), 33), torch.tensor([999.0, 0.0])).numpy()
+        v = record("vae", RefVAE(), 903)
+        img = torch.rand((3, 3, 64, 64), generator=torch.Generator().manual_seed(34)) * 2 - 1
+        out["vae_moments"], out["vae_decoded"] = v.moments(img).numpy(), v.decode(rnd((3, 4, 16, 16), 35, 0.7)).numpy()
+        h = record("ho", build_ref_ho(), 904)
+        out["ho_y"] = h(rnd((2, 3, 32, 32), 36), torch.tensor([10.0, 870.0])).numpy()
+        u = record("ldm_uncond", build_ref_sd_unet(TINY_LDM_UNCOND), 905)
+        out["ldm_uncond_y"] = u(rnd((2, 3, 16, 16), 37), torch.tensor([3, 777])).numpy()
+    return out
+
+
+XTR_CHECK = dict(width=128, layers=3, vocab=500, positions=40, wseed=3, ids_seed=4, ids_shape=(2, 33))
+
+
+def xtr_check_ids():
+    c = XTR_CHECK
+    return torch.randint(0, c["vocab"], c["ids_shape"], generator=torch.Generator().manual_seed(c["ids_seed"]))
+
+
+def xtr_module_run(cfg, wseed, ids):
+    """the reference's x-transformers encoder on oracle.xtr_text's seeded weights: ({name: shape}, embeddings)"""
+    ref_import.setup()
+    from ldm.modules.x_transformer import Encoder, TransformerWrapper
+    from oracle import xtr_text
+    m = TransformerWrapper(num_tokens=cfg.vocab, max_seq_len=cfg.positions,
+                           attn_layers=Encoder(dim=cfg.width, depth=cfg.layers), emb_dropout=0.0).eval()
+    missing, unexpected = m.load_state_dict(xtr_text.synth_state_dict(cfg, wseed), strict=False)
+    assert not unexpected and all(k.startswith("to_logits") for k in missing), (missing, unexpected)
+    with torch.no_grad():
+        y = m(ids, return_embeddings=True)
+    return {k: tuple(v.shape) for k, v in m.state_dict().items() if not k.startswith("to_logits")}, y
+
+
+def gen_live_records():
+    """python -m oracle.gen_golden --only records: what the two live-reference tests compare with where it is absent"""
+    from oracle import xtr_text
+    with ref_import.session():
+        save("reference_second_draw", **second_draw())
+        c = XTR_CHECK
+        cfg = xtr_text.XtrTextCfg(width=c["width"], layers=c["layers"], vocab=c["vocab"], positions=c["positions"])
+        shapes, y = xtr_module_run(cfg, c["wseed"], xtr_check_ids())
+    save("xtr_text_module_check", y=y, ids=xtr_check_ids(), shapes=np.asarray(json.dumps(shapes)), wseed=c["wseed"])
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     a = ap.parse_args()
     todo = dict(schedule=gen_schedule, nets=gen_nets, latent=gen_latent_cycle, c1=gen_c1, xtr=gen_xtr_text,
-                pixel_refine=gen_pixel_refine, ldm_uncond=gen_ldm_uncond)
+                pixel_refine=gen_pixel_refine, ldm_uncond=gen_ldm_uncond, records=gen_live_records)
     for k, fn in todo.items():
         if not a.only or a.only == k:
             fn()

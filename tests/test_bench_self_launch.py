@@ -66,3 +66,40 @@ def test_eight_ranks_dry_run_c4_and_c5_batches():
     assert res["host_threads_per_rank"] == max(1, _cores() // 8)
     res = _run(["--gpus", "8", "--workload", "c5", "--steps", "2", "--warmup", "0", "--dry-run"])
     assert res["ranks_seen"] == list(range(8)) and res["config"]["global_batch"] == 32 and res["config"]["batch_per_gpu"] == 4
+
+
+def test_dump_outputs_writes_the_last_step_of_every_rank(tmp_path):
+    """--dump-outputs DIR: what the timed path returned in its last step, gathered over the ranks, as float32 .npy files;
+    the same arguments give the same arrays on every run, and --steps 0 is refused rather than timing nothing."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        res = _run(["--gpus", "2", "--steps", "5", "--warmup", "1", "--coalesce", "2", "--dry-run", "--dump-outputs", str(d)])
+        assert res["steps"] == 5 and res["outputs"]["dir"] == str(d)
+        runs.append({n: np.load(str(d / (n + ".npy"))) for n in ("original_image", "image", "loss")})
+    got = runs[0]
+    assert got["original_image"].dtype == np.float32 and got["original_image"].shape == (8, 3, 8, 8)
+    assert got["loss"].shape == (8,) and np.array_equal(got["image"], 1.0 - got["original_image"])
+    assert all(np.array_equal(got[n], runs[1][n]) for n in got)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-run"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
+
+
+def test_dump_outputs_samples_past_its_budget(tmp_path):
+    """over the size budget every array keeps the same fraction of its elements, at seeded indices (the same on every run)"""
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    arrays = {"image": torch.arange(40000, dtype=torch.float32).reshape(4, 100, 100), "loss": torch.zeros(4, dtype=torch.float64)}
+    info = [bench.dump_outputs(str(tmp_path / d), arrays, budget=8192 + 40000) for d in ("a", "b")]
+    assert info[0] == info[1] and info[0]["image"]["sampled"] and info[0]["image"]["shape"] == [4, 100, 100]
+    a, b = (np.load(str(tmp_path / d / "image.npy")) for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.size == info[0]["image"]["saved_elements"] and 4000 < a.size < 40000 // 2
+    assert np.array_equal(a, b) and np.all(np.diff(a) > 0)  # sorted indices of a strictly increasing array
+    assert np.load(str(tmp_path / "a" / "loss.npy")).dtype == np.float64
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in ("image.npy", "loss.npy")) <= 8192 + 40000

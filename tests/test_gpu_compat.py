@@ -3,7 +3,9 @@
 from the copy oracle/stage_reference.py stages next to the built library; test side only) drives the HIP U-Net through
 `LatentDiffusionHIP.apply_model`, and its z / latents are compared with the engine's fused loops on the same network, contexts
 and noise. Two independent implementations of the loop around ONE network: the reference's torch scheduler arithmetic with a
-C-ABI call per forward, against cd_dpm_encode / cd_ddim_decode / cd_cycle_translate (one fused step kernel per step)."""
+C-ABI call per forward, against cd_dpm_encode / cd_ddim_decode / cd_cycle_translate (one fused step kernel per step).
+Where neither copy of the reference exists, the oracle's restatement of the same sampler (oracle/samplers.py, pinned to the
+reference by the committed fixtures) drives the same seam in its place, with the same draws and the same bounds."""
 import pytest
 import torch
 
@@ -26,16 +28,37 @@ def _draws(seed, shape, K):
     return torch.stack([first] + [torch.randn(shape, device="cuda") for _ in range(K - 1)], 0)
 
 
+def _oracle_sampler_loops(model, S, skip, x0, c, uc, c2, dec_scale, noise):
+    """Without the reference tree: the same two loops in the oracle's restatement of DDIMSampler (oracle/samplers.py,
+    pinned to the reference's own runs by tests/golden/latent_cycle_tiny.npz), host-side torch fp32 step arithmetic,
+    every network evaluation through the same seam, `LatentDiffusionHIP.apply_model`, on identical draws."""
+    from oracle import samplers
+    unet = lambda x, t, cc: model.apply_model(x, t, cc).cpu()
+    c, uc, c2 = c.cpu(), uc.cpu(), c2.cpu()
+    with torch.no_grad():
+        z = samplers.latent_encode(samplers.cfg_model(unet, c, uc, 1.0), x0.cpu(), S, 0.1, list(noise.cpu()),
+                                   skip_steps=skip, white_box_steps=S + 1)
+        z = torch.stack(z, dim=1)
+        x = samplers.latent_decode(samplers.cfg_model(unet, c2, uc, dec_scale), z[:, 0], z[:, 1:], S, 0.1, skip_steps=skip)
+    return z.cuda(), x.cuda()
+
+
 @pytest.mark.parametrize("dec_scale", [1.0, 3.0])
 def test_reference_ddim_sampler_over_the_hip_unet_matches_the_fused_loops(engine, report, dec_scale):
-    if not ref_import.available():
-        pytest.skip("no reference tree (neither /root/reference nor oracle/_ref)")
     fx = gu.load("latent_cycle_tiny")
     net, _sd = _load(engine, tiny_sd_desc(), fx)
     x0, c, uc, c2 = (t.cuda() for t in gu.latent_cycle_inputs())
     S, skip = 99, 91
     K = S - skip  # 8 steps of the real 99-step schedule
     model = LatentDiffusionHIP(engine, net)
+    if not ref_import.available():
+        z_ref, x_ref = _oracle_sampler_loops(model, S, skip, x0, c, uc, c2, dec_scale, _draws(4242, tuple(x0.shape), K))
+    else:
+        z_ref, x_ref = _reference_sampler_loops(model, S, skip, x0, c, uc, c2, dec_scale)
+    _compare_with_fused_loops(engine, report, net, S, skip, K, x0, c, uc, c2, dec_scale, z_ref, x_ref)
+
+
+def _reference_sampler_loops(model, S, skip, x0, c, uc, c2, dec_scale):
     with ref_import.session():
         from ldm.models.diffusion.ddim import DDIMSampler  # the reference's class, as it is
         torch.cuda.manual_seed(4242)
@@ -48,6 +71,10 @@ def test_reference_ddim_sampler_over_the_hip_unet_matches_the_fused_loops(engine
                                                           shape=(4, 16, 16), eta=0.1, verbose=False, x_T=z_ref[:, 0],
                                                           skip_steps=skip, unconditional_guidance_scale=dec_scale,
                                                           unconditional_conditioning=uc)
+    return z_ref, x_ref
+
+
+def _compare_with_fused_loops(engine, report, net, S, skip, K, x0, c, uc, c2, dec_scale, z_ref, x_ref):
     assert z_ref.shape == (2, K + 1, 4, 16, 16) and z_ref.is_cuda
     noise = _draws(4242, tuple(x0.shape), K)
     sch = schedule.DDIMSchedule(schedule.latent_alphas_cumprod(), S, 0.1)
