@@ -13,10 +13,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libcyclediff.so")
 
 CD_NET_UNET_OPENAI, CD_NET_UNET_HO, CD_NET_VAE_KL, CD_NET_CLIP_TEXT, CD_NET_BERT_XTR = 1, 2, 3, 4, 5
-CD_NET_OCLIP_TEXT, CD_NET_OCLIP_VISION = 6, 7
+CD_NET_OCLIP_TEXT, CD_NET_OCLIP_VISION, CD_NET_INCEPTION_FID = 6, 7, 8
 CD_SCHED_DDIM, CD_SCHED_DDPM = 0, 1
 CD_PREC_16, CD_PREC_F32, CD_PREC_F32X3 = 0, 1, 2
-ACT_NONE, ACT_SILU, ACT_GELU, ACT_GEGLU = 0, 1, 2, 3
+ACT_NONE, ACT_SILU, ACT_GELU, ACT_GEGLU, ACT_QGELU, ACT_RELU = 0, 1, 2, 3, 4, 5
 
 
 class NetDesc(C.Structure):
@@ -64,6 +64,7 @@ SIGNATURES = {
     "cd_text_encode": [_VP, _I, _VP, _I, _I, _VP],
     "cd_clip_text_features": [_VP, _I, _VP, _I, _I, _VP],
     "cd_clip_image_features": [_VP, _I, _VP, _I, _VP],
+    "cd_inception_features": [_VP, _I, _VP, _I, _I, _VP],
     "cd_vae_encode": [_VP, _I, _VP, _VP, _U64, _I, _I, _I, _F, _VP],
     "cd_vae_decode": [_VP, _I, _VP, _I, _I, _F, _F, _F, _VP],
     "cd_dpm_encode": [_VP, _I, _I, _VP, _VP, _VP, _I, _F, _I, _I, _VP, _VP, _U64, _I, _VP],

@@ -266,6 +266,7 @@ int cd_net_create(cd_handle h, const cd_net_desc* d, int* net_id) {
     case CD_NET_BERT_XTR:
     case CD_NET_OCLIP_TEXT:
     case CD_NET_OCLIP_VISION: n = make_clip_text(*d); break;
+    case CD_NET_INCEPTION_FID: n = make_inception_fid(*d); break;
     default: CD_CHECK(false, "unknown net kind %d", d->kind);
   }
   n->params.overflow = h->overflow_dev;
@@ -473,6 +474,18 @@ int cd_text_encode(cd_handle h, int net, const int32_t* tokens, int B, int L, fl
 static TextEncoder* get_tower(cd_handle h, int net, int kind) {
   CD_CHECK(h && net >= 0 && net < (int)h->nets.size() && h->nets[net]->kind() == kind, "net %d has the wrong kind", net);
   return static_cast<TextEncoder*>(h->nets[net].get());
+}
+
+int cd_inception_features(cd_handle h, int net, const float* img, int B, int stop_block, float* out) {
+  CD_API_BEGIN
+  CD_CHECK(h, "null handle");
+  enter_engine(h);
+  CD_CHECK(net >= 0 && net < (int)h->nets.size(), "bad net id %d", net);
+  CD_CHECK(img && out && B > 0, "bad argument");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  inception_fid_features(h->nets[net].get(), c, img, B, stop_block, out);
+  CD_API_END
 }
 
 int cd_clip_text_features(cd_handle h, int net, const int32_t* tokens, int B, int L, float* out) {

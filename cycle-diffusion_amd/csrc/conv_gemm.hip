@@ -899,6 +899,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
           } else if (p.act == ACT_QGELU) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) v[e] = v[e] / (1.0f + __expf(-1.702f * v[e]));
+          } else if (p.act == ACT_RELU) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.0f);
           }
         }
         if (p.resid && p.resid_f32) {

@@ -261,4 +261,9 @@ class TextEncoder : public Net {  // token ids -> conditioning sequence (SURVEY.
 };
 std::unique_ptr<TextEncoder> make_clip_text(const cd_net_desc& d);
 
+// the FID Inception-v3 (inception.hip): pool3 features [B][2048] fp32, or the fp32 NCHW output of block list entry
+// stop_block >= 0 (include/cyclediff.h cd_inception_features)
+std::unique_ptr<Net> make_inception_fid(const cd_net_desc& d);
+void inception_fid_features(Net* n, Ctx& c, const float* img, int B, int stop_block, float* out);
+
 }  // namespace cd

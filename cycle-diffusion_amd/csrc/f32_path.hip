@@ -522,7 +522,7 @@ void launch_conv_gemm_f32(hipStream_t st, const ConvGemmParams& p) {
   CD_CHECK(p.C0 % 32 == 0 && p.C1 % 32 == 0, "conv_f32: channels must be multiples of 32 (C0=%d C1=%d)", p.C0, p.C1);
   CD_CHECK(p.Ktot == p.KH * p.KW * Ctot, "conv_f32: Ktot mismatch");
   CD_CHECK(p.M > 0 && p.N > 0 && p.nbatch == 1, "conv_f32: empty or batched problem");
-  CD_CHECK(p.act != ACT_GEGLU && p.act != ACT_QGELU && !p.stats && p.splitk <= 1, "conv_f32: unsupported epilogue");
+  CD_CHECK(p.act != ACT_GEGLU && p.act != ACT_QGELU && p.act != ACT_RELU && !p.stats && p.splitk <= 1, "conv_f32: unsupported epilogue");
   CD_CHECK((p.ld0 % 4) == 0 && (p.src1 == nullptr || (p.ld1 % 4) == 0), "conv_f32: ld must be a multiple of 4");
   CD_CHECK(((uintptr_t)p.src0 & 15) == 0 && ((uintptr_t)p.wgt & 15) == 0, "conv_f32: 16-B alignment");
   KernelProfiler* prof = g_conv_prof;  // bench.py's roofline leg: per-launch HIP events on the launch stream

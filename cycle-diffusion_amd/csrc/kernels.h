@@ -46,7 +46,8 @@ void launch_set_int(hipStream_t st, int* p, int v);
 void launch_add_int(hipStream_t st, int* p, int d);
 
 // ---------------------------------------------------------------- implicit-GEMM conv / GEMM (conv_gemm.hip)
-enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_GEGLU = 3, ACT_QGELU = 4 };  // QGELU: x*sigmoid(1.702x) (CLIP)
+enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_GEGLU = 3, ACT_QGELU = 4, ACT_RELU = 5 };  // QGELU: x*sigmoid(1.702x) (CLIP)
+// RELU: max(x, 0) (the BasicConv2d units of the FID Inception-v3, inception.hip)
 
 struct ConvGemmParams {
   // A operand: activations, NHWC bf16; optional second source = channel concat (th.cat, openaimodel.py:736)

@@ -117,6 +117,67 @@ def ho_ddpm_desc(image_size, ch, ch_mult, num_res_blocks, attn_resolutions, in_c
                      attn=tuple(attn_resolutions), precision=precision)
 
 
+def inception_fid_desc():
+    """The FID Inception-v3 (csrc/inception.hip): 299 x 299 input, 16-bit storage; no other descriptor field is read."""
+    return make_desc(_ffi.CD_NET_INCEPTION_FID, image_size=299, in_channels=3, out_channels=2048, model_channels=0,
+                     num_res_blocks=0, channel_mult=(), precision=_ffi.CD_PREC_16)
+
+
+def inception_fid_units():
+    """[(name, in_channels, out_channels, (kh, kw))] of every BasicConv2d of the FID Inception-v3 (torchvision Inception3
+    naming), in the engine's declaration order."""
+    u = [("Conv2d_1a_3x3", 3, 32, (3, 3)), ("Conv2d_2a_3x3", 32, 32, (3, 3)), ("Conv2d_2b_3x3", 32, 64, (3, 3)),
+         ("Conv2d_3b_1x1", 64, 80, (1, 1)), ("Conv2d_4a_3x3", 80, 192, (3, 3))]
+    for name, cin, pf in (("Mixed_5b", 192, 32), ("Mixed_5c", 256, 64), ("Mixed_5d", 288, 64)):
+        u += [(name + ".branch1x1", cin, 64, (1, 1)), (name + ".branch5x5_1", cin, 48, (1, 1)),
+              (name + ".branch5x5_2", 48, 64, (5, 5)), (name + ".branch3x3dbl_1", cin, 64, (1, 1)),
+              (name + ".branch3x3dbl_2", 64, 96, (3, 3)), (name + ".branch3x3dbl_3", 96, 96, (3, 3)),
+              (name + ".branch_pool", cin, pf, (1, 1))]
+    u += [("Mixed_6a.branch3x3", 288, 384, (3, 3)), ("Mixed_6a.branch3x3dbl_1", 288, 64, (1, 1)),
+          ("Mixed_6a.branch3x3dbl_2", 64, 96, (3, 3)), ("Mixed_6a.branch3x3dbl_3", 96, 96, (3, 3))]
+    for name, c7 in (("Mixed_6b", 128), ("Mixed_6c", 160), ("Mixed_6d", 160), ("Mixed_6e", 192)):
+        u += [(name + ".branch1x1", 768, 192, (1, 1)), (name + ".branch7x7_1", 768, c7, (1, 1)),
+              (name + ".branch7x7_2", c7, c7, (1, 7)), (name + ".branch7x7_3", c7, 192, (7, 1)),
+              (name + ".branch7x7dbl_1", 768, c7, (1, 1)), (name + ".branch7x7dbl_2", c7, c7, (7, 1)),
+              (name + ".branch7x7dbl_3", c7, c7, (1, 7)), (name + ".branch7x7dbl_4", c7, c7, (7, 1)),
+              (name + ".branch7x7dbl_5", c7, 192, (1, 7)), (name + ".branch_pool", 768, 192, (1, 1))]
+    u += [("Mixed_7a.branch3x3_1", 768, 192, (1, 1)), ("Mixed_7a.branch3x3_2", 192, 320, (3, 3)),
+          ("Mixed_7a.branch7x7x3_1", 768, 192, (1, 1)), ("Mixed_7a.branch7x7x3_2", 192, 192, (1, 7)),
+          ("Mixed_7a.branch7x7x3_3", 192, 192, (7, 1)), ("Mixed_7a.branch7x7x3_4", 192, 192, (3, 3))]
+    for name, cin in (("Mixed_7b", 1280), ("Mixed_7c", 2048)):
+        u += [(name + ".branch1x1", cin, 320, (1, 1)), (name + ".branch3x3_1", cin, 384, (1, 1)),
+              (name + ".branch3x3_2a", 384, 384, (1, 3)), (name + ".branch3x3_2b", 384, 384, (3, 1)),
+              (name + ".branch3x3dbl_1", cin, 448, (1, 1)), (name + ".branch3x3dbl_2", 448, 384, (3, 3)),
+              (name + ".branch3x3dbl_3a", 384, 384, (1, 3)), (name + ".branch3x3dbl_3b", 384, 384, (3, 1)),
+              (name + ".branch_pool", cin, 192, (1, 1))]
+    return u
+
+
+# output shapes (C, H, W) of cd_inception_features' block list: the stem convs and pools one by one, then each Mixed block
+INCEPTION_BLOCKS = ("Conv2d_1a_3x3", "Conv2d_2a_3x3", "Conv2d_2b_3x3", "maxpool1", "Conv2d_3b_1x1", "Conv2d_4a_3x3",
+                    "maxpool2", "Mixed_5b", "Mixed_5c", "Mixed_5d", "Mixed_6a", "Mixed_6b", "Mixed_6c", "Mixed_6d",
+                    "Mixed_6e", "Mixed_7a", "Mixed_7b", "Mixed_7c")
+INCEPTION_BLOCK_SHAPES = ((32, 149, 149), (32, 147, 147), (64, 147, 147), (64, 73, 73), (80, 73, 73), (192, 71, 71),
+                          (192, 35, 35), (256, 35, 35), (288, 35, 35), (288, 35, 35), (768, 17, 17), (768, 17, 17),
+                          (768, 17, 17), (768, 17, 17), (768, 17, 17), (1280, 8, 8), (2048, 8, 8), (2048, 8, 8))
+
+
+def inception_synthetic_state_dict(seed=0):
+    """Seeded synthetic weights for the FID Inception-v3, keyed as its checkpoint (`X.conv.weight`, `X.bn.*`): He-normal
+    convs (std sqrt(2 / fan_in), so that activations keep their scale through 94 ReLU layers), BN weight ~ 1, small bias and
+    mean, running_var = 1 + a small positive term (Engine.random_init would draw negative variances)."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for name, cin, cout, (kh, kw) in inception_fid_units():
+        fan_in = cin * kh * kw
+        sd[name + ".conv.weight"] = torch.randn((cout, cin, kh, kw), generator=g) * float(np.sqrt(2.0 / fan_in))
+        sd[name + ".bn.weight"] = 1.0 + 0.05 * torch.randn(cout, generator=g)
+        sd[name + ".bn.bias"] = 0.05 * torch.randn(cout, generator=g)
+        sd[name + ".bn.running_mean"] = 0.05 * torch.randn(cout, generator=g)
+        sd[name + ".bn.running_var"] = 1.0 + 0.1 * torch.rand(cout, generator=g)
+    return sd
+
+
 class Engine:
     """One engine per rank / stream (cd_engine_create)."""
 
@@ -272,6 +333,28 @@ class Engine:
         assert img.shape[1:] == (3, d.image_size, d.image_size), img.shape
         out = torch.empty((img.shape[0], d.out_channels), device=self.device, dtype=torch.float32)
         check(self.lib.cd_clip_image_features(self.h, net, ptr(img), img.shape[0], ptr(out)))
+        return out
+
+    def load_inception_state_dict(self, net, sd):
+        """A pytorch-fid / clean-fid Inception state_dict: every tensor the network declares, `fc.*` and
+        `*.num_batches_tracked` skipped. Raises KeyError on a missing tensor."""
+        sd = {k: v for k, v in sd.items() if not k.startswith("fc.") and not k.endswith(".num_batches_tracked")}
+        n, first = self.load_state_dict(net, sd, strict=True)
+        if n:
+            raise KeyError("Inception state_dict lacks %d tensors, first: %s" % (n, first))
+
+    def inception_features(self, net, img, stop_block=-1):
+        """cd_inception_features: normalised [B, 3, 299, 299] fp32 -> pool3 [B, 2048] fp32 (stop_block -1), or the fp32 NCHW
+        output of block list entry `stop_block` (include/cyclediff.h)."""
+        img = self._f32(img)
+        assert img.shape[1:] == (3, 299, 299), img.shape
+        B = img.shape[0]
+        if stop_block < 0:
+            shape = (B, 2048)
+        else:
+            shape = (B,) + INCEPTION_BLOCK_SHAPES[stop_block]
+        out = torch.empty(shape, device=img.device, dtype=torch.float32)
+        check(self.lib.cd_inception_features(self.h, net, ptr(img), B, int(stop_block), ptr(out)))
         return out
 
     def vae_encode(self, net, img, noise=None, seed=0, sample=True, scale=0.18215):

@@ -28,7 +28,7 @@ extern "C" {
 typedef struct cd_engine* cd_handle;
 
 enum { CD_NET_UNET_OPENAI = 1, CD_NET_UNET_HO = 2, CD_NET_VAE_KL = 3, CD_NET_CLIP_TEXT = 4, CD_NET_BERT_XTR = 5,
-       CD_NET_OCLIP_TEXT = 6, CD_NET_OCLIP_VISION = 7 };
+       CD_NET_OCLIP_TEXT = 6, CD_NET_OCLIP_VISION = 7, CD_NET_INCEPTION_FID = 8 };
 enum { CD_SCHED_DDIM = 0, CD_SCHED_DDPM = 1 };
 enum { CD_PREC_16 = 0, CD_PREC_F32 = 1, CD_PREC_F32X3 = 2 };
 
@@ -49,7 +49,13 @@ enum { CD_PREC_16 = 0, CD_PREC_F32 = 1, CD_PREC_F32X3 = 2 };
  *   OCLIP_TEXT / OCLIP_VISION : the text and image towers of OpenAI CLIP (ViT-B/32 in the reference:
  *                 model/energy/clean_clip.py:10 `clip.load("ViT-B/32")`), weights keyed by the openai/CLIP package's
  *                 state_dict names; out_channels = embedding width (512); VISION: image_size = input resolution
- *                 (224), z_channels = patch size (32), in_channels = 3 */
+ *                 (224), z_channels = patch size (32), in_channels = 3
+ *   INCEPTION_FID : the Inception-v3 of the FID / KID metrics (torchvision Inception3 with the FIDInceptionA / C / E_1 / E_2
+ *                 blocks of pytorch-fid and clean-fid) up to its 2048-d pool3 features; image_size = 299, precision =
+ *                 CD_PREC_16 (the only one implemented), no other field is read. Weights keyed by that network's
+ *                 state_dict names, `X.conv.weight`, `X.bn.weight`, `X.bn.bias`, `X.bn.running_mean`, `X.bn.running_var`
+ *                 for every BasicConv2d X (`Conv2d_1a_3x3`, `Mixed_5b.branch1x1`, ...); BatchNorm (eps 1e-3) is folded
+ *                 into the packed weights inside the engine before the next forward */
 typedef struct cd_net_desc {
   int kind;
   int image_size;          /* spatial size of the network input (latent 64, pixel 256, ...)      */
@@ -134,6 +140,14 @@ int cd_text_encode(cd_handle h, int net, const int32_t* tokens, int B, int L, fl
 /* DirectionalCLIP's feature extractors (model/energy/clean_clip.py:24-31): model.encode_text(tokens) and
  * model.encode_image(preprocessed) of OpenAI CLIP, un-normalised. tokens [B,L] int32; img [B,3,R,R] fp32 already
  * resized / centre-cropped / mean-std normalised; out [B,embed] fp32. */
+/* Inception-v3 features for FID / KID (clean-fid's `build_feature_extractor` network; evaluation/translate_to_dog.py
+ * computes the metrics on them). img [B,3,299,299] fp32, already resized and normalised ((x - 128) / 128 on the 0..255
+ * scale). stop_block = -1: out = pool3 [B,2048]. stop_block = k >= 0: out = the output of entry k of the block list as
+ * fp32 NCHW [B,C,H,W]: 0 Conv2d_1a_3x3 (32x149x149), 1 Conv2d_2a_3x3 (32x147x147), 2 Conv2d_2b_3x3 (64x147x147),
+ * 3 max-pool (64x73x73), 4 Conv2d_3b_1x1 (80x73x73), 5 Conv2d_4a_3x3 (192x71x71), 6 max-pool (192x35x35), 7-9 Mixed_5b/5c/5d
+ * (256/288/288x35x35), 10 Mixed_6a (768x17x17), 11-14 Mixed_6b..6e (768x17x17), 15 Mixed_7a (1280x8x8), 16-17 Mixed_7b/7c
+ * (2048x8x8). */
+int cd_inception_features(cd_handle h, int net, const float* img, int B, int stop_block, float* out);
 int cd_clip_text_features(cd_handle h, int net, const int32_t* tokens, int B, int L, float* out);
 int cd_clip_image_features(cd_handle h, int net, const float* img, int B, float* out);
 

@@ -97,6 +97,17 @@ def main(argv=None):
     ap.add_argument("--synthetic-weights", action="store_true",
                     help="run on seeded synthetic weights when a checkpoint file is missing (default: error, as the "
                          "reference's torch.load); recorded as weights_origin in metrics.json")
+    ap.add_argument("--fid_ref_dir", default=None,
+                    help="target-domain images (png / jpg, searched recursively): adds FID / KID of the written outputs "
+                         "against them to metrics.json (evaluation/translate_to_dog.py); Inception-v3 on the engine")
+    ap.add_argument("--fid_ref_stats", default=None,
+                    help="npz cache of the reference images' Inception features (read if present, else written)")
+    ap.add_argument("--fid_inception", default=None,
+                    help="Inception-v3 state_dict for FID / KID (pytorch-fid pt_inception-2015-12-05-*.pth; default "
+                         "CYCLEDIFF_FID_INCEPTION, or seeded synthetic weights with --synthetic-weights)")
+    ap.add_argument("--text_metrics", action="store_true",
+                    help="text tasks: per-sample CLIP and directional CLIP (evaluation/translate_text.py) on the unclamped "
+                         "outputs; ViT-B/32 weights from CYCLEDIFF_CLIP_RANKER")
     a = ap.parse_args(argv)
     if a.synthetic_weights:
         os.environ["CYCLEDIFF_SYNTHETIC_WEIGHTS"] = "1"
@@ -135,11 +146,30 @@ def main(argv=None):
             b["is_padding"] = list(pad)
             yield b
 
+    fid_net = fid_origin = ranker = None
+    engine = getattr(wrapper, "engine", None)
+    if a.fid_ref_dir or a.text_metrics:
+        from cycle_diffusion_amd.runtime import get_engine
+        engine = engine or get_engine(dev)
+    if a.fid_ref_dir:
+        from cycle_diffusion_amd.utils import fid
+        fid_net, fid_origin = fid.load_inception(engine, a.fid_inception)
+    if a.text_metrics:
+        from cycle_diffusion_amd.utils import text_metrics
+        ranker = getattr(wrapper, "ranker", None)
+        if not hasattr(ranker, "features"):
+            ranker = text_metrics.make_ranker(engine)
+
     grid_cap = 100 * a.per_device_eval_batch_size  # the reference keeps 100 dataloader batches for its grids
     for batch, orig, img in folded_calls(model, batches(), a.fold, a.seed, dev):
         n_done += img.shape[0]
         if a.grid and rank == 0 and sum(p[0].shape[0] for p in grid_pairs) < grid_cap:
             grid_pairs.append((orig.detach().clamp(0, 1).cpu(), img.detach().clamp(0, 1).cpu()))
+        keep = [j for j in range(img.shape[0]) if not batch["is_padding"][j]]
+        feats = fid.features(engine, fid_net, img[keep]) if fid_net is not None and keep else None
+        scores = None
+        if ranker is not None and "encode_text" in batch:
+            scores = text_metrics.text_scores(ranker, img, orig, batch["encode_text"], batch["decode_text"])
         for j in range(img.shape[0]):
             if batch["is_padding"][j]:  # wrap-around padding of the last global batch: its original is written elsewhere
                 continue
@@ -151,6 +181,10 @@ def main(argv=None):
             for k in ("encode_text", "decode_text"):
                 if k in batch:
                     row[k] = batch[k][j]
+            if scores is not None:
+                row["clip"], row["d-clip"] = scores[0][j], scores[1][j]
+            if feats is not None:
+                row["_inception"] = feats[keep.index(j)]  # travels with the row to rank 0, dropped before writing
             rows.append(row)
             from PIL import Image
             Image.fromarray((g.permute(1, 2, 0).numpy() * 255 + 0.5).astype("uint8")).save(
@@ -170,8 +204,28 @@ def main(argv=None):
         assert len({r["sample_id"] for r in rows}) == len(rows)  # padding rows were skipped where they were produced
         rows.sort(key=lambda r: r["sample_id"])
         summary = {k: sum(r[k] for r in rows) / max(1, len(rows)) for k in ("psnr", "ssim", "l2")}
+        extra = {}
+        if a.text_metrics:
+            scored = [r for r in rows if "clip" in r]
+            if scored:
+                for k in ("clip", "d-clip"):
+                    summary[k] = sum(r[k] for r in scored) / len(scored)
+            extra["text_metrics"] = {"n": len(scored), "weights_origin": getattr(ranker, "weights_origin", None)}
+        if fid_net is not None:
+            import numpy as np
+            gen = np.stack([r.pop("_inception") for r in rows])
+            ref = None
+            if a.fid_ref_stats and os.path.exists(a.fid_ref_stats):
+                ref = np.load(a.fid_ref_stats)["features"]
+            if ref is None:
+                ref = fid.features_u8(engine, fid_net, fid.load_reference_images(a.fid_ref_dir, wrapper.resolution))
+                if a.fid_ref_stats:
+                    np.savez(a.fid_ref_stats, features=ref)
+            r = fid.fid_kid(gen, ref)
+            summary.update(fid=r["fid"], kid=r["kid"], fid_sqrtm_imag=r["fid_sqrtm_imag"])
+            extra["fid_eval"] = {"n_gen": r["n_gen"], "n_ref": r["n_ref"], "weights_origin": fid_origin}
         with open(os.path.join(a.output_dir, "metrics.json"), "w") as fh:
-            json.dump({"summary": summary, "weights_origin": getattr(wrapper, "weights_origin", None),
+            json.dump({"summary": summary, "weights_origin": getattr(wrapper, "weights_origin", None), **extra,
                        "samples": rows}, fh, indent=1)
         print(json.dumps({"n": len(rows), **summary, "seconds": wall, "images_per_s_this_rank": n_done / wall}))
     return 0
