@@ -3,7 +3,7 @@
 512x512, 99-step DPM-Encoder inversion + 99-step coupled decode with decoder CFG 3 (BASELINE.json
 metric; SURVEY.md §8d "C2 headline"), synthetic weights / images / contexts (no checkpoints here).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU, RCCL for the output gather. Either the caller starts the ranks - `python -m
   torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`,
   RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env - or the plain command is given and bench.py starts them
@@ -16,15 +16,20 @@ forward = wrapper.encode (VAE encode + DPM-Encoder) + wrapper.forward (coupled d
 i.e. exactly what Trainer.prediction_step times in the reference (trainer/trainer.py:788-789), followed
 by the per-step output gather (trainer.py:833). Prints ONE JSON line on rank 0.
 
+A plain run does only what that line's headline needs: set-up, warm-up, the K timed steps, `--dump-outputs`, the line.
+`--full` adds, after the timed steps, the measurements that take runs of their own: `single_batch` (c2), `roofline` (one
+more launch set under per-launch HIP events, then the device's sustained MFMA rate), `bf16` (c2 on one GPU: one more
+bench.py process on the bf16 library) and `cpu_baseline` (c2 on one GPU).
+
 Steps are issued `--coalesce` at a time (default: 16 for C2, 4 otherwise; a remainder forms one smaller tail set,
 `config.launch_sets`): the engine folds the queued batches into
 ONE launch set (C2: 64 images through the DPM-Encoder, 128 rows through the CFG decode, the first stage in calls of 32
 images), so every GEMM sees 16x the rows with one copy of the weights; each step still gets its own all-gather, in step
 order. `--coalesce 8` / `4` / `1` are the rounds-2b..4 / round-2a / round-1 operating points (8 against 16 on one box:
 3.35 -> 3.44 images/s, profiles/r5_bench_lines_coalesce_8_vs_16.json; every one of them is pinned to the reference by
-tests/test_gpu_e2e_fullsize.py's folded-batch tests). The line also carries `single_batch` - launch sets of ONE step, the
-operating point of the reference's own driver loop. `main.py --fold N` is the same look-ahead for real data. `--in-flight R`
-additionally keeps R such launch sets running on R independent engines / HIP streams.
+tests/test_gpu_e2e_fullsize.py's folded-batch tests). With `--full` the line also carries `single_batch` - launch sets of
+ONE step, the operating point of the reference's own driver loop. `main.py --fold N` is the same look-ahead for real
+data. `--in-flight R` additionally keeps R such launch sets running on R independent engines / HIP streams.
 
 Other BASELINE.json configurations: `--workload c3` (LDM text2img-large shapes, 256 x 256, batch 16) and
 `--workload c5r` (AFHQ improved-DDPM pair, 256 x 256, batch 4; REDUCED chain custom_steps 100 / es_steps 85 /
@@ -354,7 +359,7 @@ def bf16_leg(steps=16):
     env = dict(os.environ, CYCLEDIFF_LIB=lib)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", "0", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", "0", "--full", "--no-cpu-baseline",
            "--no-single-batch", "--no-bf16"]
     try:
         p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -449,10 +454,16 @@ def main():
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=0, help="image triplets per GPU per step (default: the workload's "
                     "BASELINE batch: 4 for C2, README.md:153; 16 for C3, README.md:195)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-single-batch", action="store_true", help="skip the extra launch-sets-of-one-step measurement")
-    ap.add_argument("--no-bf16", action="store_true", help="skip the bf16-library leg (c2 default run on one GPU)")
-    ap.add_argument("--single-steps", type=int, default=2, help="steps of the single-batch measurement (c2 default run)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what it does not need: the single-batch operating point (c2), "
+                         "the roofline launch set with per-launch HIP events and the sustained MFMA rate, the bf16-library "
+                         "leg (c2, one GPU) and the CPU baseline (c2, one GPU). Without it a run sets up, warms up, times "
+                         "--steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-single-batch", action="store_true",
+                    help="skip the launch sets of one step: the --full measurement and its warm-up set")
+    ap.add_argument("--no-bf16", action="store_true", help="--full: skip the bf16-library leg (c2 on one GPU)")
+    ap.add_argument("--single-steps", type=int, default=2, help="--full: steps of the single-batch measurement (c2)")
     ap.add_argument("--coalesce", type=int, default=0,
                     help="steps folded into one engine launch set (same images in flight as that many replicas, ONE "
                          "copy of the weights, that many times the rows per GEMM); 1 = one launch set per step; "
@@ -562,9 +573,12 @@ def main():
     # launch sets: K steps are issued C at a time (the last set may be smaller)
     sets = launch_sets(a.steps, C)
     S = max(sets)  # steps of the (largest) launch set: the operating point the line is measured at
-    single = (not a.no_single_batch) and C > 1 and a.workload == "c2"
+    # the launch sets of one step are warmed up on every c2 run, --full or not: the warm-up draws the engine's noise from
+    # the global generator, so its launch sets decide the noise the timed steps see
+    warm_single = (not a.no_single_batch) and C > 1 and a.workload == "c2"
+    single = a.full and warm_single
     folded = {n: (images[:n].reshape(n * (hi - lo), 3, R, R), sample_id.repeat(n), sum(src[:n], []), sum(tgt[:n], []))
-              for n in set(sets) | {1 if single else 0} if n}
+              for n in set(sets) | {1 if warm_single else 0} if n}
 
     coupled_by_set = {}  # launch-set size (steps) -> did translate() take the coupled loop (None: wrapper has none)
 
@@ -667,35 +681,22 @@ def main():
             single_dt = float(tt.item())
 
     res = None
-    # roofline of the dominant kernel (implicit-GEMM conv / GEMM family): one more launch set (all ranks take part in
-    # its gathers) with per-launch HIP events on rank 0's engine stream; achieved = sum(2*M*N*K) / sum(durations)
-    if rank == 0:
-        eng.prof_enable(True)
-    if ensemble:
-        mini_ensemble()
-    else:
-        gather(0, compute(0, S))
-    sync()
+    # --full: roofline of the dominant kernel (implicit-GEMM conv / GEMM family): one more launch set (all ranks take part
+    # in its gathers) with per-launch HIP events on rank 0's engine stream; achieved = sum(2*M*N*K) / sum(durations)
+    if a.full:
+        if rank == 0:
+            eng.prof_enable(True)
+        if ensemble:
+            mini_ensemble()
+        else:
+            gather(0, compute(0, S))
+        sync()
     if rank == 0:
         ips = a.steps * B * world / dt
-        n_launch, k_ms, k_flops = eng.prof_collect()
-        eng.prof_enable(False)
         f32 = getattr(wrapper, "precision", "") == "fp32"
         x3 = getattr(wrapper, "precision", "") == "fp32x3"
         # split mode: algorithmic flops (2 M N K of the fp32 conv) against a third of the 16-bit MFMA peak
         peak = PEAK_F32_TFLOPS if f32 else (PEAK_TFLOPS / 3.0 if x3 else PEAK_TFLOPS)
-        ach = k_flops / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
-        traffic, traffic_source = pmc_traffic_per_launch(S) if a.workload == "c2" and not (f32 or x3) else (None, None)
-        # the ceiling of THIS device on this lease, after the timed region: a bare 16-bit MFMA loop on every CU settles
-        # where the package power cap lets it (MI355X, 1400 W: 1.7-1.8 GHz = 1.7-1.8 PFLOP/s)
-        sustained = None
-        if not f32:
-            try:
-                s_tf, s_ghz = eng.mfma_sustained(300)
-                sustained = {"tflops": s_tf, "ghz": s_ghz, "what": "bare v_mfma_f32_32x32x16 loop on random operands, every "
-                             "CU, 0.3 s, after the timed region (csrc/diag.hip)"}
-            except Exception as e:  # noqa: BLE001 - a diagnostic never fails the bench line
-                sustained = {"error": "%s: %s" % (type(e).__name__, e)}
         fmt = "fp16" if eng.lib.cd_act_format() == 1 else "bf16"
         res = {
             "metric": wl["metric"], "value": ips, "unit": "images/s",
@@ -727,32 +728,46 @@ def main():
                        # classifier-free-guidance decodes (shared prefix, DESIGN.md 7 r3 f) - roofline.achieved counts
                        # what was launched
                        "flop_per_image_basis": "reference algorithm: every U-Net forward in full"},
-            "roofline": {"bound": "mfma", "kernel": "k_conv_f32 (fp32 implicit GEMM)" if f32 else
-                         ("k_conv_gemm on split operands (K x 3) + k_conv_f32 for raw-input convs; algorithmic flops, "
-                          "peak = 16-bit MFMA peak / 3") if x3 else "k_conv_gemm (all tile instantiations)",
-                         "achieved": ach, "peak": peak, "unit": "TFLOP/s", "frac": ach / peak,
-                         "traffic": traffic, "traffic_unit": "HBM-side bytes per launch (PMC, profiles/)",
-                         "traffic_source": traffic_source,
-                         "operating_point": ("the ensemble's engine calls at their real batch sizes on 4-step chains (skip 95), "
-                                             "per-launch HIP events") if ensemble else
-                         "one launch set of %d steps, single stream, per-launch HIP events" % S,
-                         "launches_per_step": n_launch / S, "kernel_ms_per_step": k_ms / S,
-                         "algorithmic_tflop_per_step": k_flops / 1e12 / S,
-                         "whole_path_frac": ips * wl["flop_per_image"] / 1e12 / (world * peak),
-                         # what that fraction prices against what: the 16-bit lines against the dense 16-bit MFMA peak; the
-                         # fp32 / fp32x3 lines mix three pipes (split products on the 16-bit cores at a third of their rate,
-                         # raw-input convs and attention on v_mfma_f32_32x32x2_f32 at 157 TFLOP/s, fp32 VALU norms), so their
-                         # fraction is an index against ONE of them, not a utilisation
-                         "whole_path_frac_basis": ("algorithmic FLOPs of the reference path / fp32 MFMA peak (157.3 TFLOP/s); "
-                                                   "attention and norms run on other pipes" if f32 else
-                                                   "algorithmic FLOPs of the reference path / (16-bit MFMA peak / 3): the split "
-                                                   "products' ceiling; raw-input convs and attention run on the fp32 MFMA pipe" if x3
-                                                   else "algorithmic FLOPs of the reference path / dense 16-bit MFMA peak")},
         }
-        if sustained is not None:
-            res["roofline"]["sustained_peak"] = sustained
-            if sustained.get("tflops"):
-                res["roofline"]["frac_of_sustained"] = ach / (sustained["tflops"] / (3.0 if x3 else 1.0))
+        if a.full:
+            n_launch, k_ms, k_flops = eng.prof_collect()
+            eng.prof_enable(False)
+            ach = k_flops / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
+            traffic, traffic_source = pmc_traffic_per_launch(S) if a.workload == "c2" and not (f32 or x3) else (None, None)
+            res["roofline"] = {
+                "bound": "mfma", "kernel": "k_conv_f32 (fp32 implicit GEMM)" if f32 else
+                ("k_conv_gemm on split operands (K x 3) + k_conv_f32 for raw-input convs; algorithmic flops, "
+                 "peak = 16-bit MFMA peak / 3") if x3 else "k_conv_gemm (all tile instantiations)",
+                "achieved": ach, "peak": peak, "unit": "TFLOP/s", "frac": ach / peak,
+                "traffic": traffic, "traffic_unit": "HBM-side bytes per launch (PMC, profiles/)",
+                "traffic_source": traffic_source,
+                "operating_point": ("the ensemble's engine calls at their real batch sizes on 4-step chains (skip 95), "
+                                    "per-launch HIP events") if ensemble else
+                "one launch set of %d steps, single stream, per-launch HIP events" % S,
+                "launches_per_step": n_launch / S, "kernel_ms_per_step": k_ms / S,
+                "algorithmic_tflop_per_step": k_flops / 1e12 / S,
+                "whole_path_frac": ips * wl["flop_per_image"] / 1e12 / (world * peak),
+                # what that fraction prices against what: the 16-bit lines against the dense 16-bit MFMA peak; the
+                # fp32 / fp32x3 lines mix three pipes (split products on the 16-bit cores at a third of their rate,
+                # raw-input convs and attention on v_mfma_f32_32x32x2_f32 at 157 TFLOP/s, fp32 VALU norms), so their
+                # fraction is an index against ONE of them, not a utilisation
+                "whole_path_frac_basis": ("algorithmic FLOPs of the reference path / fp32 MFMA peak (157.3 TFLOP/s); "
+                                          "attention and norms run on other pipes" if f32 else
+                                          "algorithmic FLOPs of the reference path / (16-bit MFMA peak / 3): the split "
+                                          "products' ceiling; raw-input convs and attention run on the fp32 MFMA pipe" if x3
+                                          else "algorithmic FLOPs of the reference path / dense 16-bit MFMA peak")}
+            # the ceiling of THIS device on this lease, after the timed region: a bare 16-bit MFMA loop on every CU settles
+            # where the package power cap lets it (MI355X, 1400 W: 1.7-1.8 GHz = 1.7-1.8 PFLOP/s)
+            if not f32:
+                try:
+                    s_tf, s_ghz = eng.mfma_sustained(300)
+                    sustained = {"tflops": s_tf, "ghz": s_ghz, "what": "bare v_mfma_f32_32x32x16 loop on random operands, "
+                                 "every CU, 0.3 s, after the timed region (csrc/diag.hip)"}
+                except Exception as e:  # noqa: BLE001 - a diagnostic never fails the bench line
+                    sustained = {"error": "%s: %s" % (type(e).__name__, e)}
+                res["roofline"]["sustained_peak"] = sustained
+                if sustained.get("tflops"):
+                    res["roofline"]["frac_of_sustained"] = ach / (sustained["tflops"] / (3.0 if x3 else 1.0))
         if ensemble:
             n_cand = (wrapper.n_trials * len(wrapper.skip_steps) * len(wrapper.encoder_unconditional_guidance_scales) *
                       len(wrapper.decoder_unconditional_guidance_scales))
@@ -766,7 +781,8 @@ def main():
             if n_cand != full:  # a subset (--trials): the line's value is per image of THIS subset; scale by candidates
                 res["config"]["ensemble"]["images_per_s_at_540_candidates"] = ips * n_cand / full
                 res["config"]["flop_per_image"] = wl["flop_per_image"] * n_cand / full
-                res["roofline"]["whole_path_frac"] = ips * res["config"]["flop_per_image"] / 1e12 / (world * peak)
+                if a.full:
+                    res["roofline"]["whole_path_frac"] = ips * res["config"]["flop_per_image"] / 1e12 / (world * peak)
         if single_dt is not None:
             sv = a.single_steps * B * world / single_dt
             res["single_batch_value"] = sv  # images/s with ONE batch of B per launch set (`--coalesce 1`)
@@ -774,10 +790,10 @@ def main():
                                    "coupled_loop": single_coupled,
                                    "ms_per_step": 1e3 * single_dt / a.single_steps, "images_in_flight_per_gpu": B,
                                    "whole_path_frac": sv * wl["flop_per_image"] / 1e12 / (world * peak)}
-        if (world == 1 and not a.no_bf16 and a.workload == "c2" and not (f32 or x3) and fmt == "fp16"
+        if (a.full and world == 1 and not a.no_bf16 and a.workload == "c2" and not (f32 or x3) and fmt == "fp16"
                 and not os.environ.get("CYCLEDIFF_LIB") and not dist.is_initialized()):
             res["bf16"] = bf16_leg()
-        if world == 1 and not a.no_cpu_baseline and a.workload == "c2":
+        if a.full and world == 1 and not a.no_cpu_baseline and a.workload == "c2":
             ref = cpu_baseline_reference()
             if ref is not None:  # the reference itself; the oracle port's forward-extrapolated figure beside it
                 port = cpu_baseline(eng, wrapper.unet, wrapper.vae, quick=True)

@@ -13,7 +13,7 @@ for K in 0 1 0 1; do
   echo "korder $K: $(grep 'B=32' $OUT/unet_b32_k$K.txt) $(grep '\[conv_gemm\]' $OUT/unet_b32_k$K.txt)"
 done
 for K in 0 1; do
-  CYCLEDIFF_KORDER=$K timeout 900 python bench.py --steps 8 --warmup 8 --no-cpu-baseline --no-single-batch > $OUT/bench_k$K.json 2> $OUT/bench_k$K.err; echo "korder $K: $(tail -1 $OUT/bench_k$K.json | cut -c1-150)"
+  CYCLEDIFF_KORDER=$K timeout 900 python bench.py --full --steps 8 --warmup 8 --no-cpu-baseline --no-single-batch > $OUT/bench_k$K.json 2> $OUT/bench_k$K.err; echo "korder $K: $(tail -1 $OUT/bench_k$K.json | cut -c1-150)"
 done
 cd /tmp
 for K in 0 1; do

@@ -11,5 +11,5 @@ done
 for v in prev new_k1; do
   L=cycle-diffusion_amd/lib/libcyclediff.so
   [ $v = prev ] && L=cycle-diffusion_amd/lib/libcyclediff_prev.so
-  CYCLEDIFF_LIB=$PWD/$L timeout 900 python bench.py --steps 8 --warmup 8 --no-cpu-baseline --no-single-batch > $OUT/bench_$v.json 2> $OUT/bench_$v.err; echo "$v: $(tail -1 $OUT/bench_$v.json | cut -c1-140)"
+  CYCLEDIFF_LIB=$PWD/$L timeout 900 python bench.py --full --steps 8 --warmup 8 --no-cpu-baseline --no-single-batch > $OUT/bench_$v.json 2> $OUT/bench_$v.err; echo "$v: $(tail -1 $OUT/bench_$v.json | cut -c1-140)"
 done

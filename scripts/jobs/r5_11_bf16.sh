@@ -11,4 +11,4 @@ import json
 for row in json.load(open('gpurun_out/parity_report.json')):
     print(row['name'], {k: round(v,3) for k,v in row.items() if isinstance(v,float) and 'psnr' in k})
 PY
-timeout 900 python bench.py --steps 16 --warmup 0 --no-cpu-baseline --no-single-batch > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; tail -1 $OUT/bench_bf16.json | cut -c1-200
+timeout 900 python bench.py --full --steps 16 --warmup 0 --no-cpu-baseline --no-single-batch > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; tail -1 $OUT/bench_bf16.json | cut -c1-200

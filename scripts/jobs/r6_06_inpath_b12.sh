@@ -9,5 +9,5 @@ timeout 2400 python scripts/inpath_tune.py $OUT/tune_inpath_b12.txt $OUT/inpath_
 head -1 $OUT/inpath_b12_report.txt
 for t in new old new old; do
   if [ $t = new ]; then export CYCLEDIFF_TUNE_DEFAULT=$OUT/tune_inpath_b12.txt; else unset CYCLEDIFF_TUNE_DEFAULT; fi
-  timeout 900 python bench.py --coalesce 1 --steps 4 --warmup 1 --no-cpu-baseline --no-bf16 --no-single-batch > $OUT/bench_c1_$t.json 2> $OUT/err.txt; echo "table $t: $(tail -1 $OUT/bench_c1_$t.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['achieved'])")"
+  timeout 900 python bench.py --full --coalesce 1 --steps 4 --warmup 1 --no-cpu-baseline --no-bf16 --no-single-batch > $OUT/bench_c1_$t.json 2> $OUT/err.txt; echo "table $t: $(tail -1 $OUT/bench_c1_$t.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['achieved'])")"
 done

@@ -13,6 +13,6 @@ export CYCLEDIFF_TILE_GROUP=8 CYCLEDIFF_TILE_GROUP_MIN_N=2048
 bash scripts/profile_unet_pmc_by_shape.sh 64 > $OUT/pmc_g8.log 2>&1; tail -14 $OUT/pmc_g8.log | cut -c1-140
 cp gpurun_out/prof_pmc/conv_gemm_traffic_by_shape_b64.json $OUT/conv_gemm_traffic_by_shape_b64_group8.json
 for g in 8 0 8 0; do
-  CYCLEDIFF_TILE_GROUP=$g timeout 900 python bench.py --steps 16 --warmup 0 --no-cpu-baseline --no-bf16 --no-single-batch > $OUT/bench_g${g}_$RANDOM.json 2> $OUT/err.txt
+  CYCLEDIFF_TILE_GROUP=$g timeout 900 python bench.py --full --steps 16 --warmup 0 --no-cpu-baseline --no-bf16 --no-single-batch > $OUT/bench_g${g}_$RANDOM.json 2> $OUT/err.txt
   echo "bench group $g: $(ls -t $OUT/bench_g${g}_*.json | head -1 | xargs tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['achieved'])")"
 done

@@ -8,7 +8,7 @@ for i in 1 2; do
   CYCLEDIFF_LIB=$OLD CYCLEDIFF_GEMM_LOG=1 timeout 300 python scripts/bench_unet.py 64 4 gemmlog > $OUT/unet_b64_old_$i.txt 2>&1; echo "old: $(grep 'launches' $OUT/unet_b64_old_$i.txt | head -1)"; grep "act3" $OUT/unet_b64_old_$i.txt | cut -c1-130
 done
 for i in 1 2; do
-  timeout 900 python bench.py --steps 16 --warmup 0 --no-cpu-baseline --no-bf16 --single-steps 3 > $OUT/bench_new_$i.json 2> $OUT/err.txt; echo "new $(tail -1 $OUT/bench_new_$i.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['achieved'], d['single_batch_value'])")"
-  CYCLEDIFF_LIB=$OLD timeout 900 python bench.py --steps 16 --warmup 0 --no-cpu-baseline --no-bf16 --single-steps 3 > $OUT/bench_old_$i.json 2> $OUT/err.txt; echo "old $(tail -1 $OUT/bench_old_$i.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['achieved'], d['single_batch_value'])")"
+  timeout 900 python bench.py --full --steps 16 --warmup 0 --no-cpu-baseline --no-bf16 --single-steps 3 > $OUT/bench_new_$i.json 2> $OUT/err.txt; echo "new $(tail -1 $OUT/bench_new_$i.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['achieved'], d['single_batch_value'])")"
+  CYCLEDIFF_LIB=$OLD timeout 900 python bench.py --full --steps 16 --warmup 0 --no-cpu-baseline --no-bf16 --single-steps 3 > $OUT/bench_old_$i.json 2> $OUT/err.txt; echo "old $(tail -1 $OUT/bench_old_$i.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['achieved'], d['single_batch_value'])")"
 done
 timeout 900 python -m pytest tests/test_gpu_e2e_fullsize.py -x -q -m gpu -k "end_to_end_vs_reference" > $OUT/pytest_e2e.log 2>&1; echo "e2e rc=$?"; tail -3 $OUT/pytest_e2e.log

@@ -7,7 +7,7 @@ timeout 1500 python -m pytest tests/test_gpu_ops.py -x -q -m gpu > $OUT/pytest.l
 for i in 1 2; do
   for v in prod ntst ntld; do
     if [ $v = prod ]; then unset CYCLEDIFF_LIB; else export CYCLEDIFF_LIB=$L/libcyclediff_$v.so; fi
-    timeout 900 python bench.py --steps 16 --warmup 0 --no-cpu-baseline --no-bf16 --single-steps 3 > $OUT/bench_${v}_$i.json 2> $OUT/bench_${v}_$i.err; echo "$v $(tail -1 $OUT/bench_${v}_$i.json | cut -c1-140)"
+    timeout 900 python bench.py --full --steps 16 --warmup 0 --no-cpu-baseline --no-bf16 --single-steps 3 > $OUT/bench_${v}_$i.json 2> $OUT/bench_${v}_$i.err; echo "$v $(tail -1 $OUT/bench_${v}_$i.json | cut -c1-140)"
   done
 done
 unset CYCLEDIFF_LIB

@@ -9,5 +9,5 @@ timeout 2400 python scripts/inpath_tune.py $OUT/tune_inpath.txt $OUT/inpath_repo
 head -1 $OUT/inpath_report.txt
 for t in new old new old; do
   if [ $t = new ]; then export CYCLEDIFF_TUNE_DEFAULT=$OUT/tune_inpath.txt; else unset CYCLEDIFF_TUNE_DEFAULT; fi
-  timeout 900 python bench.py --steps 16 --warmup 0 --no-cpu-baseline --no-bf16 --no-single-batch > $OUT/bench_$t.json 2> $OUT/err.txt; echo "table $t: $(tail -1 $OUT/bench_$t.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['achieved'])")"
+  timeout 900 python bench.py --full --steps 16 --warmup 0 --no-cpu-baseline --no-bf16 --no-single-batch > $OUT/bench_$t.json 2> $OUT/err.txt; echo "table $t: $(tail -1 $OUT/bench_$t.json | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['roofline']['achieved'])")"
 done

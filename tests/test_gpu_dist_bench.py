@@ -26,7 +26,7 @@ def test_bench_under_torchrun_world1_rccl():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist",
-           "--steps", "1", "--warmup", "1", "--coalesce", "1", "--no-cpu-baseline"]
+           "--steps", "1", "--warmup", "1", "--coalesce", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{") and '"metric"' in l][-1]
@@ -48,3 +48,6 @@ def test_bench_self_launch_as_one_command_rccl():
     res = json.loads(line)
     assert res["n_gpus"] == 1 and res["value"] > 0
     assert res["config"]["distributed"] == "nccl(RCCL) process group"
+    # a plain run (no --full) prints the headline and nothing that takes runs of its own
+    assert res["ms_per_step"] > 0 and res["unit"] == "images/s" and res["higher_is_better"] is True
+    assert not {"roofline", "single_batch", "bf16", "cpu_baseline"} & set(res)
