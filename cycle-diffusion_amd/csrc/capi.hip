@@ -638,6 +638,38 @@ int cd_ddim_decode_v(cd_handle h, int net, int sched_kind, const float* z, int z
   CD_API_END
 }
 
+// Deterministic DDIM inversion (DDIB's encoder): DiffusionCLIP's denoising_step(..., eta=0, sampling_type='ddim') walked with
+// t_next > t (model/lib/ddpm_ddim/utils/diffusion_utils.py:114-121). With eta = 0 that step is
+//   x0_hat = (x - sqrt(1-a_in)*e)/sqrt(a_in) ;  x <- sqrt(a_out)*x0_hat + sqrt(1-a_out)*e
+// which is k_decode_step_ddim with sigma = 0 in the same operation order (a sigma = 0 row draws no noise and adds +0), so the
+// decode kernel - including its fused write of the next forward's input - runs every step. Rows are in loop order: row j is
+// step j, its `t` the timestep of the input's level.
+int cd_ddim_invert(cd_handle h, int net, int sched_kind, const float* x0, const float* ctx_c, const float* ctx_uc,
+                   int ctx_len, float guidance, int B, int K, const cd_step_coef* coef_host, float* x_out,
+                   float* traj_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x0 && coef_host && x_out && B > 0 && K > 0, "bad argument");
+  CD_CHECK(sched_kind == CD_SCHED_DDIM, "inversion is only defined for sched_kind = CD_SCHED_DDIM (eta = 0)");
+  for (int j = 0; j < K; ++j)
+    CD_CHECK(coef_host[j].sigma == 0.f && coef_host[j].sa > 0.f, "inversion row %d: sigma must be 0 and sa > 0", j);
+  ArenaScope arena_scope(h->arena);
+  SamplerState s = setup_sampler(h, net, ctx_c, ctx_uc, ctx_len, guidance, B);
+  s.tab = upload_coef(h, coef_host, K);
+  const int64_t n = (int64_t)B * s.C * s.HW;
+  HIP_CHECK(hipMemcpyAsync(s.xt, x0, (size_t)n * 4, hipMemcpyDeviceToDevice, h->st));
+  if (!s.f32) launch_nchw_to_nhwc(h->st, s.xt, s.xin, B, s.C, s.HW, s.cpad, 1.f, 0.f, s.cfg ? 1 : 0);
+  for (int j = 0; j < K; ++j) {
+    run_unet(h, s, j);
+    launch_decode_step(h->st, CD_SCHED_DDIM, s.xt, s.ehv, nullptr, 0, nullptr, 0, (uint32_t)(0x3000 + j), B, s.C, s.HW,
+                       s.tab, nullptr, j, s.xin16(), s.cpad, s.cfg ? 1 : 0, nullptr);
+    if (traj_out) HIP_CHECK(hipMemcpyAsync(traj_out + (int64_t)j * n, s.xt, (size_t)n * 4, hipMemcpyDeviceToDevice, h->st));
+    h->pacer.tick(h->st);
+  }
+  HIP_CHECK(hipMemcpyAsync(x_out, s.xt, (size_t)n * 4, hipMemcpyDeviceToDevice, h->st));
+  CD_API_END
+}
+
 // The coupled source -> target loop (north_star): DPM-Encoder step k and decode step k evaluate the SAME network at the SAME
 // timestep, and the decode step only needs eps_k AFTER its forward - so both ride in one U-Net batch
 //   [ encoder rows (B, or uncond B | cond B under encoder guidance) | decoder rows (Bd = n_dec * B, or uncond Bd | cond Bd) ]

@@ -151,10 +151,14 @@ __global__ void k_decode_step_ddim(float* __restrict__ x, const float* __restric
     float e = load_eps_hat(eh, eh_sb, eh_sc, eh_sp, b, c, p, B, cfg, gvec ? gvec[b] : g);
     float px0 = (xv - co.r * e) / co.sa;
     float dir = co.dirc * e;
-    float nz;
-    if (eps) nz = eps[(int64_t)(eps_bmod ? b % eps_bmod : b) * eps_bstride + rem];
-    else nz = noise ? noise[i] : philox_normal(seed, stream, (uint64_t)i);
-    float nn = co.sigma * nz;
+    // sigma == 0 (eta = 0 tables: DDIB's inversion and decode) reads and draws no noise: the term is +0 either way
+    float nn = 0.f;
+    if (co.sigma != 0.f) {
+      float nz;
+      if (eps) nz = eps[(int64_t)(eps_bmod ? b % eps_bmod : b) * eps_bstride + rem];
+      else nz = noise ? noise[i] : philox_normal(seed, stream, (uint64_t)i);
+      nn = co.sigma * nz;
+    }
     float xn = co.sap * px0 + dir + nn;
     x[i] = xn;
     if (x0_pred) x0_pred[i] = px0;

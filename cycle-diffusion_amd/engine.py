@@ -423,6 +423,23 @@ class Engine:
             self._keep = g  # the launches read it asynchronously
         return x
 
+    def ddim_invert(self, net, x0, coef, ctx_c=None, ctx_uc=None, guidance=1.0, trajectory=False):
+        """cd_ddim_invert: deterministic DDIM inversion (DDIB's encoder) over the K rows of `coef` (loop order, sigma 0:
+        DDIMSchedule.coef_invert / PixelSchedule.coef_invert). Returns x_K [B, C, H, W], or (x_K, [K, B, C, H, W] of every
+        step's x) with trajectory=True."""
+        x0 = self._f32(x0)
+        K = len(coef)
+        coef = np.ascontiguousarray(coef)
+        x = torch.empty_like(x0)
+        traj = torch.empty((K,) + tuple(x0.shape), device=x0.device, dtype=torch.float32) if trajectory else None
+        L = ctx_c.shape[1] if ctx_c is not None else (ctx_uc.shape[1] if ctx_uc is not None else 0)
+        check(self.lib.cd_ddim_invert(self.h, net, _ffi.CD_SCHED_DDIM, ptr(x0),
+                                      ptr(self._f32(ctx_c)) if ctx_c is not None else None,
+                                      ptr(self._f32(ctx_uc)) if ctx_uc is not None else None,
+                                      L, C.c_float(guidance), x0.shape[0], K, C.c_void_p(coef.ctypes.data), ptr(x),
+                                      ptr(traj)))
+        return (x, traj) if trajectory else x
+
     def cycle_translate(self, net, kind, x0, coef_enc, coef_dec, enc_ctx_c=None, enc_ctx_uc=None, enc_guidance=1.0,
                         dec_ctx_c=None, dec_ctx_uc=None, dec_guidance=1.0, n_dec=1, noise=None, seed=0, last_uses_x0=True):
         """The coupled loop (cd_cycle_translate): dpm_encode and ddim_decode of the same network over the whole chain with ONE

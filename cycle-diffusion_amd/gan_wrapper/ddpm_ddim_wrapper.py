@@ -72,12 +72,7 @@ class DDPMDDIMWrapper(torch.nn.Module):
         self.refine_steps, self.refine_iterations = refine_steps, refine_iterations
         self.sample_type, self.eta = sample_type, eta
         self.t_0 = t_0 if t_0 is not None else 999
-        if sample_type == "ddim":
-            assert eta > 0
-        elif sample_type == "ddpm":
-            assert eta is None
-        else:
-            raise ValueError()
+        self._check_eta(sample_type, eta)
         if source_model_type not in MODEL_TYPES:
             raise NotImplementedError(source_model_type)
         arch, default_path = MODEL_TYPES[source_model_type]
@@ -99,6 +94,16 @@ class DDPMDDIMWrapper(torch.nn.Module):
         self.sched = schedule.PixelSchedule(custom_steps, es_steps, sample_type=sample_type, eta=eta, t_0=self.t_0,
                                             refine_steps=refine_steps)
         self._anchor = torch.nn.Parameter(torch.zeros(1, device=self.engine.device), requires_grad=True)
+
+    @staticmethod
+    def _check_eta(sample_type, eta):
+        """the reference's check (ddpm_ddim_wrapper.py:332-337): 'ddim' takes eta > 0, 'ddpm' none"""
+        if sample_type == "ddim":
+            assert eta > 0
+        elif sample_type == "ddpm":
+            assert eta is None
+        else:
+            raise ValueError()
 
     def _randn(self, n, shape):
         if self.noise_source is not None:
@@ -139,12 +144,17 @@ class DDPMDDIMWrapper(torch.nn.Module):
         last = self._randn(1, tuple(zz[:, 0].shape))  # denoising_step's randn_like
         x = self.engine.ddim_decode(self.net, self.sched.kind, zz, self.sched.coef_decode(),
                                     n_eps=self.es_steps - 1, noise_tail=last)
+        x = self._refine(x)
+        self._range_guard()
+        return x
+
+    def _refine(self, x):
+        """the stochastic refinement after the chain (ddpm_ddim_wrapper.py:431-453), if refine_steps > 0"""
         if self.refine_steps:
             assert self.refine_steps < self.custom_steps
             for _ in range(self.refine_iterations):
                 nz = self._randn(self.refine_steps + 1, tuple(x.shape))
                 x = self.engine.pix_refine(self.net, self.sched.kind, x, self.sched.coef_refine(), noise=nz)
-        self._range_guard()
         return x
 
     def forward(self, z, class_label=None):

@@ -132,8 +132,7 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                 raise RuntimeError("no text encoder: pass cond_stage / text_encoder, or load a checkpoint that has one")
             cond_stage = StandInTextEmbedder(udesc.context_dim)
         self.cond_stage = cond_stage
-        n_candidates = (n_trials or 1) * len(skip_steps or [0]) * len(encoder_unconditional_guidance_scales or [1]) * \
-            len(decoder_unconditional_guidance_scales or [1])
+        n_candidates = self._ensemble_size()
         if ranker is None and n_candidates > 1:
             # the reference builds its DirectionalCLIP unconditionally (sd_wrapper:140) and uses it when there is more
             # than one candidate (:213-235): an ensemble config needs no extra key here either
@@ -199,9 +198,14 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
             groups[k].append(i)
         return [groups[k] for k in order]
 
+    def _ensemble_size(self):
+        """candidates per sample: trial x encoder scale x skip x decoder scale (sd_wrapper:155-166, 186-204)"""
+        return (self.n_trials or 1) * len(self.skip_steps or [0]) * len(self.encoder_unconditional_guidance_scales or [1]) * \
+            len(self.decoder_unconditional_guidance_scales or [1])
+
     # ---- encode (sd_wrapper:169-206)
-    def _encode_front(self, image, encode_text):
-        """first stage, conditioning and the members' noise in the reference's draw order -> (x0, c, uc, members)"""
+    def _first_stage(self, image):
+        """z0 = scale * E(2 * image - 1), the posterior sampled (its noise drawn first, on the CPU) or its mean"""
         image = (image - 0.5) * 2.0
         assert image.shape[2] == image.shape[3] == self.resolution
         image = image.to(self.device, torch.float32)
@@ -215,6 +219,12 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         x0 = torch.cat([self.engine.vae_encode(self.vae, image[i:i + per], noise=None if noise is None else noise[i:i + per],
                                                sample=self.SAMPLE_POSTERIOR, scale=self.SCALE_FACTOR)
                         for i in range(0, bsz, per)], 0)
+        return x0
+
+    def _encode_front(self, image, encode_text):
+        """first stage, conditioning and the members' noise in the reference's draw order -> (x0, c, uc, members)"""
+        x0 = self._first_stage(image)
+        bsz = x0.shape[0]
         sch = self._schedule()
         assert self.eta > 0
         c, uc = self.get_condition(encode_text, bsz)
@@ -375,8 +385,7 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
 
     def _select(self, img_ensemble, original_img, encode_text, decode_text):
         """the candidate the reference returns (sd_wrapper:213-249): the only one, or per sample the directional-CLIP argmax"""
-        assert len(img_ensemble) == len(self.decoder_unconditional_guidance_scales) * \
-            len(self.encoder_unconditional_guidance_scales) * len(self.skip_steps) * self.n_trials
+        assert len(img_ensemble) == self._ensemble_size()
         if len(img_ensemble) == 1:
             return img_ensemble[0]
         if self.ranker is None:

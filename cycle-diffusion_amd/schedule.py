@@ -60,6 +60,29 @@ class DDIMSchedule:
     def coef_decode(self, skip_steps=0):
         return _pack(self._rows(len(self) - skip_steps))
 
+    def coef_invert(self, skip_steps=0):
+        """DDIB's deterministic inversion (cd_ddim_invert): K - skip rows in LOOP order. Row j takes x from the level
+        a_prev[j] to the level a[j] with eps_hat evaluated at the timestep of the input's own level (0 for j = 0, then
+        tau[j-1]) - DiffusionCLIP's denoising_step(eta=0, 'ddim') convention walked with t_next > t
+        (diffusion_utils.py:114-121): x0_hat = (x - sqrt(1-a_prev[j]) e)/sqrt(a_prev[j]),
+        x <- sqrt(a[j]) x0_hat + sqrt(1-a[j]) e."""
+        rows = []
+        for j in range(len(self) - skip_steps):
+            ai, ao = self.a_prev[j], self.a[j]
+            t = 0 if j == 0 else int(self.timesteps[j - 1])
+            rows.append((np.sqrt(ai), np.sqrt(ONE - ai), np.sqrt(ao), np.sqrt(ONE - ao), 0.0, np.sqrt(ONE - ai), 1.0, t))
+        return _pack(rows)
+
+    def coef_sdedit(self, t_enc):
+        """SDEdit (img2img): (start row, decode rows). The start row is stochastic_encode(z0, t=t_enc) (ddim.py:648-661:
+        sqrt(ddim_alphas)[t_enc], ddim_sqrt_one_minus_alphas[t_enc]) - one row, consumed by cd_dpm_encode with K = 0; the
+        decode rows are decode(t_start=t_enc)'s indices t_enc-1 .. 0 (ddim.py:663-681), stored by index as coef_decode's.
+        The noise level t_enc paired with decode indices below it is the reference's own img2img pairing."""
+        assert 1 <= t_enc <= len(self) - 1, t_enc
+        a = self.a[t_enc]
+        start = _pack([(np.sqrt(a), self.r[t_enc], 0.0, 0.0, 0.0, 0.0, 1.0, 0)])
+        return start, _pack(self._rows(t_enc))
+
     def coef_refine(self, refine_steps):
         """DDIMSampler.refine (ddim.py:114-168, 339-393) on a schedule built with eta = 1: rows 0..R-1 = the R random
         p_sample_ddim steps by `index`, row R = the re-noising to the DDIM level R - 1 (ddim.py:349-351)."""
@@ -94,7 +117,9 @@ class PixelSchedule:
     def __init__(self, custom_steps, es_steps, sample_type="ddim", eta=0.1, t_0=999, refine_steps=0,
                  beta_start=0.0001, beta_end=0.02, T=1000):
         if sample_type == "ddim":
-            assert eta is not None and eta > 0
+            # eta = 0: the deterministic tables of the DDIB baseline only (coef_invert / coef_decode_eta0); the wrapper
+            # itself keeps the reference's eta > 0 (ddpm_ddim_wrapper.py:332-333)
+            assert eta is not None and eta >= 0
         elif sample_type == "ddpm":
             assert eta is None
         else:
@@ -159,6 +184,32 @@ class PixelSchedule:
         for it, (i, j) in enumerate(pairs):
             rows[K - 1 - it] = self._row(i, j, self.eta)
         return _pack(rows)
+
+    def _row_eta0(self, i, j):
+        """denoising_step(..., eta=0, 'ddim') (diffusion_utils.py:114-117): no sigma term, sqrt(1 - at_next) direction."""
+        at = self.acp[i]
+        atn = ONE if j == -1 else self.acp[j]
+        return (np.sqrt(at), np.sqrt(ONE - at), np.sqrt(atn), np.sqrt(ONE - atn), 0.0, np.sqrt(ONE - at), 1.0, i)
+
+    def coef_invert(self):
+        """DDIB's inversion (cd_ddim_invert), DiffusionCLIP's loop: t = seq[k-1] -> t_next = seq[k] for k = 1 .. es_steps-1,
+        eta = 0; es_steps - 1 rows in LOOP order."""
+        return _pack([self._row_eta0(self.seq[k - 1], self.seq[k]) for k in range(1, len(self.seq))])
+
+    def coef_decode_eta0(self):
+        """The eta = 0 decode over the reversed pairs (DDIB's target side): es_steps rows stored by index as coef_decode's;
+        the last step goes to t_next = -1."""
+        return _pack([self._row_eta0(i, j) for i, j in zip(self.seq, self.seq_next)])
+
+    def coef_sdedit(self, strength):
+        """SDEdit on the pixel DDPMs: (i_s, start row, decode rows). i_s = int(strength * (es_steps - 1)); the start row is
+        sample_xt(x0, t=seq[i_s]) (ddpm_ddim_wrapper.py:310-314) for cd_dpm_encode with K = 0; the decode rows are
+        generate()'s chain from index i_s down (rows 0 .. i_s of coef_decode, the last one to t_next = -1)."""
+        i_s = int(strength * (self.es_steps - 1))
+        assert 0 <= i_s <= self.es_steps - 1, (strength, i_s)
+        at = self.acp[self.seq[i_s]]
+        start = _pack([(np.sqrt(at), np.sqrt(ONE - at), 0.0, 0.0, 0.0, 0.0, 1.0, 0)])
+        return i_s, start, self.coef_decode()[:i_s + 1].copy()
 
     def coef_refine(self):
         """R random DDIM(eta=1) steps after re-noising to t = refine_steps-1 (:431-453)."""

@@ -195,6 +195,17 @@ int cd_ddim_decode_v(cd_handle h, int net, int sched_kind, const float* z, int z
                      const float* ctx_c, const float* ctx_uc, int ctx_len, const float* guidance_per_sample, int B,
                      int K, const cd_step_coef* coef_host, const float* noise_tail, uint64_t seed, float* x_out);
 
+/* Deterministic DDIM inversion, the encoder of the DDIB baseline: DiffusionCLIP's denoising_step(..., eta=0,
+ * sampling_type='ddim') walked towards noise, t_next > t (model/lib/ddpm_ddim/utils/diffusion_utils.py:114-121).
+ *   x0 [B,C,H,W]; ctx_* / guidance as cd_dpm_encode's (classifier-free guidance doubles the rows, ddim.py:550-559);
+ *   coef_host: K rows in LOOP order, row j = step j: t = timestep of the input's level, sa / r = sqrt(a_in) /
+ *   sqrt(1 - a_in), sap / dirc = sqrt(a_out) / sqrt(1 - a_out), sigma = 0 (required);
+ *   step j: x0_hat = (x - r*e)/sa, x <- sap*x0_hat + dirc*e (one forward per step);
+ *   x_out [B,C,H,W] = the last x; traj_out [K,B,C,H,W] (x after every step) or NULL. sched_kind must be CD_SCHED_DDIM. */
+int cd_ddim_invert(cd_handle h, int net, int sched_kind, const float* x0, const float* ctx_c, const float* ctx_uc,
+                   int ctx_len, float guidance, int B, int K, const cd_step_coef* coef_host, float* x_out,
+                   float* traj_out);
+
 /* The coupled source -> target loop in ONE call: what Model.forward composes from the wrapper's encode() and forward()
  * (model/text_unsupervised_translation.py:24-40: z = gan_wrapper.encode(image, encode_text); img = gan_wrapper(z, ...)) when
  * both run on the same network over the whole chain (white_box_steps = custom_steps + 1): the DPM-Encoder step and the decode
