@@ -875,6 +875,18 @@ int cd_op_conv2d_16(cd_handle h, const float* x0, int C0, const float* x1, int C
   CD_API_END
 }
 
+int cd_op_last_gemm_config(cd_handle h, int* tile_id, int* bk, int* splitk, int* chm, int* tile_group) {
+  CD_API_BEGIN
+  CD_CHECK(h, "bad argument");
+  const GemmLaunchInfo li = conv_gemm_last_launch();
+  if (tile_id) *tile_id = li.tile_id;
+  if (bk) *bk = li.bk;
+  if (splitk) *splitk = li.splitk;
+  if (chm) *chm = li.chm;
+  if (tile_group) *tile_group = li.tile_group;
+  CD_API_END
+}
+
 int cd_op_groupnorm(cd_handle h, const float* x, int B, int C, int H, int W, int G, float eps,
                     const float* gamma, const float* beta, const float* film, int silu, float* y) {
   CD_API_BEGIN

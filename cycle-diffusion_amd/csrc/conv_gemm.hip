@@ -991,6 +991,13 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
 }
 
 
+// the K order a launch takes (launch_cfg below; the trace line and the read-back of launch_conv_gemm give the same answer)
+inline bool takes_channel_major(const ConvGemmParams& p) {
+  const int64_t a_bytes = (int64_t)p.B * p.Hs * p.Ws * (p.C0 + p.C1) * 2;
+  return p.korder != 0 && p.KH * p.KW > 1 && p.KH <= 8 && p.KW <= 8 && !p.up &&
+         (p.korder == 2 || (p.Hs * p.Ws >= 4096 && a_bytes >= (32ll << 20)));
+}
+
 template <int BM, int BN, int BK, int WM, int WN, int NSTAGE>
 int launch_cfg(hipStream_t st, const ConvGemmParams& p) {
   using T = TileCfg<BM, BN, BK, WM, WN, NSTAGE>;
@@ -1007,9 +1014,7 @@ int launch_cfg(hipStream_t st, const ConvGemmParams& p) {
   // level of the U-Nets from 8 samples up, the first stages) miss the 4 MiB L2 in tap-major order - there the order cuts the
   // fabric traffic by 45 % for 2 % of the conv's time (per-step offset update); on the 32 x 32 .. 8 x 8 levels the
   // activations stay L2 / Infinity-Cache resident either way and the update costs 2-7 % (profiles/r4_k_order_in_situ.txt)
-  const int64_t a_bytes = (int64_t)p.B * p.Hs * p.Ws * (p.C0 + p.C1) * 2;
-  const bool chm = p.korder != 0 && p.KH * p.KW > 1 && p.KH <= 8 && p.KW <= 8 && !p.up &&
-                   (p.korder == 2 || (p.Hs * p.Ws >= 4096 && a_bytes >= (32ll << 20)));
+  const bool chm = takes_channel_major(p);
   static PerDeviceOnce attr_once;  // engines on several host threads / devices launch the same instantiation
   auto kern0 = k_conv_gemm<BM, BN, BK, WM, WN, NSTAGE, false>;
   auto kern1 = k_conv_gemm<BM, BN, BK, WM, WN, NSTAGE, true>;
@@ -1063,6 +1068,10 @@ const CfgInfo kCfgs[] = {
 };
 inline bool cfg_needs_bk64(int id) { return id == 20 || id == 21 || id == 23; }
 constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
+// dispatch<32> below has no 8 x 1 / 4 x 4 / 8 x 2 wave grids: these ids launch another id's BK = 32 instantiation
+inline int bk32_alias(int id) { return id == 9 ? 7 : id == 13 ? 12 : id == 18 ? 5 : id == 19 ? 5 : id; }
+// ids with a single instantiation, 32 deep, whatever the channel counts
+inline bool cfg_always_bk32(int id) { return id == 24 || id == 25; }
 
 }  // namespace gemm_detail
 thread_local SplitKWorkspace g_conv_splitk;
@@ -1124,6 +1133,7 @@ int dispatch(hipStream_t st, const ConvGemmParams& p, int id) {
 }
 
 thread_local const char* g_last_cfg = "";
+thread_local GemmLaunchInfo g_last_launch;
 
 // CU count of the current device (256 on an unpartitioned MI355X; a partitioned part has fewer): "does this configuration
 // fill the chip" is asked against it, not against a literal
@@ -1157,6 +1167,7 @@ int pick_config(const ConvGemmParams& p) {
 using namespace gemm_detail;
 
 const char* conv_gemm_last_config() { return g_last_cfg; }
+GemmLaunchInfo conv_gemm_last_launch() { return g_last_launch; }
 
 thread_local KernelProfiler* g_conv_prof = nullptr;
 
@@ -1395,13 +1406,21 @@ void launch_conv_gemm(hipStream_t st, const ConvGemmParams& p) {
   if (p.act == ACT_GEGLU && (ci->TN % 64) != 0) { id = 2; ci = &kCfgs[1]; }
   if (cfg_needs_bk64(id)) CD_CHECK(k64, "conv_gemm: tile configuration %d needs channel counts that are multiples of 64", id);
   g_last_cfg = ci->name;
+  {  // read-back for the tests (cd_op_last_gemm_config): what is launched below, not what was asked for
+    GemmLaunchInfo li;
+    const bool lin = id == kLinStreamTile;
+    li.bk = (lin || (k64 && !cfg_always_bk32(id))) ? 64 : 32;
+    li.tile_id = li.bk == 32 ? bk32_alias(id) : id;
+    li.splitk = pk.splitk > 1 ? pk.splitk : 1;
+    li.chm = !lin && takes_channel_major(pk) ? 1 : 0;
+    li.tile_group = lin ? 0 : pk.tile_group;
+    g_last_launch = li;
+  }
   // CYCLEDIFF_GEMM_TRACE=1: one line per launch, in launch order (scripts/pmc_traffic_by_shape.py matches them with the
   // dispatches of a rocprofv3 counter pass: M N K KH stride up cat nbatch act resid out_f32 chm | tile)
   static const bool trace = [] { const char* e = getenv("CYCLEDIFF_GEMM_TRACE"); return e && e[0] == '1'; }();
   if (trace) {
-    const int64_t a_bytes = (int64_t)p.B * p.Hs * p.Ws * Ctot * 2;
-    const bool chm = id != kLinStreamTile && pk.korder != 0 && p.KH * p.KW > 1 && p.KH <= 8 && p.KW <= 8 && !p.up &&
-                     (pk.korder == 2 || (p.Hs * p.Ws >= 4096 && a_bytes >= (32ll << 20)));
+    const bool chm = id != kLinStreamTile && takes_channel_major(pk);
     fprintf(stderr, "[gemm_trace] %d %d %d %d %d %d %d %d %d %d %d %d | %s x%d\n", p.M, p.N, p.Ktot, p.KH, p.stride, p.up,
             p.src1 ? 1 : 0, p.nbatch, p.act, p.resid ? 1 : 0, p.out_f32, chm ? 1 : 0, ci->name, pk.splitk > 1 ? pk.splitk : 1);
   }

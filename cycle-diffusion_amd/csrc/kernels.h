@@ -127,6 +127,15 @@ struct SplitKWorkspace {
 extern thread_local SplitKWorkspace g_conv_splitk;  // the calling thread's engine (capi.hip enter_engine)
 void launch_conv_gemm(hipStream_t st, const ConvGemmParams& p);
 const char* conv_gemm_last_config();
+// what the calling thread's most recent launch_conv_gemm ran, after every fallback (read-only; no effect on any launch)
+struct GemmLaunchInfo {
+  int tile_id = 0;     // the kCfgs id whose instantiation was launched (or kLinStreamTile)
+  int bk = 0;          // K-step depth of that instantiation: 32 or 64
+  int splitk = 1;      // effective split (1 = none)
+  int chm = 0;         // 1 = the channel-major K order was taken
+  int tile_group = 0;  // group size of the tile walk (0 = row-major)
+};
+GemmLaunchInfo conv_gemm_last_launch();
 int conv_gemm_num_configs();
 const char* conv_gemm_config_name(int id);
 

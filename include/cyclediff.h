@@ -245,6 +245,12 @@ int cd_op_conv2d_16(cd_handle h, const float* x0, int C0, const float* x1, int C
                     const void* packed_w, int N, int KH, int KW, int stride, int pad, int asym_pad, int up,
                     const float* bias, const float* rowvec, const float* resid, int act, int tile, float* y,
                     float* stats);
+/* what the calling thread's most recent implicit-GEMM launch (any convolution / linear layer, the two entry points above
+ * included) ran after every fallback of the launcher: tile_id = the tile configuration whose instantiation was launched (a
+ * configuration without a 32-deep instantiation of its own reports the one it borrows; 30 = the streaming linear kernel),
+ * bk = K-step depth (32 or 64), splitk = effective split-K factor (1 = none), chm = 1 if the channel-major K order was taken,
+ * tile_group = group size of the tile walk (0 = row-major). Read-only; any pointer may be NULL. */
+int cd_op_last_gemm_config(cd_handle h, int* tile_id, int* bk, int* splitk, int* chm, int* tile_group);
 int cd_op_groupnorm(cd_handle h, const float* x, int B, int C, int H, int W, int G, float eps,
                     const float* gamma, const float* beta, const float* film, int silu, float* y);
 int cd_op_layernorm(cd_handle h, const float* x, int rows, int C, const float* gamma, const float* beta,

@@ -75,24 +75,52 @@ def conv2d(eng, x0, w, x1=None, stride=1, pad=1, asym=False, up=False, bias=None
     return y.cpu()
 
 
-def conv2d16(eng, x0, w, stride=1, pad=1, bias=None, resid=None, act=0, tile=0, geglu=False, want_stats=False, rowvec=None):
+def conv2d16(eng, x0, w, stride=1, pad=1, bias=None, resid=None, act=0, tile=0, geglu=False, want_stats=False, rowvec=None,
+             x1=None, asym=False, up=False):
     """cd_op_conv2d_16: the convolution with the engine's 16-bit output (+ the fused GroupNorm statistics)"""
     handle, (N, Cin, KH, KW) = pack_conv(eng, w, geglu)
     B, C0, H, W = x0.shape
-    Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    C1 = x1.shape[1] if x1 is not None else 0
+    Hin, Win = (2 * H, 2 * W) if up else (H, W)
+    if asym:
+        Ho, Wo = (Hin + 1 - KH) // stride + 1, (Win + 1 - KW) // stride + 1
+    else:
+        Ho, Wo = (Hin + 2 * pad - KH) // stride + 1, (Win + 2 * pad - KW) // stride + 1
     Nout = N // 2 if geglu else N
     y = torch.empty((B, Nout, Ho, Wo), device="cuda", dtype=torch.float32)
     st = torch.zeros((B * Ho * Wo // 32, 2, Nout), device="cuda", dtype=torch.float32) if want_stats else None
     b = None
     if bias is not None:
         b = dev(geglu_pack_vec(bias) if geglu else bias)
-    xs0 = dev(x0)
+    xs0, xs1 = dev(x0), dev(x1) if x1 is not None else None
     rs = dev(resid) if resid is not None else None
     rv = dev(rowvec) if rowvec is not None else None
-    check(eng.lib.cd_op_conv2d_16(eng.h, ptr(xs0), C0, None, 0, B, H, W, handle, N, KH, KW, stride, pad, 0, 0, ptr(b),
-                                  ptr(rv), ptr(rs), act, tile, ptr(y), ptr(st)))
+    check(eng.lib.cd_op_conv2d_16(eng.h, ptr(xs0), C0, ptr(xs1), C1, B, H, W, handle, N, KH, KW, stride, pad, int(asym),
+                                  int(up), ptr(b), ptr(rv), ptr(rs), act, tile, ptr(y), ptr(st)))
     torch.cuda.synchronize()
     return (y.cpu(), st.cpu()) if want_stats else y.cpu()
+
+
+def last_gemm_config(eng):
+    """cd_op_last_gemm_config: what this thread's most recent implicit-GEMM launch ran, after the launcher's fallbacks"""
+    v = [C.c_int() for _ in range(5)]
+    check(eng.lib.cd_op_last_gemm_config(eng.h, *[C.byref(x) for x in v]))
+    return dict(zip(("tile", "bk", "split", "chm", "tile_group"), (x.value for x in v)))
+
+
+def run_conv_case(eng, c, o, tile):
+    """One case of the configuration sweep (tests/_gemm_sweep.py: case dict `c`, operands `o`) on `tile` (id | split << 8 |
+    bk32 << 16): (y, statistics or None, read-back of what ran)."""
+    kw = dict(x1=o["x1"], stride=c["stride"], pad=c["pad"], asym=c["asym"], up=c["up"], bias=o["bias"], rowvec=o["rowvec"],
+              resid=o["resid"], act=c["act"], tile=tile, geglu=c["geglu"])
+    st = None
+    if c["out16"]:
+        y = conv2d16(eng, o["x0"], o["w"], want_stats=c["stats"], **kw)
+        if c["stats"]:
+            y, st = y
+    else:
+        y = conv2d(eng, o["x0"], o["w"], **kw)
+    return y, st, last_gemm_config(eng)
 
 
 def groupnorm(eng, x, gamma, beta, eps, silu=False, film=None):
