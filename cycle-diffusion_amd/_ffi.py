@@ -16,6 +16,8 @@ CD_NET_UNET_OPENAI, CD_NET_UNET_HO, CD_NET_VAE_KL, CD_NET_CLIP_TEXT, CD_NET_BERT
 CD_NET_OCLIP_TEXT, CD_NET_OCLIP_VISION, CD_NET_INCEPTION_FID = 6, 7, 8
 CD_SCHED_DDIM, CD_SCHED_DDPM = 0, 1
 CD_PREC_16, CD_PREC_F32, CD_PREC_F32X3 = 0, 1, 2
+CD_MASK_QSAMPLE, CD_MASK_ENCODER = 0, 1
+MASK_SOURCES = {"q_sample": CD_MASK_QSAMPLE, "encoder": CD_MASK_ENCODER}
 ACT_NONE, ACT_SILU, ACT_GELU, ACT_GEGLU, ACT_QGELU, ACT_RELU = 0, 1, 2, 3, 4, 5
 
 
@@ -73,6 +75,10 @@ SIGNATURES = {
     "cd_ddim_invert": [_VP, _I, _I, _VP, _VP, _VP, _I, _F, _I, _I, _VP, _VP, _VP],
     "cd_cycle_translate": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I, _VP,
                            _VP],
+    "cd_ddim_decode_masked": [_VP, _I, _I, _VP, _I, _I, _VP, _VP, _I, _F, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP, _I, _I, _VP, _VP,
+                              _U64, _VP],
+    "cd_cycle_translate_masked": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I,
+                                  _VP, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP],
     "cd_pix_refine": [_VP, _I, _I, _VP, _I, _I, _VP, _VP, _U64],
     "cd_op_pack_conv_weight": [_VP, _VP, _I, _I, _I, _I, _I, C.POINTER(_VP), C.POINTER(_I), C.POINTER(_I)],
     "cd_op_free": [_VP, _VP],
@@ -86,6 +92,7 @@ SIGNATURES = {
     "cd_op_softmax_rows": [_VP, _VP, _I64, _I, _VP],
     "cd_op_timestep_embedding": [_VP, _VP, _I, _I, _I, _VP],
     "cd_op_sched_step": [_VP, _I, _I, _VP, _VP, _VP, _VP, _I, _F, _VP, _VP, _I, _I, _I, _I, _VP],
+    "cd_op_sched_step_masked": [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, _VP, _VP, _I, _I, _F, _F, _VP, _I, _I, _I, _I, _VP, _I],
     "cd_op_bench_conv": [_VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float)],
     "cd_op_bench_mfma_sustained": [_VP, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)],
     "cd_op_probe": [_VP, _I, _VP, _VP, _SZ],

@@ -350,10 +350,8 @@ Guidance resolve_guidance(const float* ctx_c, const float* ctx_uc, float g) {
   return r;
 }
 
-StepCoef* upload_coef(cd_engine* h, const cd_step_coef* host, int n) {
-  static_assert(sizeof(cd_step_coef) == sizeof(StepCoef), "coef ABI");
-  const size_t bytes = (size_t)n * sizeof(StepCoef);
-  StepCoef* d = (StepCoef*)h->arena.alloc(bytes);
+void* upload_table(cd_engine* h, const void* host, size_t bytes) {
+  void* d = h->arena.alloc(bytes);
   CoefStaging& cs = h->coef_staging;
   if (cs.host && bytes <= CoefStaging::kSlotBytes) {
     const int slot = cs.next;
@@ -368,6 +366,51 @@ StepCoef* upload_coef(cd_engine* h, const cd_step_coef* host, int n) {
     HIP_CHECK(hipStreamSynchronize(h->st));  // host table may be freed by the caller right after return
   }
   return d;
+}
+
+StepCoef* upload_coef(cd_engine* h, const cd_step_coef* host, int n) {
+  static_assert(sizeof(cd_step_coef) == sizeof(StepCoef), "coef ABI");
+  return (StepCoef*)upload_table(h, host, (size_t)n * sizeof(StepCoef));
+}
+
+// Arguments of the region-keeping decode (cd_ddim_decode_masked / cd_cycle_translate_masked), checked on the host before
+// any launch. `B` is the decoder's batch.
+struct MaskArgs {
+  const float* mask = nullptr;        // [B_mask, 1, H, W]
+  const float* x0 = nullptr;          // [B_mask, C, H, W] ("q_sample")
+  int B_mask = 0;
+  int source = CD_MASK_QSAMPLE;
+  const float* qcoef_host = nullptr;  // K x (qa, qb)
+  const float* noise = nullptr;       // [K, B, C, H, W] or NULL -> Philox(seed)
+  uint64_t seed = 0;
+};
+
+void check_mask_args(const MaskArgs& m, UNet* u, int sched_kind, int B, bool coupled) {
+  CD_CHECK(sched_kind == CD_SCHED_DDIM, "a keep-mask is only defined for sched_kind = CD_SCHED_DDIM (the reference has no mask "
+                                        "hook on DDPMDDIMWrapper)");
+  CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer,
+           "a keep-mask is only defined for the latent text networks, not for the pixel networks");
+  CD_CHECK(m.mask, "mask is NULL");
+  CD_CHECK(m.B_mask > 0 && B % m.B_mask == 0, "mask shape mismatch: %d mask rows for a batch of %d", m.B_mask, B);
+  if (m.source == CD_MASK_ENCODER) {
+    CD_CHECK(coupled, "mask_source = encoder needs the coupled loop (cd_cycle_translate_masked): the encoder's trajectory "
+                      "does not exist in a separate decode");
+    CD_CHECK(!m.qcoef_host && !m.noise, "mask_source = encoder takes no q-sample table and no mask noise: pass NULL");
+  } else {
+    CD_CHECK(m.source == CD_MASK_QSAMPLE, "bad mask_source %d", m.source);
+    CD_CHECK(m.x0 && m.qcoef_host, "mask_source = q_sample needs x0 and the q-sample coefficient table");
+  }
+}
+
+// the blend of level k (table row k) whose q-sample draw is slot `slot` (the loop's iteration number)
+MaskBlend mask_blend_of(const MaskArgs& m, const float2* qtab, int k, int slot, int64_t n) {
+  MaskBlend b;
+  b.mask = m.mask; b.mask_bmod = m.B_mask;
+  b.src = m.x0; b.src_bmod = m.B_mask;
+  b.qtab = qtab; b.qrow = k;
+  b.noise = m.noise ? m.noise + (int64_t)slot * n : nullptr;
+  b.seed = m.seed; b.stream = (uint32_t)(0x4000 + slot);
+  return b;
 }
 
 struct SamplerState {
@@ -587,8 +630,9 @@ int cd_dpm_encode(cd_handle h, int net, int sched_kind, const float* x0, const f
 static void ddim_decode_impl(cd_handle h, int net, int sched_kind, const float* z, int z_slots, int n_eps,
                              const float* ctx_c, const float* ctx_uc, int ctx_len, float guidance, const float* gvec,
                              int B, int K, const cd_step_coef* coef_host, const float* noise_tail, uint64_t seed,
-                             float* x_out) {
+                             float* x_out, const MaskArgs* mk = nullptr) {
   CD_CHECK(h && z && coef_host && x_out && B > 0 && K > 0 && n_eps <= z_slots - 1, "bad argument");
+  if (mk) check_mask_args(*mk, get_unet(h, net), sched_kind, B, /*coupled=*/false);
   ArenaScope arena_scope(h->arena);
   SamplerState s = setup_sampler(h, net, ctx_c, ctx_uc, ctx_len, guidance, B);
   // the 'ddpm' posterior kernels carry no classifier-free-guidance combine (the pixel DDPMs that use them are unconditional,
@@ -603,12 +647,20 @@ static void ddim_decode_impl(cd_handle h, int net, int sched_kind, const float* 
   const int64_t zbs = (int64_t)z_slots * chw;
   // x = z[:, 0]  (sd_wrapper:153; ddpm_ddim_wrapper.py:404)
   HIP_CHECK(hipMemcpy2DAsync(s.xt, chw * 4, z, zbs * 4, chw * 4, B, hipMemcpyDeviceToDevice, h->st));
-  if (!s.f32) launch_nchw_to_nhwc(h->st, s.xt, s.xin, B, s.C, s.HW, s.cpad, 1.f, 0.f, s.cfg ? 1 : 0);
+  const float2* qtab = nullptr;
+  if (mk) {  // img = q_sample(x0, ts) * mask + (1. - mask) * img ahead of the first forward too (ddim.py:427-430)
+    qtab = (const float2*)upload_table(h, mk->qcoef_host, (size_t)K * 2 * sizeof(float));
+    launch_mask_blend_init(h->st, s.xt, mask_blend_of(*mk, qtab, K - 1, 0, n), B, s.C, s.HW, s.xin16(), s.cpad, s.cfg ? 1 : 0);
+  } else if (!s.f32) launch_nchw_to_nhwc(h->st, s.xt, s.xin, B, s.C, s.HW, s.cpad, 1.f, 0.f, s.cfg ? 1 : 0);
   for (int i = 0; i < K; ++i) {
     const int k = K - 1 - i;
     run_unet(h, s, k);
     const float* eps = (i < n_eps) ? z + (int64_t)(1 + i) * chw : nullptr;
     const float* nz = (!eps && noise_tail) ? noise_tail + (int64_t)(i - n_eps) * n : nullptr;
+    if (mk)
+      launch_decode_step_masked(h->st, s.xt, s.ehv, eps, zbs, nz, seed, (uint32_t)(0x1000 + i), B, s.C, s.HW, s.tab, nullptr, k,
+                                s.xin16(), s.cpad, s.cfg ? 1 : 0, 0, mask_blend_of(*mk, qtab, k - 1, i + 1, n), k > 0 ? 1 : 0);
+    else
     launch_decode_step(h->st, sched_kind, s.xt, s.ehv, eps, zbs, nz, seed, (uint32_t)(0x1000 + i), B, s.C,
                        s.HW, s.tab, nullptr, k, s.xin16(), s.cpad, s.cfg ? 1 : 0, nullptr);
     h->pacer.tick(h->st);
@@ -635,6 +687,25 @@ int cd_ddim_decode_v(cd_handle h, int net, int sched_kind, const float* z, int z
   // any scale other than 0 / 1 selects the [uncond | cond] batch (ddim.py:550-559); the vector supplies the values
   ddim_decode_impl(h, net, sched_kind, z, z_slots, n_eps, ctx_c, ctx_uc, ctx_len, 2.0f, guidance_per_sample, B, K,
                    coef_host, noise_tail, seed, x_out);
+  CD_API_END
+}
+
+// Region-keeping decode: DDIMSampler.sample_with_eps(mask=, x0=) (ddim.py:170-228, 427-430). One launch per sampler step: the
+// blend ahead of the forward of level k-1 is the tail of decode step k (sched.hip k_decode_step_ddim_masked).
+int cd_ddim_decode_masked(cd_handle h, int net, int sched_kind, const float* z, int z_slots, int n_eps, const float* ctx_c,
+                          const float* ctx_uc, int ctx_len, float guidance, const float* guidance_per_sample, int B, int K,
+                          const cd_step_coef* coef_host, const float* noise_tail, uint64_t seed, const float* mask,
+                          const float* x0, int B_mask, int mask_source, const float* qsample_coef_host,
+                          const float* mask_noise, uint64_t mask_seed, float* x_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h, "bad argument");
+  MaskArgs mk;
+  mk.mask = mask; mk.x0 = x0; mk.B_mask = B_mask; mk.source = mask_source; mk.qcoef_host = qsample_coef_host;
+  mk.noise = mask_noise; mk.seed = mask_seed;
+  if (guidance_per_sample) CD_CHECK(ctx_c && ctx_uc, "cd_ddim_decode_masked: a guidance vector needs both contexts");
+  ddim_decode_impl(h, net, sched_kind, z, z_slots, n_eps, ctx_c, ctx_uc, ctx_len, guidance_per_sample ? 2.0f : guidance,
+                   guidance_per_sample, B, K, coef_host, noise_tail, seed, x_out, &mk);
   CD_API_END
 }
 
@@ -675,17 +746,16 @@ int cd_ddim_invert(cd_handle h, int net, int sched_kind, const float* x0, const 
 //   [ encoder rows (B, or uncond B | cond B under encoder guidance) | decoder rows (Bd = n_dec * B, or uncond Bd | cond Bd) ]
 // followed by the encoder's step kernel (x_{k-1}, eps_k -> z) and then the decoder's (consumes eps_k). 99 forwards of
 // B + 2 Bd rows instead of 99 of B and 99 of 2 Bd. Per-sample arithmetic is that of cd_dpm_encode followed by cd_ddim_decode(_v).
-int cd_cycle_translate(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
+static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
                        const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
                        float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
                        const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                       uint64_t seed, int last_uses_x0, float* z_out, float* x_out) {
-  CD_API_BEGIN
-  enter_engine(h);
+                       uint64_t seed, int last_uses_x0, float* z_out, float* x_out, const MaskArgs* mk) {
   CD_CHECK(h && x0 && coef_enc_host && coef_dec_host && z_out && x_out && B > 0 && n_dec > 0 && K > 0, "bad argument");
   ArenaScope arena_scope(h->arena);
   UNet* u = get_unet(h, net);
   const int Bd = B * n_dec;
+  if (mk) check_mask_args(*mk, u, sched_kind, B, /*coupled=*/true);
   const int C = u->desc.in_channels, HW = u->image_size * u->image_size, cpad = u->in_cpad, out_ld = u->out_channels;
   const bool f32 = u->f32;
   Guidance ge = resolve_guidance(enc_ctx_c, enc_ctx_uc, enc_guidance);
@@ -733,7 +803,17 @@ int cd_cycle_translate(cd_handle h, int net, int sched_kind, const float* x0, co
   launch_init_xt(h->st, x0, noise, seed, 0u, xt_e, z_out, zbs, B, C, HW, tab_e, K, xin_e, cpad, ge.cfg ? 1 : 0);
   for (int j = 0; j < n_dec; ++j)
     HIP_CHECK(hipMemcpyAsync(xt_d + (int64_t)j * n, xt_e, (size_t)n * 4, hipMemcpyDeviceToDevice, h->st));
-  if (!f32) launch_nchw_to_nhwc(h->st, xt_d, xin_d, Bd, C, HW, cpad, 1.f, 0.f, gd.cfg ? 1 : 0);
+  // the keep-mask blend of level k for the decoder rows: q_sample(x0) with the draw of iteration `slot`, or - "encoder" - the
+  // DPM-Encoder's own x_t of that level, which is what xt_e holds once the encoder's step kernel of the iteration has run
+  const float2* qtab = nullptr;
+  if (mk && mk->source == CD_MASK_QSAMPLE) qtab = (const float2*)upload_table(h, mk->qcoef_host, (size_t)K * 2 * sizeof(float));
+  auto blend_of = [&](int k, int slot) {
+    MaskBlend b = mask_blend_of(*mk, qtab, k, slot, (int64_t)Bd * chw);
+    if (mk->source == CD_MASK_ENCODER) { b.src = xt_e; b.src_bmod = B; }
+    return b;
+  };
+  if (mk) launch_mask_blend_init(h->st, xt_d, blend_of(K - 1, 0), Bd, C, HW, xin_d, cpad, gd.cfg ? 1 : 0);
+  else if (!f32) launch_nchw_to_nhwc(h->st, xt_d, xin_d, Bd, C, HW, cpad, 1.f, 0.f, gd.cfg ? 1 : 0);
   // rows that repeat the rows just ahead of them (the decoder's cond half repeats its uncond half): the network computes
   // everything ahead of the first cross-attention once for them - only when the encoder half has no such pair of its own
   const int dup_tail = (gd.cfg && !ge.cfg) ? Bd : 0;
@@ -757,11 +837,48 @@ int cd_cycle_translate(cd_handle h, int net, int sched_kind, const float* x0, co
     float* zslot = z_out + (1 + i) * chw;
     launch_encode_step(h->st, sched_kind, x0, xt_e, eh_e, nz, seed, (uint32_t)(1 + i), zslot, zbs, B, C, HW, tab_e, nullptr, k,
                        is_last, xin_e, cpad, ge.cfg ? 1 : 0);
+    if (mk)
+      launch_decode_step_masked(h->st, xt_d, eh_d, zslot, zbs, nullptr, seed, (uint32_t)(0x1000 + i), Bd, C, HW, tab_d, nullptr, k,
+                                xin_d, cpad, gd.cfg ? 1 : 0, /*eps_bmod=*/n_dec > 1 ? B : 0, blend_of(k - 1, i + 1), k > 0 ? 1 : 0);
+    else
     launch_decode_step(h->st, sched_kind, xt_d, eh_d, zslot, zbs, nullptr, seed, (uint32_t)(0x1000 + i), Bd, C, HW, tab_d,
                        nullptr, k, xin_d, cpad, gd.cfg ? 1 : 0, nullptr, /*eps_bmod=*/n_dec > 1 ? B : 0);
     h->pacer.tick(h->st);
   }
   HIP_CHECK(hipMemcpyAsync(x_out, xt_d, (size_t)Bd * chw * 4, hipMemcpyDeviceToDevice, h->st));
+}
+
+int cd_cycle_translate(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
+                       const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
+                       float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
+                       const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
+                       uint64_t seed, int last_uses_x0, float* z_out, float* x_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
+                       dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
+                       z_out, x_out, nullptr);
+  CD_API_END
+}
+
+// The coupled loop with a keep-mask on its decoder rows. mask_source = CD_MASK_ENCODER keeps the region on the source image's
+// OWN trajectory: the encoder's x_t of every level is live in the same iteration (the reference's "deterministic forward
+// pass?" TODO, ddim.py:429), no extra noise is drawn.
+int cd_cycle_translate_masked(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
+                              const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
+                              float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
+                              const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
+                              uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
+                              int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
+                              float* z_out, float* x_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  MaskArgs mk;
+  mk.mask = mask; mk.x0 = mask_x0; mk.B_mask = B_mask; mk.source = mask_source; mk.qcoef_host = qsample_coef_host;
+  mk.noise = mask_noise; mk.seed = mask_seed;
+  cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
+                       dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
+                       z_out, x_out, &mk);
   CD_API_END
 }
 
@@ -983,6 +1100,37 @@ int cd_op_sched_step(cd_handle h, int mode, int sched_kind, const cd_step_coef* 
   } else {
     launch_decode_step(h->st, sched_kind, xt, eh, eps_in, chw, noise, 0, 0, B, C, HW, tab, nullptr, 0, nullptr,
                        0, 0, nullptr);
+  }
+  HIP_CHECK(hipStreamSynchronize(h->st));
+  CD_API_END
+}
+
+// the masked step kernels on explicit tensors: mode 0 = k_mask_blend_init, 2 = k_decode_step_ddim_masked (blend = 0: last step)
+int cd_op_sched_step_masked(cd_handle h, int mode, const cd_step_coef* coef_host, float* x, const float* eps_hat, int cfg,
+                            float guidance, const float* eps_in, const float* mask, const float* src, int B_mask,
+                            int mask_source, float qa, float qb, const float* mask_noise, int blend, int B, int C, int HW,
+                            void* xin16_out, int cfg_dup) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && mask && src && B > 0 && C > 0 && HW > 0, "bad argument");
+  CD_CHECK(B_mask > 0 && B % B_mask == 0, "mask shape mismatch: %d mask rows for a batch of %d", B_mask, B);
+  CD_CHECK(mode == 0 || (coef_host && eps_hat), "bad argument");
+  ArenaScope arena_scope(h->arena);
+  const int64_t chw = (int64_t)C * HW;
+  MaskBlend mk;
+  mk.mask = mask; mk.src = src; mk.mask_bmod = mk.src_bmod = B_mask; mk.noise = mask_noise;
+  if (mask_source == CD_MASK_QSAMPLE) {
+    CD_CHECK(mask_noise, "q_sample mode needs the noise tensor here");
+    const float q[2] = {qa, qb};
+    mk.qtab = (const float2*)upload_table(h, q, sizeof(q));
+  }
+  if (mode == 0) {
+    launch_mask_blend_init(h->st, x, mk, B, C, HW, (bf16_t*)xin16_out, C, cfg_dup);
+  } else {
+    StepCoef* tab = upload_coef(h, coef_host, 1);
+    EpsHat eh; eh.p = eps_hat; eh.sb = chw; eh.sc = HW; eh.sp = 1; eh.cfg = cfg; eh.g = guidance;  // NCHW view
+    launch_decode_step_masked(h->st, x, eh, eps_in, chw, nullptr, 0, 0, B, C, HW, tab, nullptr, 0, (bf16_t*)xin16_out, C,
+                              cfg_dup, 0, mk, blend);
   }
   HIP_CHECK(hipStreamSynchronize(h->st));
   CD_API_END

@@ -42,6 +42,24 @@ void launch_decode_step(hipStream_t st, int kind, float* x, const EpsHat& eh, co
                         bf16_t* xin, int xin_cpad, int cfg_dup_next, float* x0_pred, int eps_bmod = 0);
 // eps_bmod > 0: sample b takes its injected eps from slot sample b % eps_bmod (the coupled loop decodes several guidance scales
 // of the same eps_bmod encoder samples in one batch)
+// region-keeping decode (ddim.py:427-430): what the masked step kernels blend into the decoder's latent ahead of a forward
+struct MaskBlend {
+  const float* mask = nullptr;   // [mask_bmod, 1, HW], 1 = keep the source
+  const float* src = nullptr;    // "q_sample": x0 [src_bmod, C, HW]; "encoder": the DPM-Encoder's x_t [src_bmod, C, HW]
+  int mask_bmod = 1, src_bmod = 1;
+  const float2* qtab = nullptr;  // "q_sample": (sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod)[tau[k]] by row k; else null
+  int qrow = 0;                  // row of the level being blended
+  const float* noise = nullptr;  // "q_sample": that level's draw [B, C, HW], or null -> Philox(seed, stream)
+  uint64_t seed = 0;
+  uint32_t stream = 0;
+};
+void launch_mask_blend_init(hipStream_t st, float* x, const MaskBlend& mk, int B, int C, int HW, bf16_t* xin, int xin_cpad,
+                            int cfg_dup);
+// SCHED_DDIM only; blend = 0 on the last step (nothing is blended after it)
+void launch_decode_step_masked(hipStream_t st, float* x, const EpsHat& eh, const float* eps, int64_t eps_bstride,
+                               const float* noise, uint64_t seed, uint32_t stream, int B, int C, int HW,
+                               const StepCoef* tab, const int* step_ptr, int step, bf16_t* xin, int xin_cpad,
+                               int cfg_dup_next, int eps_bmod, const MaskBlend& mk, int blend);
 void launch_set_int(hipStream_t st, int* p, int v);
 void launch_add_int(hipStream_t st, int* p, int d);
 

@@ -222,6 +222,78 @@ __global__ void k_decode_step_ddpm(float* __restrict__ x, const float* __restric
   }
 }
 
+// ---------------- region-keeping decode (DDIMSampler.ddim_sampling_with_eps(mask=, x0=), ddim.py:427-430) ----------------
+// Ahead of EVERY forward the reference replaces the running latent: img = q_sample(x0, ts) * mask + (1. - mask) * img. The
+// blend ahead of the forward of level k-1 rides in the tail of decode step k (still one launch per sampler step); the one
+// ahead of the first forward is k_mask_blend_init. fp32 operation order as written there: src*m, 1-m, (1-m)*x, then the add.
+//   qtab != nullptr ("q_sample"): src = qa*x0 + qb*n  (LatentDiffusion.q_sample, ddpm.py:271-274), n from `noise` or Philox
+//   qtab == nullptr ("encoder") : src = the DPM-Encoder's own x_t of that level, as it lies in memory
+// sample b reads mask row b % mask_bmod and source row b % src_bmod (ensemble members share their sample's mask).
+__device__ inline float mask_blend(const MaskBlend& mk, int b, int64_t chw, int HW, int64_t rem, int p, int64_t i, float xv) {
+  float m = mk.mask[(int64_t)(b % mk.mask_bmod) * HW + p];
+  float sv = mk.src[(int64_t)(b % mk.src_bmod) * chw + rem];
+  if (mk.qtab) {
+    const float2 q = mk.qtab[mk.qrow];
+    float nz = mk.noise ? mk.noise[i] : philox_normal(mk.seed, mk.stream, (uint64_t)i);
+    float a0 = q.x * sv;
+    float a1 = q.y * nz;
+    sv = a0 + a1;
+  }
+  float keep = sv * m;
+  float om = 1.f - m;
+  float free_ = om * xv;
+  return keep + free_;
+}
+
+// x <- blend(x) ahead of the first forward (x = x_T = z[:, 0]); writes the forward's 16-bit input
+__global__ void k_mask_blend_init(float* __restrict__ x, MaskBlend mk, int B, int C, int HW, bf16_t* xin, int xin_cpad,
+                                  int cfg_dup) {
+  const int64_t chw = (int64_t)C * HW, n = (int64_t)B * chw;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int b = (int)(i / chw);
+    int64_t rem = i - (int64_t)b * chw;
+    int c = (int)(rem / HW), p = (int)(rem - (int64_t)c * HW);
+    float v = mask_blend(mk, b, chw, HW, rem, p, i, x[i]);
+    x[i] = v;
+    write_xin(xin, xin_cpad, cfg_dup, B, C, HW, b, c, p, v);
+  }
+}
+
+// k_decode_step_ddim followed, unless `blend` is 0 (the last step), by the blend of the next level
+__global__ void k_decode_step_ddim_masked(float* __restrict__ x, const float* __restrict__ eh,
+                                          int64_t eh_sb, int64_t eh_sc, int64_t eh_sp, int cfg, float g,
+                                          const float* __restrict__ gvec,
+                                          const float* __restrict__ eps, int64_t eps_bstride,
+                                          const float* __restrict__ noise, uint64_t seed,
+                                          uint32_t stream, int B, int C, int HW, const StepCoef* tab,
+                                          const int* step_ptr, int step_imm, bf16_t* xin, int xin_cpad,
+                                          int cfg_dup_next, int eps_bmod, MaskBlend mk, int blend) {
+  const int64_t chw = (int64_t)C * HW, n = (int64_t)B * chw;
+  const StepCoef co = pick(tab, step_ptr, step_imm);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int b = (int)(i / chw);
+    int64_t rem = i - (int64_t)b * chw;
+    int c = (int)(rem / HW), p = (int)(rem - (int64_t)c * HW);
+    float xv = x[i];
+    float e = load_eps_hat(eh, eh_sb, eh_sc, eh_sp, b, c, p, B, cfg, gvec ? gvec[b] : g);
+    float px0 = (xv - co.r * e) / co.sa;
+    float dir = co.dirc * e;
+    float nn = 0.f;
+    if (co.sigma != 0.f) {
+      float nz;
+      if (eps) nz = eps[(int64_t)(eps_bmod ? b % eps_bmod : b) * eps_bstride + rem];
+      else nz = noise ? noise[i] : philox_normal(seed, stream, (uint64_t)i);
+      nn = co.sigma * nz;
+    }
+    float xn = co.sap * px0 + dir + nn;
+    if (blend) xn = mask_blend(mk, b, chw, HW, rem, p, i, xn);
+    x[i] = xn;
+    write_xin(xin, xin_cpad, cfg_dup_next, B, C, HW, b, c, p, xn);
+  }
+}
+
 // step counter for graph-replayed loops
 __global__ void k_add_int(int* p, int d) { if (threadIdx.x == 0 && blockIdx.x == 0) *p += d; }
 __global__ void k_set_int(int* p, int v) { if (threadIdx.x == 0 && blockIdx.x == 0) *p = v; }
@@ -270,6 +342,22 @@ void launch_decode_step(hipStream_t st, int kind, float* x, const EpsHat& eh, co
                        eh.sc, eh.sp, eps, eps_bstride, noise, seed, stream, B, C, HW, tab,
                        step_ptr, step, xin, xin_cpad, eps_bmod);
   }
+}
+
+void launch_mask_blend_init(hipStream_t st, float* x, const MaskBlend& mk, int B, int C, int HW, bf16_t* xin, int xin_cpad,
+                            int cfg_dup) {
+  int64_t n = (int64_t)B * C * HW;
+  hipLaunchKernelGGL(k_mask_blend_init, dim3(ew_grid(n)), dim3(256), 0, st, x, mk, B, C, HW, xin, xin_cpad, cfg_dup);
+}
+
+void launch_decode_step_masked(hipStream_t st, float* x, const EpsHat& eh, const float* eps, int64_t eps_bstride,
+                               const float* noise, uint64_t seed, uint32_t stream, int B, int C, int HW,
+                               const StepCoef* tab, const int* step_ptr, int step, bf16_t* xin, int xin_cpad,
+                               int cfg_dup_next, int eps_bmod, const MaskBlend& mk, int blend) {
+  int64_t n = (int64_t)B * C * HW;
+  hipLaunchKernelGGL(k_decode_step_ddim_masked, dim3(ew_grid(n)), dim3(256), 0, st, x, eh.p, eh.sb, eh.sc, eh.sp, eh.cfg,
+                     eh.g, eh.gvec, eps, eps_bstride, noise, seed, stream, B, C, HW, tab, step_ptr, step, xin, xin_cpad,
+                     cfg_dup_next, eps_bmod, mk, blend);
 }
 
 void launch_set_int(hipStream_t st, int* p, int v) {

@@ -1,7 +1,8 @@
 """(image, source text, target text) triplets for evaluation - the reference's DevDataset
 (preprocess/translate_text512.py:41-83 over data/translate-text.json: a list of {"img_path", "encode_text",
 "decode_text"}): CenterCropLongEdge -> Resize(resolution) -> ToTensor, one item per JSON entry in [start, end).
-Unpaired (image-only) entries simply omit the two texts."""
+Unpaired (image-only) entries simply omit the two texts. An entry may carry a "mask_path": a grey image, white = keep the
+source there (the wrappers' `mask=`), cropped and resized like the image."""
 import json
 import os
 
@@ -26,6 +27,14 @@ def load_image(path, resolution):
     return torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0).permute(2, 0, 1).contiguous()  # ToTensor
 
 
+def load_mask(path, resolution):
+    """grey keep-mask -> [1, R, R] in [0, 1] (white = keep): the image's centre crop and bilinear resize"""
+    img = center_crop_long_edge(Image.open(path).convert("L"))
+    if img.size != (resolution, resolution):
+        img = img.resize((resolution, resolution), Image.BILINEAR)
+    return torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0)[None].contiguous()
+
+
 class TripletDataset(torch.utils.data.Dataset):
     def __init__(self, json_path, resolution, start=0, end=None, root=None):
         with open(json_path) as fh:
@@ -46,6 +55,11 @@ class TripletDataset(torch.utils.data.Dataset):
         for k in ("encode_text", "decode_text"):
             if k in meta:
                 item[k] = meta[k]
+        if "mask_path" in meta:
+            mpath = meta["mask_path"]
+            if not os.path.isabs(mpath):
+                mpath = os.path.join(self.root, mpath)
+            item["mask"] = load_mask(mpath, self.resolution)
         return item
 
 
@@ -55,4 +69,8 @@ def collate(items):
     for k in ("encode_text", "decode_text"):
         if k in items[0]:
             out[k] = [it[k] for it in items]
+    if any("mask" in it for it in items):  # a batch without any mask carries no `mask` key at all
+        zero = torch.zeros((1,) + tuple(items[0]["original_image"].shape[1:]))
+        out["mask"] = torch.stack([it.get("mask", zero) for it in items])
+        out["has_mask"] = ["mask" in it for it in items]  # host-side bookkeeping: never handed to the model
     return out

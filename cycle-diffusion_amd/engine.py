@@ -472,6 +472,102 @@ class Engine:
         self._keep = (gvec, ctxs, nz)  # the launches read them asynchronously
         return z, x
 
+    def _mask_args(self, mask, x0, B, qcoef, mask_noise, mask_source, H, W, Cc, K, b_noise=None):
+        """checked (mask, x0, B_mask, source id, qcoef, noise) of the masked entry points; `b_noise`: the decoder's batch"""
+        b_noise = B if b_noise is None else b_noise
+        if mask_source not in _ffi.MASK_SOURCES:
+            raise ValueError("mask_source must be one of %s" % sorted(_ffi.MASK_SOURCES))
+        mask = self._f32(mask)
+        if mask.dim() != 4 or mask.shape[1:] != (1, H, W) or B % mask.shape[0] != 0:
+            raise ValueError("mask must be [B_mask, 1, %d, %d] with B_mask dividing %d, got %s" % (H, W, B, tuple(mask.shape)))
+        Bm = mask.shape[0]
+        if mask_source == "encoder":
+            if qcoef is not None or mask_noise is not None:
+                raise ValueError("mask_source = 'encoder' takes no q-sample table and no mask noise")
+            return mask, None, Bm, _ffi.CD_MASK_ENCODER, None, None
+        x0 = self._f32(x0)
+        if tuple(x0.shape) != (Bm, Cc, H, W):
+            raise ValueError("the blend's x0 must be %s, got %s" % ((Bm, Cc, H, W), tuple(x0.shape)))
+        qcoef = np.ascontiguousarray(qcoef, dtype=np.float32)
+        if qcoef.shape != (K, 2):
+            raise ValueError("q-sample table must be [%d, 2] (DDIMSchedule.coef_qsample), got %s" % (K, qcoef.shape))
+        if mask_noise is not None:
+            mask_noise = self._f32(mask_noise)
+            if tuple(mask_noise.shape) != (K, b_noise, Cc, H, W):
+                raise ValueError("mask_noise must be %s, got %s" % ((K, b_noise, Cc, H, W), tuple(mask_noise.shape)))
+        return mask, x0, Bm, _ffi.CD_MASK_QSAMPLE, qcoef, mask_noise
+
+    def ddim_decode_masked(self, net, kind, z, coef, mask, x0, qcoef, mask_noise=None, mask_seed=0, n_eps=None, ctx_c=None,
+                           ctx_uc=None, guidance=1.0, noise_tail=None, seed=0, mask_source="q_sample"):
+        """cd_ddim_decode_masked: ddim_decode with the keep-mask blend x <- src_k*m + (1-m)*x ahead of every forward
+        (sample_with_eps(mask=, x0=), ddim.py:427-430). mask [B_mask, 1, H, W] (1 = keep), x0 [B_mask, C, H, W], B_mask
+        dividing B; qcoef = DDIMSchedule.coef_qsample(skip); mask_noise [K, B, C, H, W] (slot i = the draw of loop iteration
+        i) or None (Philox(mask_seed)). mask_source = "encoder" is refused here: it exists on the coupled loop only."""
+        if mask_source == "encoder":
+            raise ValueError("mask_source = 'encoder' needs the coupled loop (cycle_translate_masked / translate()): the "
+                             "encoder's trajectory no longer exists in a separate decode")
+        z = self._f32(z)
+        B, T, Cc, H, W = z.shape
+        K = len(coef)
+        if n_eps is None:
+            n_eps = T - 1
+        mask, x0, Bm, src, qcoef, mask_noise = self._mask_args(mask, x0, B, qcoef, mask_noise, mask_source, H, W, Cc, K)
+        x = torch.empty((B, Cc, H, W), device=z.device, dtype=torch.float32)
+        coef = np.ascontiguousarray(coef)
+        L = ctx_c.shape[1] if ctx_c is not None else (ctx_uc.shape[1] if ctx_uc is not None else 0)
+        cc = self._f32(ctx_c) if ctx_c is not None else None
+        cu = self._f32(ctx_uc) if ctx_uc is not None else None
+        nt = self._f32(noise_tail) if noise_tail is not None else None
+        gvec, gscalar = None, 1.0
+        if isinstance(guidance, (int, float)):
+            gscalar = float(guidance)
+        else:
+            gvec = torch.as_tensor(guidance, dtype=torch.float32).to(z.device).contiguous()
+            if gvec.numel() != B or bool(((gvec == 0) | (gvec == 1)).any()):
+                raise ValueError("per-sample guidance: B scales, none of them 0 or 1")
+        check(self.lib.cd_ddim_decode_masked(self.h, net, kind, ptr(z), T, n_eps, ptr(cc), ptr(cu), L, C.c_float(gscalar),
+                                             ptr(gvec), B, K, C.c_void_p(coef.ctypes.data), ptr(nt), C.c_uint64(seed),
+                                             ptr(mask), ptr(x0), Bm, src, C.c_void_p(qcoef.ctypes.data), ptr(mask_noise),
+                                             C.c_uint64(mask_seed), ptr(x)))
+        self._keep = (gvec, cc, cu, nt, mask, x0, mask_noise)  # the launches read them asynchronously
+        return x
+
+    def cycle_translate_masked(self, net, kind, x0, coef_enc, coef_dec, mask, mask_x0=None, qcoef=None, mask_noise=None,
+                               mask_seed=0, mask_source="q_sample", enc_ctx_c=None, enc_ctx_uc=None, enc_guidance=1.0,
+                               dec_ctx_c=None, dec_ctx_uc=None, dec_guidance=1.0, n_dec=1, noise=None, seed=0,
+                               last_uses_x0=True):
+        """cd_cycle_translate_masked: cycle_translate with the keep-mask on the decoder rows. mask [B_mask, 1, H, W], B_mask
+        dividing B. "q_sample": mask_x0 [B_mask, C, H, W], qcoef = coef_qsample(skip), mask_noise [K, n_dec * B, C, H, W] or
+        None; "encoder": the kept region follows the encoder's own x_t of every level, nothing else is passed or drawn."""
+        x0 = self._f32(x0)
+        K = len(coef_dec)
+        assert len(coef_enc) == K + 1
+        B, Cc, H, W = x0.shape
+        mask, mask_x0, Bm, src, qcoef, mask_noise = self._mask_args(mask, mask_x0, B, qcoef, mask_noise, mask_source, H, W, Cc,
+                                                                    K, b_noise=n_dec * B)
+        z = torch.empty((B, K + 1, Cc, H, W), device=x0.device, dtype=torch.float32)
+        x = torch.empty((n_dec * B, Cc, H, W), device=x0.device, dtype=torch.float32)
+        coef_enc, coef_dec = np.ascontiguousarray(coef_enc), np.ascontiguousarray(coef_dec)
+        ctxs = [self._f32(t) if t is not None else None for t in (enc_ctx_c, enc_ctx_uc, dec_ctx_c, dec_ctx_uc)]
+        L = next((t.shape[1] for t in ctxs if t is not None), 0)
+        for t, rows in zip(ctxs, (B, B, n_dec * B, n_dec * B)):
+            assert t is None or t.shape[0] == rows, (t.shape, rows)
+        gvec, gscalar = None, 1.0
+        if isinstance(dec_guidance, (int, float)):
+            gscalar = float(dec_guidance)
+        else:
+            gvec = torch.as_tensor(dec_guidance, dtype=torch.float32).to(x0.device).contiguous()
+            if gvec.numel() != n_dec * B or bool(((gvec == 0) | (gvec == 1)).any()):
+                raise ValueError("per-sample guidance: n_dec * B scales, none of them 0 or 1")
+        nz = self._f32(noise) if noise is not None else None
+        check(self.lib.cd_cycle_translate_masked(
+            self.h, net, kind, ptr(x0), ptr(ctxs[0]), ptr(ctxs[1]), C.c_float(enc_guidance), ptr(ctxs[2]), ptr(ctxs[3]),
+            C.c_float(gscalar), ptr(gvec), L, B, n_dec, K, C.c_void_p(coef_enc.ctypes.data), C.c_void_p(coef_dec.ctypes.data),
+            ptr(nz), C.c_uint64(seed), int(last_uses_x0), ptr(mask), ptr(mask_x0), Bm, src,
+            C.c_void_p(qcoef.ctypes.data) if qcoef is not None else None, ptr(mask_noise), C.c_uint64(mask_seed), ptr(z), ptr(x)))
+        self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise)  # the launches read them asynchronously
+        return z, x
+
     def pix_refine(self, net, kind, x, coef, noise=None, seed=0):
         x = self._f32(x).clone()
         R = len(coef) - 1

@@ -39,6 +39,12 @@ class _LatentBaseline(_NoCoupledLoop):
     share their rows and batch structure fold into one cd_ddim_decode(_v) call, as the CycleDiffusion wrapper folds its
     ensemble; then the first stage and the post-process (x + 1) / 2."""
 
+    def forward(self, z_ensemble, original_img, encode_text, decode_text, mask=None):
+        if mask is not None:
+            raise ValueError("%s takes no keep-mask: the region-keeping decode is CycleDiffusion's (SDStochasticText / "
+                             "LatentDiffStochasticText)" % type(self).__name__)
+        return super().forward(z_ensemble, original_img, encode_text, decode_text)
+
     def _decode_jobs(self, jobs, decode_text, bsz):
         c, uc = self.get_condition(decode_text, bsz)
         latents = {}

@@ -157,7 +157,10 @@ class DDPMDDIMWrapper(torch.nn.Module):
                 x = self.engine.pix_refine(self.net, self.sched.kind, x, self.sched.coef_refine(), noise=nz)
         return x
 
-    def forward(self, z, class_label=None):
+    def forward(self, z, class_label=None, mask=None):
+        if mask is not None:  # the reference has no mask hook on DDPMDDIMWrapper
+            raise ValueError("%s (gan_type DDPM_DDIM) takes no keep-mask: the region-keeping decode exists on the latent text "
+                             "wrappers only" % type(self).__name__)
         img = self.generate(z.to(self.device, torch.float32), class_label)
         return (img + 1.0) / 2.0  # post_process Normalize(mean=-1, std=2) (:386-389)
 

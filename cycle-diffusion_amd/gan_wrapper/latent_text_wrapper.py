@@ -66,8 +66,15 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
     def __init__(self, source_model_type, custom_steps, eta, white_box_steps, skip_steps,
                  encoder_unconditional_guidance_scales=None, decoder_unconditional_guidance_scales=None,
                  n_trials=None, cond_stage=None, ranker=None, device=None, text_encoder=None,
-                 noise_on_cpu=False, fold_ensemble=True, ranker_path=None, precision="fp16", couple=True):
+                 noise_on_cpu=False, fold_ensemble=True, ranker_path=None, precision="fp16", couple=True,
+                 mask_source="q_sample"):
         super().__init__()
+        # `[gan] mask_source`: what a keep-mask (forward / translate `mask=`) holds its region to - 'q_sample': a freshly noised
+        # copy of the source latent per step, the reference's sample_with_eps(mask=, x0=) (ddim.py:427-430); 'encoder': the
+        # DPM-Encoder's own x_t of every level (coupled loop only, no extra noise)
+        if str(mask_source) not in _ffi.MASK_SOURCES:
+            raise ValueError("mask_source must be one of %s" % sorted(_ffi.MASK_SOURCES))
+        self.mask_source = str(mask_source)
         # `[gan] precision`: arithmetic of the U-Net AND (round 5) of the first stage - the reference's `precision = "full"` covers
         # both (sd_wrapper:117, autoencoder.py:324-333); the text towers stay 16-bit (their output is the conditioning, rounded
         # once). 'fp16' (default):
@@ -249,6 +256,9 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
 
     def encode(self, image, encode_text):
         x0, c, uc, members = self._encode_front(image, encode_text)
+        return self._encode_members(x0, c, uc, members)
+
+    def _encode_members(self, x0, c, uc, members):
         bsz, sch = x0.shape[0], self._schedule()
         z_ensemble = [None] * len(members)
         per_call = max(1, self.MAX_FOLD // bsz)
@@ -274,8 +284,37 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         return max(0, min(K, self.white_box_steps - skip - 1))
 
     # ---- generate (sd_wrapper:142-167)
-    def generate(self, z_ensemble, decode_text, latents=None):
-        """`latents` (translate()): {output slot: latent [bsz, C, h, w]} of candidates the coupled loop already decoded."""
+    # ---- keep-mask (sample_with_eps(mask=, x0=), ddim.py:427-430)
+    def _latent_mask(self, mask, bsz):
+        """pixel-space [B, 1, R, R] in [0, 1] (1 = keep the source) -> latent [B, 1, R/f, R/f]: the f x f block mean, f the
+        first stage's down-sampling factor; not thresholded - the blend is linear in m, a feathered mask stays feathered"""
+        mask = torch.as_tensor(mask).to(self.device, torch.float32)
+        if mask.dim() != 4 or tuple(mask.shape) != (bsz, 1, self.resolution, self.resolution):
+            raise ValueError("mask must be [%d, 1, %d, %d], got %s" % (bsz, self.resolution, self.resolution, tuple(mask.shape)))
+        if bool((mask < 0).any()) or bool((mask > 1).any()):
+            raise ValueError("mask values must lie in [0, 1] (1 = keep the source)")
+        return torch.nn.functional.avg_pool2d(mask, self.vae_factor).contiguous()
+
+    def _mask_draws(self, K, bsz, n_eps=None):
+        """the K q_sample draws of ONE sample_with_eps(mask=) call in its own order (randn_like(x0) at the top of every step,
+        ddim.py:429), and - interleaved as the reference draws them - the fresh noise of the steps past the white-box prefix
+        (ddim.py:437 `eps=None`) -> (mask_noise [K, bsz, C, h, w], tail or None)"""
+        shape = (bsz, self.channels, self.image_size, self.image_size)
+        n_eps = K if n_eps is None else n_eps
+        if not (self.noise_on_cpu or self.noise_source is not None):
+            return self._randn((K,) + shape), (self._randn((K - n_eps,) + shape) if K > n_eps else None)
+        mn, tail = [], []
+        for i in range(K):
+            mn.append(self._randn(shape))
+            if i >= n_eps:
+                tail.append(self._randn(shape))
+        return torch.stack(mn, 0), (torch.stack(tail, 0) if tail else None)
+
+    def generate(self, z_ensemble, decode_text, latents=None, mask=None, x0=None, mask_noise=None):
+        """`latents` (translate()): {output slot: latent [bsz, C, h, w]} of candidates the coupled loop already decoded.
+        `mask` (LATENT mask [bsz, 1, h, w]) with `x0` [bsz, C, h, w]: the "q_sample" keep-mask decode; every candidate draws
+        its own K noise tensors in the order the reference's loop would call sample_with_eps (z member -> decoder scale);
+        `mask_noise`: {output slot: [K, bsz, C, h, w]} of draws translate() already made in that order."""
         sch = self._schedule()
         n_dec = len(self.decoder_unconditional_guidance_scales)
         bsz = z_ensemble[0].shape[0]
@@ -291,6 +330,16 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
             n_tail = (len(sch) - skip) - (slots - 1)
             for j, dec_scale in enumerate(self.decoder_unconditional_guidance_scales):
                 tail = None
+                if mask is not None:
+                    slot = i * n_dec + j
+                    if mask_noise is not None and slot in mask_noise:
+                        mn = mask_noise[slot]
+                    elif slot in latents:
+                        mn = None
+                    else:
+                        mn, tail = self._mask_draws(len(sch) - skip, bsz, n_eps=slots - 1)
+                    jobs.append((slot, int(skip), float(dec_scale), zz, tail, mn))
+                    continue
                 if n_tail > 0:
                     shape = (bsz, self.channels, self.image_size, self.image_size)
                     if self.noise_on_cpu or self.noise_source is not None:
@@ -314,6 +363,16 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                     guidance = torch.tensor([sc for sc in scales for _ in range(bsz)], dtype=torch.float32)
                 else:
                     guidance = scales[0]
+                if mask is not None:
+                    x = self.engine.ddim_decode_masked(
+                        self.unet, _ffi.CD_SCHED_DDIM, torch.cat([todo[i][3] for i in idx], dim=0).contiguous(),
+                        sch.coef_decode(skip), mask, x0, sch.coef_qsample(skip),
+                        mask_noise=torch.cat([todo[i][5] for i in idx], dim=1).contiguous(), ctx_c=c.repeat(n, 1, 1),
+                        ctx_uc=uc.repeat(n, 1, 1), guidance=guidance,
+                        noise_tail=None if todo[idx[0]][4] is None else torch.cat([todo[i][4] for i in idx], dim=1).contiguous())
+                    for j, i in enumerate(idx):
+                        latents[todo[i][0]] = x[j * bsz:(j + 1) * bsz]
+                    continue
                 x = self.engine.ddim_decode(self.unet, _ffi.CD_SCHED_DDIM,
                                             torch.cat([todo[i][3] for i in idx], dim=0).contiguous(),
                                             sch.coef_decode(skip), ctx_c=c.repeat(n, 1, 1), ctx_uc=uc.repeat(n, 1, 1),
@@ -325,7 +384,8 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         # decode_first_stage, then post_process (x+1)/2 fused into the final layout kernel; candidates in output order, in calls
         # of at most _vae_batch() images
         per = self._vae_batch()
-        lat = torch.cat([latents[k] for k in range(n_jobs)], 0)
+        self.last_latents = [latents[k] for k in range(n_jobs)]  # the candidates' latents ahead of the first stage
+        lat = torch.cat(self.last_latents, 0)
         img = torch.cat([self.engine.vae_decode(self.vae, lat[i:i + per].contiguous(), scale=self.SCALE_FACTOR,
                                                 out_mul=0.5, out_add=0.5) for i in range(0, lat.shape[0], per)], 0)
         return [img[k * bsz:(k + 1) * bsz] for k in range(n_jobs)]
@@ -335,13 +395,17 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         return "cond" if scale == 1.0 else ("uncond" if scale == 0.0 else "cfg")
 
     # ---- encode + generate as ONE coupled loop (north_star; include/cyclediff.h cd_cycle_translate)
-    def translate(self, image, encode_text, decode_text):
+    def translate(self, image, encode_text, decode_text, mask=None):
         """What Model.forward composes (model/text_unsupervised_translation.py:24-40): `self(encode(image, encode_text), image,
         encode_text, decode_text)`, with the DPM-Encoder and the decode of every ensemble member running as one loop - step k of
         both evaluates the same U-Net at the same timestep, and the decode step needs eps_k only after its forward, so each
         step is ONE forward over [encoder rows | decoder rows] (C2: 12 rows per step for a batch of 4 instead of 4, then 8).
         Same draws in the same order, same member order, same per-sample arithmetic as the two calls. Chains that leave part
-        of the decode to fresh noise (white_box_steps shorter than the chain) take the two calls."""
+        of the decode to fresh noise (white_box_steps shorter than the chain) take the two calls.
+        `mask` (pixel-space [B, 1, R, R] in [0, 1], 1 = keep the source): the region-keeping edit, see _translate_masked;
+        without one every call below is the unmasked path's."""
+        if mask is not None:
+            return self._translate_masked(image, encode_text, decode_text, mask)
         sch = self._schedule()
         whole = all(self._white_box_loop(len(sch) - sk, sk) == len(sch) - sk for sk in self.skip_steps)
         dec_scales = [float(sc) for sc in self.decoder_unconditional_guidance_scales]
@@ -380,8 +444,101 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         img_ensemble = self.generate(z_ensemble, decode_text, latents=latents)
         return self._select(img_ensemble, image, encode_text, decode_text)
 
-    def forward(self, z_ensemble, original_img, encode_text, decode_text):
-        return self._select(self.generate(z_ensemble, decode_text), original_img, encode_text, decode_text)
+    def _translate_masked(self, image, encode_text, decode_text, mask):
+        """translate() with a keep-mask: ahead of every forward the decoder's latent becomes src_k * m + (1 - m) * x, m the
+        block mean of `mask` (ddim.py:427-430). x0 of the blend is the first-stage encoding encode() works on (the sampled z0
+        for the SD family). mask_source 'q_sample': src_k = q_sample(x0, tau[k]) with K fresh draws per candidate, made after
+        the encoder's in the reference's order - coupled or as two calls, by the same rule as the unmasked translate().
+        'encoder': src_k = the DPM-Encoder's own x_t of level k; ALWAYS the coupled loop - past COUPLE_MAX_TOKENS it runs in
+        chunks of samples. The decoded image is NOT pasted over in pixel space: the kept region goes through the first stage
+        like the rest."""
+        sch = self._schedule()
+        bsz = image.shape[0]
+        m = self._latent_mask(mask, bsz)
+        encoder = self.mask_source == "encoder"
+        whole = all(self._white_box_loop(len(sch) - sk, sk) == len(sch) - sk for sk in self.skip_steps)
+        dec_scales = [float(sc) for sc in self.decoder_unconditional_guidance_scales]
+        n_dec = len(dec_scales)
+        kinds = [self._kind(sc) for sc in dec_scales]
+        main = "cfg" if "cfg" in kinds else kinds[0]
+        ride = [j for j in range(n_dec) if kinds[j] == main and (main == "cfg" or dec_scales[j] == dec_scales[kinds.index(main)])]
+        enc_cfg = any(self._kind(float(sc)) == "cfg" for sc in self.encoder_unconditional_guidance_scales)
+        rows1 = (2 if enc_cfg else 1) + len(ride) * (2 if main == "cfg" else 1)  # rows of one sample of one member
+        tokens = self.image_size ** 2
+        fits = bsz * rows1 * tokens <= self.couple_max_tokens
+        if encoder:
+            if not whole:
+                raise ValueError("mask_source = 'encoder' needs the DPM-Encoder over the whole chain (white_box_steps = "
+                                 "custom_steps + 1): a shorter prefix has no encoder trajectory for the remaining steps")
+            if len(ride) != n_dec:
+                raise ValueError("mask_source = 'encoder': every decoder scale must ride in the coupled loop (all guided, or "
+                                 "one unguided scale) - a candidate decoded from z afterwards has no encoder trajectory")
+            coupled = True
+        else:
+            coupled = bool(self.couple and whole and fits)
+        self.last_translate_coupled = coupled
+        x0, c_src, uc, members = self._encode_front(image, encode_text)
+        if not coupled:
+            z_ensemble = self._encode_members(x0, c_src, uc, members)
+            return self._select(self.generate(z_ensemble, decode_text, mask=m, x0=x0), image, encode_text, decode_text)
+        c_tgt, _ = self.get_condition(decode_text, bsz)
+        mask_noise = {}
+        if not encoder:  # the reference's order: every member encoded, then member -> decoder scale, K draws each
+            for i, mem in enumerate(members):
+                for j in range(n_dec):
+                    mask_noise[i * n_dec + j] = self._mask_draws(len(sch) - mem[1], bsz)[0]
+        bc = bsz if fits else max(1, self.couple_max_tokens // (rows1 * tokens))  # samples per coupled call
+        per_call = max(1, min(self.MAX_FOLD // (bc * (1 + len(ride))), self.couple_max_tokens // (bc * rows1 * tokens)))
+        z_parts, lat_parts = [[] for _ in members], {}
+        for s0 in range(0, bsz, bc):
+            sl = slice(s0, min(bsz, s0 + bc))
+            nb = sl.stop - sl.start
+            for grp in self._groups([(mm[0], mm[1]) for mm in members]):
+                enc_scale, skip = members[grp[0]][0], members[grp[0]][1]
+                for idx in self._chunks(grp, per_call):
+                    n, nr = len(idx), len(ride)
+                    if main == "cfg" and len({dec_scales[j] for j in ride}) > 1:
+                        guidance = torch.tensor([dec_scales[j] for j in ride for _ in range(n * nb)], dtype=torch.float32)
+                    else:
+                        guidance = dec_scales[ride[0]]
+                    kw = {}
+                    if not encoder:  # decoder row (jr * n + mi) * nb + b
+                        kw = dict(mask_x0=x0[sl].contiguous(), qcoef=sch.coef_qsample(skip),
+                                  mask_noise=torch.cat([mask_noise[i * n_dec + j][:, sl] for j in ride for i in idx],
+                                                       dim=1).contiguous())
+                    z, x = self.engine.cycle_translate_masked(
+                        self.unet, _ffi.CD_SCHED_DDIM, x0[sl].repeat(n, 1, 1, 1), sch.coef_encode(skip), sch.coef_decode(skip),
+                        m[sl].contiguous(), mask_source=self.mask_source, enc_ctx_c=c_src[sl].repeat(n, 1, 1),
+                        enc_ctx_uc=uc[sl].repeat(n, 1, 1), enc_guidance=enc_scale, dec_ctx_c=c_tgt[sl].repeat(n * nr, 1, 1),
+                        dec_ctx_uc=uc[sl].repeat(n * nr, 1, 1), dec_guidance=guidance, n_dec=nr,
+                        noise=torch.cat([members[i][2][:, sl] for i in idx], dim=1).contiguous(), last_uses_x0=True, **kw)
+                    for mi, i in enumerate(idx):
+                        z_parts[i].append(z[mi * nb:(mi + 1) * nb].reshape(nb, -1))
+                        for jr, j in enumerate(ride):
+                            lat_parts.setdefault(i * n_dec + j, []).append(x[(jr * n + mi) * nb:(jr * n + mi + 1) * nb])
+        z_ensemble = [torch.cat(p, 0) for p in z_parts]
+        latents = {k: torch.cat(v, 0) for k, v in lat_parts.items()}
+        img_ensemble = self.generate(z_ensemble, decode_text, latents=latents, mask=m, x0=x0, mask_noise=mask_noise)
+        return self._select(img_ensemble, image, encode_text, decode_text)
+
+    def forward(self, z_ensemble, original_img, encode_text, decode_text, mask=None):
+        """`mask` (pixel-space [B, 1, R, R] in [0, 1], 1 = keep the source): the reference's sample_with_eps(mask=, x0=) decode.
+        The blend's x0 is `original_img` re-encoded here with the posterior MEAN - no noise is drawn for it, whatever the
+        family's encode() samples. Only mask_source 'q_sample' exists on this two-call path: the encoder's trajectory is gone
+        once encode() has returned. The decoded image is not pasted over in pixel space: the kept region goes through the
+        first stage like the rest."""
+        if mask is None:
+            return self._select(self.generate(z_ensemble, decode_text), original_img, encode_text, decode_text)
+        if self.mask_source == "encoder":
+            raise ValueError("mask_source = 'encoder' needs translate(): in encode() + forward() the encoder's trajectory no "
+                             "longer exists; use translate(image, encode_text, decode_text, mask=) or mask_source = q_sample")
+        bsz = z_ensemble[0].shape[0]
+        m = self._latent_mask(mask, bsz)
+        img = ((original_img - 0.5) * 2.0).to(self.device, torch.float32)
+        per = self._vae_batch()
+        x0 = torch.cat([self.engine.vae_encode(self.vae, img[i:i + per], sample=False, scale=self.SCALE_FACTOR)
+                        for i in range(0, bsz, per)], 0)
+        return self._select(self.generate(z_ensemble, decode_text, mask=m, x0=x0), original_img, encode_text, decode_text)
 
     def _select(self, img_ensemble, original_img, encode_text, decode_text):
         """the candidate the reference returns (sd_wrapper:213-249): the only one, or per sample the directional-CLIP argmax"""

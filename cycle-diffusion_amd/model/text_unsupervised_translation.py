@@ -12,10 +12,18 @@ class TextUnsupervisedTranslation(nn.Module):
         super().__init__()
         self.gan_wrapper = get_gan_wrapper(args.gan)
 
-    def forward(self, sample_id, original_image, encode_text, decode_text):
+    def forward(self, sample_id, original_image, encode_text, decode_text, mask=None):
+        """`mask` (optional batch key, [B, 1, R, R] in [0, 1], 1 = keep the source): the wrapper's region-keeping decode."""
         self.gan_wrapper.eval()
         assert not self.training
-        if hasattr(self.gan_wrapper, "translate"):
+        if mask is not None:
+            if hasattr(self.gan_wrapper, "translate"):
+                img = self.gan_wrapper.translate(original_image, encode_text, decode_text, mask=mask)
+            else:  # the baselines reject a mask by name
+                z_ensemble = self.gan_wrapper.encode(image=original_image, encode_text=encode_text)
+                img = self.gan_wrapper(z_ensemble=z_ensemble, original_img=original_image, encode_text=encode_text,
+                                       decode_text=decode_text, mask=mask)
+        elif hasattr(self.gan_wrapper, "translate"):
             # encode() + forward() as the engine's coupled loop: ONE U-Net forward per step over [encoder rows | decoder
             # rows] (include/cyclediff.h cd_cycle_translate); same draws, member order and per-sample arithmetic
             img = self.gan_wrapper.translate(original_image, encode_text, decode_text)

@@ -31,6 +31,9 @@ enum { CD_NET_UNET_OPENAI = 1, CD_NET_UNET_HO = 2, CD_NET_VAE_KL = 3, CD_NET_CLI
        CD_NET_OCLIP_TEXT = 6, CD_NET_OCLIP_VISION = 7, CD_NET_INCEPTION_FID = 8 };
 enum { CD_SCHED_DDIM = 0, CD_SCHED_DDPM = 1 };
 enum { CD_PREC_16 = 0, CD_PREC_F32 = 1, CD_PREC_F32X3 = 2 };
+/* what a keep-mask holds its region to: q_sample(x0, t) freshly noised per step (the reference, ddim.py:427-430), or the
+ * DPM-Encoder's own x_t of the level (coupled loop only) */
+enum { CD_MASK_QSAMPLE = 0, CD_MASK_ENCODER = 1 };
 
 /* Architecture descriptor (the hyper-parameters of the reference's YAML / dict configs):
  *   UNET_OPENAI : ldm/modules/diffusionmodules/openaimodel.py:413-470 (SD v1, LDM text2img) and
@@ -224,6 +227,39 @@ int cd_cycle_translate(cd_handle h, int net, int sched_kind, const float* x0, co
                        const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
                        uint64_t seed, int last_uses_x0, float* z_out, float* x_out);
 
+/* Region-keeping decode: DDIMSampler.sample_with_eps(..., mask=, x0=) (ddim.py:170-228; the branch at :427-430). Ahead of the
+ * forward of EVERY step, the first included, the running latent is replaced by
+ *     x <- src_k * m + (1 - m) * x          (fp32, in that operation order; m = 1 keeps the source, m is broadcast over C)
+ * and the blended x is what the network, x0_hat and the step formula see; nothing is blended after the last step.
+ *   Everything up to `seed` as cd_ddim_decode; guidance_per_sample non-NULL selects cd_ddim_decode_v's per-sample scales
+ *   (`guidance` is then ignored). mask [B_mask,1,H,W] in [0,1], x0 [B_mask,C,H,W], B a multiple of B_mask: sample b uses row
+ *   b % B_mask (ensemble members folded into the batch share their sample's mask). mask_source must be CD_MASK_QSAMPLE here:
+ *   src_k = qa[k]*x0 + qb[k]*n_k (LatentDiffusion.q_sample, ddpm.py:271-274) with qsample_coef_host = K rows of (qa, qb) =
+ *   float32(sqrt(alphas_cumprod))[tau[k]], float32(sqrt(1 - alphas_cumprod))[tau[k]] stored at row index = k (the fp64 square
+ *   roots of ddpm.py:141-142, NOT the sa / s1a of the DDIM table) and n_k = mask_noise[K-1-k] of mask_noise [K,B,C,H,W] (slot i
+ *   = the draw of loop iteration i, the reference's randn_like(x_start)), or Philox(mask_seed) when mask_noise is NULL.
+ * Refused (error text, nothing launched): sched_kind != CD_SCHED_DDIM and the pixel networks (the reference has no mask hook on
+ * DDPMDDIMWrapper), B % B_mask != 0, CD_MASK_ENCODER (the encoder's trajectory does not exist in a separate decode). */
+int cd_ddim_decode_masked(cd_handle h, int net, int sched_kind, const float* z, int z_slots, int n_eps, const float* ctx_c,
+                          const float* ctx_uc, int ctx_len, float guidance, const float* guidance_per_sample, int B, int K,
+                          const cd_step_coef* coef_host, const float* noise_tail, uint64_t seed, const float* mask,
+                          const float* x0, int B_mask, int mask_source, const float* qsample_coef_host,
+                          const float* mask_noise, uint64_t mask_seed, float* x_out);
+
+/* cd_cycle_translate with the keep-mask on its decoder rows. Arguments up to last_uses_x0 as cd_cycle_translate's; the mask
+ * arguments as cd_ddim_decode_masked's with the decoder's batch n_dec*B in the place of B (mask_noise [K,n_dec*B,C,H,W]; decoder
+ * row r uses mask row r % B_mask, B a multiple of B_mask), mask_x0 [B_mask,C,H,W] the x0 of the blend.
+ *   mask_source = CD_MASK_QSAMPLE: per-sample arithmetic of cd_dpm_encode followed by cd_ddim_decode_masked, bit for bit.
+ *   mask_source = CD_MASK_ENCODER: src_k = the encoder's x_t at level k of encoder sample r % B, bit for bit (x_T for the first
+ *   forward); no noise is drawn; qsample_coef_host and mask_noise must be NULL, mask_x0 is not read. */
+int cd_cycle_translate_masked(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
+                              const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
+                              float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
+                              const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
+                              uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
+                              int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
+                              float* z_out, float* x_out);
+
 /* Stochastic refinement (ddpm_ddim_wrapper.py:431-453): x_t = sa*x + s1a*n (row R of coef_host),
  * then R random-noise steps rows R-1..0. noise [R+1,B,C,H,W] or NULL. In/out x [B,C,H,W]. */
 int cd_pix_refine(cd_handle h, int net, int sched_kind, float* x, int B, int R,
@@ -265,6 +301,14 @@ int cd_op_timestep_embedding(cd_handle h, const float* t, int B, int dim, int mo
 int cd_op_sched_step(cd_handle h, int mode, int sched_kind, const cd_step_coef* coef_host, const float* x0,
                      float* xt, const float* eps_hat, int cfg, float guidance, const float* noise,
                      const float* eps_in, int is_last, int B, int C, int HW, float* z_slot);
+/* the masked step kernels on explicit tensors (bit-exact checks). mode 0: x <- blend(x) (the blend ahead of the first forward);
+ * mode 2: the CD_SCHED_DDIM decode step of cd_op_sched_step followed, when blend != 0, by the blend. src [B_mask,C,HW] is x0
+ * (CD_MASK_QSAMPLE: src_k = qa*x0 + qb*mask_noise, mask_noise [B,C,HW] required) or the source latent itself (CD_MASK_ENCODER);
+ * xin16_out (or NULL): the next forward's 16-bit NHWC input [B (2B with cfg_dup), HW, C] in the format of cd_act_format(). */
+int cd_op_sched_step_masked(cd_handle h, int mode, const cd_step_coef* coef_host, float* x, const float* eps_hat, int cfg,
+                            float guidance, const float* eps_in, const float* mask, const float* src, int B_mask,
+                            int mask_source, float qa, float qb, const float* mask_noise, int blend, int B, int C, int HW,
+                            void* xin16_out, int cfg_dup);
 /* micro-benchmark of one conv / GEMM shape on synthetic data (scripts/bench_gemm.py): average ms per launch.
  * act: low byte = activation; | 0x100 = in-place residual update of the output; | 0x200 = fused GroupNorm statistics */
 int cd_op_bench_conv(cd_handle h, int B, int H, int W, int C0, int C1, int N, int k, int stride, int up,

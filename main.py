@@ -67,6 +67,9 @@ def folded_calls(model, batches, fold, seed, device):
         for k in ("is_padding",):  # host-side bookkeeping of the driver: passed through, never handed to the model
             if k in parts[0]:
                 batch[k] = [t for p in parts for t in p[k]]
+        if any("mask" in p for p in parts):  # keep-masks (data/triplets.py): all-zero for the batches that have none
+            batch["mask"] = torch.cat([p["mask"] if "mask" in p else torch.zeros_like(p["original_image"][:, :1]) for p in parts])
+            batch["has_mask"] = [t for p in parts for t in p.get("has_mask", [False] * p["sample_id"].shape[0])]
         streams = SampleStreams(seed, batch["sample_id"].tolist(), device)
         for w in wrappers:
             if hasattr(w, "noise_source"):
@@ -74,6 +77,8 @@ def folded_calls(model, batches, fold, seed, device):
         kw = {"sample_id": batch["sample_id"].to(device), "original_image": batch["original_image"].to(device)}
         if "encode_text" in batch:
             kw.update(encode_text=batch["encode_text"], decode_text=batch["decode_text"])
+        if "mask" in batch:
+            kw.update(mask=batch["mask"].to(device))
         with torch.no_grad():
             (orig, img), _loss, _ = model(**kw)
         yield batch, orig, img
@@ -181,6 +186,11 @@ def main(argv=None):
             for k in ("encode_text", "decode_text"):
                 if k in batch:
                     row[k] = batch[k][j]
+            if "mask" in batch and batch["has_mask"][j]:  # PSNR against the input inside / outside the kept region
+                keep_px = (batch["mask"][j] >= 0.5).expand_as(o)
+                for k, sel in (("psnr_keep", keep_px), ("psnr_edit", ~keep_px)):
+                    if bool(sel.any()):
+                        row[k] = float(metrics.calculate_psnr(g[sel], o[sel]))
             if scores is not None:
                 row["clip"], row["d-clip"] = scores[0][j], scores[1][j]
             if feats is not None:
@@ -204,6 +214,10 @@ def main(argv=None):
         assert len({r["sample_id"] for r in rows}) == len(rows)  # padding rows were skipped where they were produced
         rows.sort(key=lambda r: r["sample_id"])
         summary = {k: sum(r[k] for r in rows) / max(1, len(rows)) for k in ("psnr", "ssim", "l2")}
+        for k in ("psnr_keep", "psnr_edit"):  # only when masked samples exist
+            masked = [r[k] for r in rows if k in r]
+            if masked:
+                summary[k] = sum(masked) / len(masked)
         extra = {}
         if a.text_metrics:
             scored = [r for r in rows if "clip" in r]
