@@ -931,6 +931,11 @@ static void op_conv2d(cd_handle h, const float* x0, int C0, const float* x1, int
   CD_CHECK(h && x0 && packed_w && y, "bad argument");
   ArenaScope arena_scope(h->arena);
   Ctx c = h->ctx();
+  if (up && out16) {  // an Upsample layer of the 16-bit path: give the packed weight its phase matrices, as the U-Net does at load
+    ConvW* pw = (ConvW*)const_cast<void*>(packed_w);
+    h->op_params.add_up_phase(pw);
+    h->op_params.refresh_up_phase(h->st, pw);
+  }
   ConvW w = *(const ConvW*)packed_w;
   CD_CHECK(w.N == N && w.KH == KH && w.KW == KW, "packed weight does not match the call");
   w.b = const_cast<float*>(bias);
@@ -989,6 +994,20 @@ int cd_op_conv2d_16(cd_handle h, const float* x0, int C0, const float* x1, int C
   enter_engine(h);
   op_conv2d(h, x0, C0, x1, C1, B, H, W, packed_w, N, KH, KW, stride, pad, asym_pad, up, bias, rowvec, resid, act, tile,
             true, y, stats);
+  CD_API_END
+}
+
+int cd_op_up_phase_reorder(cd_handle h, const float* x, int B, int C, int H, int W, float* y) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && y && B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "bad argument");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  Act a = alloc_act(c, 4 * B, H, W, C);  // rows in (image, phase, y, x) order, as the phase-form GEMM leaves them
+  launch_nchw_to_nhwc(h->st, x, a.p, 4 * B, C, H * W, C, 1.f, 0.f, 0);
+  Act o = alloc_act(c, B, 2 * H, 2 * W, C);
+  launch_up_phase_reorder(h->st, a.p, o.p, B, H, W, C, o.ld);
+  launch_nhwc_to_nchw(h->st, o.p, 0, o.ld, y, B, C, 4 * H * W, 1.f, 0.f);
   CD_API_END
 }
 

@@ -209,11 +209,20 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
   const int sh_hw = 31 - __builtin_clz(HWo), sh_w = 31 - __builtin_clz(p.Wout);
   int b_first = pow2 ? (m0 >> sh_hw) : (m0 / HWo);
   CD_PROBE_ONLY(if (p.dbg & 4) b_first = 0;)
+  // phase form of the x2 convs (ConvGemmParams::up_phase): the rows' "sample" index is (image, phase); the tile lies in one
+  // phase of one image, whose parity (a, b) moves the first tap and selects the weight matrix (all uniform)
+  int pad_t = p.pad_t, pad_l = p.pad_l, w_ph = 0;
+  if (p.up_phase) {
+    const int ph = b_first & 3;
+    b_first >>= 2;
+    pad_t = 1 - (ph >> 1); pad_l = 1 - (ph & 1);
+    w_ph = ph * p.w_ps;
+  }
   const int64_t samp0 = (int64_t)b_first * p.Hs * p.Ws;
   const bf16_t* base0 = p.src0 + (int64_t)zb * p.a_bs + samp0 * p.ld0;
   const bf16_t* base1 = p.src1 ? p.src1 + (int64_t)zb * p.a_bs + samp0 * p.ld1 : base0;
   const __amdgpu_buffer_rsrc_t rsw =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(p.wgt + (int64_t)zb * p.w_bs), 0, kRange, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void*)(p.wgt + (int64_t)zb * p.w_bs + w_ph), 0, kRange, 0x00020000);
 
   // ---- per-lane staging geometry
   const int srow = lane / CPR;   // row within a glds instruction
@@ -243,8 +252,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
         const int rem = m - b * HWo;
         oy = rem / p.Wout; ox = rem - oy * p.Wout;
       }
-      a_iy0[i] = oy * p.stride - p.pad_t;
-      a_ix0[i] = ox * p.stride - p.pad_l;
+      if (p.up_phase) b >>= 2;
+      a_iy0[i] = oy * p.stride - pad_t;
+      a_ix0[i] = ox * p.stride - pad_l;
       a_boff[i] = (b - b_first) * p.Hs * p.Ws;
     } else {
       a_iy0[i] = -(1 << 28);  // always out of range -> zeros
@@ -994,7 +1004,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
 // the K order a launch takes (launch_cfg below; the trace line and the read-back of launch_conv_gemm give the same answer)
 inline bool takes_channel_major(const ConvGemmParams& p) {
   const int64_t a_bytes = (int64_t)p.B * p.Hs * p.Ws * (p.C0 + p.C1) * 2;
-  return p.korder != 0 && p.KH * p.KW > 1 && p.KH <= 8 && p.KW <= 8 && !p.up &&
+  return p.korder != 0 && p.KH * p.KW > 1 && p.KH <= 8 && p.KW <= 8 && !p.up && !p.up_phase &&
          (p.korder == 2 || (p.Hs * p.Ws >= 4096 && a_bytes >= (32ll << 20)));
 }
 
@@ -1273,7 +1283,8 @@ int tuned_config(hipStream_t st, const ConvGemmParams& p, bool k64) {
   const int nout = (p.act == ACT_GEGLU) ? p.N / 2 : p.N;
   const size_t need = (size_t)p.M * nout * (p.out_f32 ? 4 : 2) * p.nbatch;
   if (need > tu.scratch_bytes) return pick_config(p);
-  ShapeKey key = {{p.M, p.N, p.Ktot, p.KH, p.C0, p.C1, p.stride, p.up, p.act, p.nbatch, p.out_f32, p.Hout, p.Wout,
+  // (the `up` slot: 1 = the x2 gather, 2 = the phase form of the same layer)
+  ShapeKey key = {{p.M, p.N, p.Ktot, p.KH, p.C0, p.C1, p.stride, p.up | (p.up_phase << 1), p.act, p.nbatch, p.out_f32, p.Hout, p.Wout,
                    (p.resid ? 1 : 0) | (p.rowvec ? 2 : 0)}};
   auto& tab = tune_table();
   auto it = tab.find(key);
@@ -1366,6 +1377,10 @@ void launch_conv_gemm(hipStream_t st, const ConvGemmParams& p) {
   CD_CHECK(((uintptr_t)p.src0 & 15) == 0 && ((uintptr_t)p.wgt & 15) == 0, "conv_gemm: 16-B alignment");
   CD_CHECK((p.ld0 % 8) == 0 && (p.src1 == nullptr || (p.ld1 % 8) == 0), "conv_gemm: ld must be a multiple of 8");
   if (p.act == ACT_GEGLU) CD_CHECK(p.N % 64 == 0, "GEGLU needs packed N %% 64 == 0");
+  if (p.up_phase)  // a tile of any configuration (BM = 64 / 128 / 256) must lie in one phase of one image
+    CD_CHECK(p.KH == 2 && p.KW == 2 && p.stride == 1 && !p.up && !p.src1 && p.nbatch == 1 && p.Hout == p.Hs && p.Wout == p.Ws &&
+                 (p.Hs * p.Ws) % 256 == 0 && p.M == 4 * p.B * p.Hs * p.Ws && p.w_ps > 0 && p.Hin == p.Hs && p.Win == p.Ws,
+             "conv_gemm: phase form of an x2 conv on %d x %d", p.Hs, p.Ws);
   bool k64 = (p.C0 % 64 == 0) && (p.C1 % 64 == 0);
   if (p.ln_fold) CD_CHECK(p.tile == kLinStreamTile, "conv_gemm: a LayerNorm-folded layer runs on lin_stream only");
   int id = p.tile ? p.tile : tuned_config(st, p, k64);
@@ -1421,7 +1436,7 @@ void launch_conv_gemm(hipStream_t st, const ConvGemmParams& p) {
   static const bool trace = [] { const char* e = getenv("CYCLEDIFF_GEMM_TRACE"); return e && e[0] == '1'; }();
   if (trace) {
     const bool chm = id != kLinStreamTile && takes_channel_major(pk);
-    fprintf(stderr, "[gemm_trace] %d %d %d %d %d %d %d %d %d %d %d %d | %s x%d\n", p.M, p.N, p.Ktot, p.KH, p.stride, p.up,
+    fprintf(stderr, "[gemm_trace] %d %d %d %d %d %d %d %d %d %d %d %d | %s x%d\n", p.M, p.N, p.Ktot, p.KH, p.stride, p.up | (p.up_phase << 1),
             p.src1 ? 1 : 0, p.nbatch, p.act, p.resid ? 1 : 0, p.out_f32, chm ? 1 : 0, ci->name, pk.splitk > 1 ? pk.splitk : 1);
   }
   KernelProfiler* prof = g_conv_prof;
@@ -1430,7 +1445,7 @@ void launch_conv_gemm(hipStream_t st, const ConvGemmParams& p) {
     char what[112] = "";
     if (prof->verbose)
       snprintf(what, sizeof(what), "M%d N%d K%d k%d s%d%s%s z%d act%d | %s x%d", p.M, p.N, p.Ktot, p.KH, p.stride,
-               p.up ? " up" : "", p.src1 ? " cat" : "", p.nbatch, p.act, ci->name, pk.splitk > 1 ? pk.splitk : 1);
+               p.up ? " up" : (p.up_phase ? " up-phase" : ""), p.src1 ? " cat" : "", p.nbatch, p.act, ci->name, pk.splitk > 1 ? pk.splitk : 1);
     if (prof->verbose && !k64) strncat(what, " bk32", sizeof(what) - strlen(what) - 1);
     prof->next_pair(&e0, &e1, 2.0 * (double)p.M * (double)p.N * (double)p.Ktot * (double)p.nbatch * p.prof_flop_scale,
                     what);
@@ -1474,6 +1489,34 @@ __global__ void k_repack_weight(const float* __restrict__ w, bf16_t* __restrict_
     if (np < N && c < Cin) v = w[(((int64_t)(n + src_row_offset) * Cin + c) * KH + r) * KW + s];
     out[i] = f2bf(v);
   }
+}
+
+// phase matrices of an x2-upsample 3 x 3 conv (ConvGemmParams::up_phase): after the replication, output parity a reads the
+// stored rows (y - 1, y) through the row taps {w0, w1 + w2} (a = 0) or (y, y + 1) through {w0 + w1, w2} (a = 1); columns alike
+__global__ void k_up_phase_weights(const bf16_t* __restrict__ w, bf16_t* __restrict__ out, int Npad, int Cpad) {
+  const int64_t total = (int64_t)16 * Npad * Cpad;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % Cpad);
+    int64_t t = i / Cpad;
+    const int dx = (int)(t & 1), dy = (int)((t >> 1) & 1); t >>= 2;
+    const int n = (int)(t % Npad);
+    const int ph = (int)(t / Npad);
+    const int a = ph >> 1, b = ph & 1;
+    const int r0 = dy ? 1 + a : 0, r1 = dy ? 2 : a;  // stored-row tap dy <- filter rows [r0, r1]
+    const int s0 = dx ? 1 + b : 0, s1 = dx ? 2 : b;
+    float v = 0.0f;
+    for (int r = r0; r <= r1; ++r)
+      for (int s = s0; s <= s1; ++s) v += bf2f(w[((int64_t)n * 9 + r * 3 + s) * Cpad + c]);
+    out[i] = f2bf(v);
+  }
+}
+
+void launch_up_phase_weights(hipStream_t st, const bf16_t* w, bf16_t* out, int Npad, int Cpad) {
+  const int64_t total = (int64_t)16 * Npad * Cpad;
+  int grid = (int)((total + 255) / 256);
+  if (grid > 4096) grid = 4096;
+  hipLaunchKernelGGL(k_up_phase_weights, dim3(grid), dim3(256), 0, st, w, out, Npad, Cpad);
 }
 
 void launch_repack_weight(hipStream_t st, const float* w, bf16_t* out, int N, int Cin, int KH,

@@ -231,6 +231,22 @@ __global__ void k_upsample2(const bf16_t* __restrict__ x, bf16_t* __restrict__ y
   }
 }
 
+__global__ void k_up_phase_reorder(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int B, int H, int W, int C, int ldy) {
+  const int Ho = H * 2, Wo = W * 2, nvec = C / 8;
+  const int64_t n = (int64_t)B * Ho * Wo * nvec;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int v = (int)(i % nvec);
+    int64_t t = i / nvec;
+    const int ox = (int)(t % Wo); t /= Wo;
+    const int oy = (int)(t % Ho);
+    const int b = (int)(t / Ho);
+    const int ph = (oy & 1) * 2 + (ox & 1);
+    *(uint4*)(y + (((int64_t)b * Ho + oy) * Wo + ox) * ldy + v * 8) =
+        *(const uint4*)(x + ((((int64_t)b * 4 + ph) * H + (oy >> 1)) * W + (ox >> 1)) * C + v * 8);
+  }
+}
+
 __global__ void k_posterior_sample(const float* __restrict__ mom, int ld, const float* __restrict__ noise,
                                    uint64_t seed, float* __restrict__ z, int B, int zc, int HW,
                                    float scale, int use_mean) {
@@ -336,6 +352,11 @@ void launch_vec_linear(hipStream_t st, const float* x, int ldx, const float* W, 
 void launch_avgpool2(hipStream_t st, const bf16_t* x, bf16_t* y, int B, int H, int W, int C) {
   const int64_t n = (int64_t)B * (H / 2) * (W / 2) * (C / 8);
   hipLaunchKernelGGL(k_avgpool2, dim3(ew_grid(n)), dim3(256), 0, st, x, y, B, H, W, C);
+}
+void launch_up_phase_reorder(hipStream_t st, const bf16_t* x, bf16_t* y, int B, int H, int W, int C, int ldy) {
+  CD_CHECK(C % 8 == 0 && ldy % 8 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0, "up_phase_reorder: 16-byte vectors");
+  const int64_t n = (int64_t)B * H * 2 * W * 2 * (C / 8);
+  hipLaunchKernelGGL(k_up_phase_reorder, dim3(ew_grid(n)), dim3(256), 0, st, x, y, B, H, W, C, ldy);
 }
 void launch_upsample2(hipStream_t st, const bf16_t* x, bf16_t* y, int B, int H, int W, int C) {
   const int64_t n = (int64_t)B * H * 2 * W * 2 * (C / 8);

@@ -52,6 +52,10 @@ struct ConvW {  // packed conv / linear weight: 16-bit (or fp32 when f32) [Npad]
   bf16_t* w = nullptr;
   bf16_t* wfrag = nullptr;  // the same rows in MFMA-fragment-major order for lin_stream.hip (1x1, 320 input channels)
   bf16_t* w3 = nullptr;     // CD_PREC_F32X3: fp16 [Npad][KH*KW][wh | wh | wl] (3 * Cpad per tap), from the fp32 rows in w
+  // 3 x 3 weights of a nearest-x2 conv, 16-bit path: the four 2 x 2 phase matrices [2 a + b][Npad][2 * 2 * Cpad] derived from w
+  // (ParamStore::add_up_phase / refresh_up_phase; ConvGemmParams::up_phase), or null
+  bf16_t* wphase = nullptr;
+  int wphase_version = -1;  // ParamStore::version the phase matrices were built at
   bool f32 = false;
   float* b = nullptr;
   int N = 0, Cin = 0, Cpad = 0, KH = 1, KW = 1, Npad = 0;
@@ -91,6 +95,10 @@ class ParamStore {
   // allocate packed storage
   ConvW* new_conv(int N, int Cin, int KH, int KW, bool bias, bool geglu = false);
   float* new_vec(int n, float init = 0.f);
+  // storage for the phase matrices of a 3 x 3 x2-upsample conv (16-bit path only; a no-op elsewhere), and their rebuild
+  // from the loaded weights when the store has changed since the last one (stream-ordered, microseconds)
+  void add_up_phase(ConvW* c);
+  void refresh_up_phase(hipStream_t st, ConvW* c);
   // declare reference tensors and where their rows go
   ParamDecl& declare(const std::string& name, std::vector<int64_t> shape);
   // whole tensor -> whole ConvW; ref_ndim = rank of the reference tensor (2 Linear, 3 Conv1d, 4 Conv2d; 0 = auto)
@@ -163,6 +171,8 @@ Act split_rows_f32_fwd(Ctx& c, const Act& x, const Act* x2 = nullptr);  // split
 Act alloc_act(Ctx& c, int B, int H, int W, int C, bool with_stats = false);
 // y = conv(x [| x2]) with the fused epilogue; returns the output view (bf16 unless out_f32)
 Act conv_fwd(Ctx& c, const ConvW& w, const Act& x, const Act* x2, const ConvOpts& o);
+// whether conv_fwd runs this nearest-x2 3 x 3 conv as four 2 x 2 phase convs on the stored grid (CYCLEDIFF_UP_PHASE=0: never)
+bool conv_up_phase_taken(const Ctx& c, const ConvW& w, const Act& x, const Act* x2, const ConvOpts& o);
 // whether a LayerNorm-folded call of this layer on `rows` tokens would run (streaming kernel applicable and the shape
 // large enough for it to be the fastest choice: the 64 x 64 level from 16 images up)
 bool conv_ln_fold_available(const Ctx& c, const ConvW& w, int64_t rows);

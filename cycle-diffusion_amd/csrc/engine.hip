@@ -50,6 +50,16 @@ ConvW* ParamStore::new_conv(int N, int Cin, int KH, int KW, bool bias, bool gegl
   if (bias) c->b = (float*)dmalloc((size_t)c->Npad * sizeof(float));
   return c;
 }
+void ParamStore::add_up_phase(ConvW* c) {
+  if (f32 || c->wphase || c->KH != 3 || c->KW != 3 || c->geglu) return;
+  c->wphase = (bf16_t*)dmalloc((size_t)4 * c->Npad * 4 * c->Cpad * sizeof(bf16_t));
+  c->wphase_version = -1;
+}
+void ParamStore::refresh_up_phase(hipStream_t st, ConvW* c) {
+  if (!c->wphase || c->wphase_version == version) return;
+  launch_up_phase_weights(st, c->w, c->wphase, c->Npad, c->Cpad);
+  c->wphase_version = version;
+}
 float* ParamStore::new_vec(int n, float init) {
   float* p = (float*)dmalloc((size_t)n * sizeof(float));
   if (init != 0.f) {
@@ -276,7 +286,49 @@ static Act conv_split_fwd(Ctx& c, const ConvW& w, const Act& x, const ConvOpts& 
   return y;
 }
 
+// Phase form of the nearest-x2 3 x 3 convs: 4/9 of the multiply-adds. Taken where the weights carry their
+// phase matrices (the U-Net Upsample layers), the stored image is a multiple of 256 pixels (a tile then lies in one phase of
+// one image: 16 x 16 and larger) and the epilogue needs nothing per output position (no residual). CYCLEDIFF_UP_PHASE=0
+// keeps the x2 gather for A/B runs; read per call (three convs a forward), so a process can run both.
+bool conv_up_phase_taken(const Ctx& c, const ConvW& w, const Act& x, const Act* x2, const ConvOpts& o) {
+  if (!o.up || c.f32 || x.split || x2 || !w.wphase || w.KH != 3 || w.KW != 3 || o.stride != 1 || o.pad != 1 || o.asym ||
+      o.resid || o.out_f32 || o.ln_fold || w.geglu || o.act != ACT_NONE)
+    return false;
+  if ((x.H * x.W) % 256 != 0 || w.N % 8 != 0 || (o.out && o.out_ld % 8 != 0)) return false;
+  const char* e = getenv("CYCLEDIFF_UP_PHASE");
+  return !(e && e[0] == '0');
+}
+
+static Act conv_up_phase_fwd(Ctx& c, const ConvW& w, const Act& x, const ConvOpts& o) {
+  ConvGemmParams p;
+  p.src0 = x.p; p.C0 = round_up(x.C, 32); p.ld0 = x.ld;
+  CD_CHECK(p.C0 == w.Cpad && x.ld >= p.C0, "conv: input channels %d do not match weight Cpad %d", p.C0, w.Cpad);
+  p.B = x.B; p.Hs = x.H; p.Ws = x.W; p.Hin = x.H; p.Win = x.W; p.Hout = x.H; p.Wout = x.W;
+  p.KH = 2; p.KW = 2; p.stride = 1; p.pad_t = 1; p.pad_l = 1;  // (the kernel takes the padding from the tile's phase)
+  p.up_phase = 1; p.w_ps = w.Npad * 4 * w.Cpad;
+  p.M = 4 * x.B * x.H * x.W;
+  p.wgt = w.wphase; p.Ktot = 4 * w.Cpad; p.N = w.N;
+  p.alpha = o.alpha; p.bias = w.b;
+  p.rowvec = o.rowvec; p.rowvec_ld = o.rowvec_ld; p.rows_per_vec = o.rows_per_vec;  // per image: its 4 H W rows stay together
+  Act y; y.B = x.B; y.H = 2 * x.H; y.W = 2 * x.W; y.C = w.N; y.f32 = false;
+  if (o.out) { y.p = (bf16_t*)o.out; y.ld = o.out_ld; }
+  else { y.ld = w.N; y.p = (bf16_t*)c.arena->alloc((size_t)p.M * w.N * 2); }
+  if (o.out && o.out_stats) y.stats_buf = o.out_stats;
+  else if (!o.out && o.want_stats) y.stats_buf = (float*)c.arena->alloc((size_t)(p.M / 32) * 2 * w.N * sizeof(float));
+  p.stats = y.stats_buf;  // 32-row blocks in phase order: an image's blocks are still its own, which is all k_gn_fold asks
+  y.stats = y.stats_buf;
+  const size_t mk = c.arena->mark();
+  bf16_t* tmp = (bf16_t*)c.arena->alloc((size_t)p.M * w.N * 2);  // rows in (image, phase, y, x) order
+  p.out = tmp; p.out_ld = w.N;
+  p.zeros = c.zeros; p.tile = o.tile;
+  launch_conv_gemm(c.st, p);
+  launch_up_phase_reorder(c.st, tmp, y.p, x.B, x.H, x.W, w.N, y.ld);
+  c.arena->release(mk);
+  return y;
+}
+
 Act conv_fwd(Ctx& c, const ConvW& w, const Act& x, const Act* x2, const ConvOpts& o) {
+  if (conv_up_phase_taken(c, w, x, x2, o)) return conv_up_phase_fwd(c, w, x, o);
   if (x.split) {
     CD_CHECK(!x2, "conv: a split activation cannot be concatenated");
     return conv_split_fwd(c, w, x, o);

@@ -133,6 +133,15 @@ struct ConvGemmParams {
   int num_cus = 256;
   int dbg = 0;  // probe build: 1 = the epilogue skips its global stores, 2 = skips the statistics, 4 = every tile gathers
                 // its A rows from the first 1024 + BM rows (an L2-resident operand: what would the K loop do without misses?)
+  // 1: the nearest-x2 3 x 3 convolution in its phase form. After the x2 replication only 2 x 2 stored
+  // pixels feed an output pixel, so the taps that share one are summed ahead of time (launch_up_phase_weights): four 2 x 2
+  // convs on the stored grid, one per output parity (a, b), K = 4 C instead of 9 C. GEMM row m = (image, phase = 2 a + b,
+  // y, x) with Hout = Hs, Wout = Ws, M = 4 B Hs Ws, KH = KW = 2, up = 0; the taps of row m start at (y + a - 1, x + b - 1)
+  // and its weights at wgt + phase * w_ps. Hs * Ws is a multiple of 256, so a tile of any configuration lies in one phase
+  // of one image. Rows leave in this order (launch_up_phase_reorder puts them in place); an image's rows, and so the
+  // 32-row statistics blocks its GroupNorm sums, stay contiguous. Tap-major K order only.
+  int up_phase = 0;
+  int w_ps = 0;  // element stride between the four phase matrices
 };
 constexpr int kProbeWords = 48;
 extern thread_local unsigned long long* g_conv_probe;  // picked up by launch_conv_gemm in the probe build
@@ -154,6 +163,9 @@ struct GemmLaunchInfo {
   int tile_group = 0;  // group size of the tile walk (0 = row-major)
 };
 GemmLaunchInfo conv_gemm_last_launch();
+// the four phase matrices of a packed 3 x 3 weight (ConvGemmParams::up_phase): w [Npad][3][3][Cpad] -> out [2 a + b][Npad][2][2][Cpad],
+// row taps {w0, w1 + w2} for a = 0 and {w0 + w1, w2} for a = 1 (columns alike with b); summed in fp32, rounded once
+void launch_up_phase_weights(hipStream_t st, const bf16_t* w, bf16_t* out, int Npad, int Cpad);
 int conv_gemm_num_configs();
 const char* conv_gemm_config_name(int id);
 
@@ -291,6 +303,9 @@ void launch_vec_linear(hipStream_t st, const float* x, int ldx, const float* W, 
 void launch_avgpool2(hipStream_t st, const bf16_t* x, bf16_t* y, int B, int H, int W, int C);
 // nearest x2 upsample (materialised; only where it cannot be folded into a conv)
 void launch_upsample2(hipStream_t st, const bf16_t* x, bf16_t* y, int B, int H, int W, int C);
+// output of a phase-form x2 conv (ConvGemmParams::up_phase) into image order: x [B][2 a + b][H][W][C] (dense) ->
+// y [B][2 y + a][2 x + b][ldy], 16-byte vectors (C and ldy multiples of 8)
+void launch_up_phase_reorder(hipStream_t st, const bf16_t* x, bf16_t* y, int B, int H, int W, int C, int ldy);
 // DiagonalGaussianDistribution sample (distributions.py:24-37) from moments NHWC fp32 [B][HW][2*zc]:
 // z = (mean + exp(0.5*clamp(logvar,-30,20))*noise) * scale -> fp32 NCHW [B][zc][HW]
 void launch_posterior_sample(hipStream_t st, const float* mom, int ld, const float* noise,

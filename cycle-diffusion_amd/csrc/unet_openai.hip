@@ -279,7 +279,7 @@ UNetOpenAI::UNetOpenAI(const cd_net_desc& d) {
         Layer u;
         const std::string up = pfx + "." + std::to_string(sub);
         if (d.resblock_updown) { u.kind = Layer::RES; u.idx = add_res_named(up, ch, ch, true, false); }
-        else { u.kind = Layer::UP_CONV; u.conv = make_conv(params, up + ".conv", ch, ch, 3, true); }
+        else { u.kind = Layer::UP_CONV; u.conv = make_conv(params, up + ".conv", ch, ch, 3, true); params.add_up_phase(u.conv); }
         b.layers.push_back(u);
         ds /= 2;
       }
@@ -646,9 +646,13 @@ Act UNetOpenAI::run_block(Ctx& c, const Block& b, Act h, const Act* skip, const 
 }
 
 // W' = W diag(gamma), b' = b + W beta for the LayerNorm-folded layers (attention.py:211-215: x + attn2(norm2(x)),
-// x + ff(norm3(x))), in both weight layouts; stream-ordered, a few microseconds, only after a parameter load
+// x + ff(norm3(x))), in both weight layouts; stream-ordered, a few microseconds, only after a parameter load.
+// The phase matrices of the Upsample convs (ConvGemmParams::up_phase) are derived weights of the same kind.
 void UNetOpenAI::refresh_ln_folds(Ctx& c) {
   if (folded_version_ == params.version) return;
+  for (const Block& b : out_blocks_)
+    for (const Layer& l : b.layers)
+      if (l.kind == Layer::UP_CONV) params.refresh_up_phase(c.st, l.conv);
   for (STW& s : st_) {
     if (!s.q2_ln) continue;
     struct { const ConvW* src; ConvW* dst; const LNW* ln; } jobs[2] = {{s.q2, s.q2_ln, &s.ln2}, {s.ff1, s.ff1_ln, &s.ln3}};

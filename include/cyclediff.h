@@ -287,6 +287,11 @@ int cd_op_conv2d_16(cd_handle h, const float* x0, int C0, const float* x1, int C
  * bk = K-step depth (32 or 64), splitk = effective split-K factor (1 = none), chm = 1 if the channel-major K order was taken,
  * tile_group = group size of the tile walk (0 = row-major). Read-only; any pointer may be NULL. */
 int cd_op_last_gemm_config(cd_handle h, int* tile_id, int* bk, int* splitk, int* chm, int* tile_group);
+/* the reorder pass behind a phase-form x2 convolution on its own (16-bit values): x fp32 [B, 4, C, H, W], the second index
+ * the output parity 2 a + b -> y fp32 NCHW [B, C, 2 H, 2 W] with y[.., 2 i + a, 2 j + b] = x[.., 2 a + b, .., i, j]; C % 8 == 0.
+ * cd_op_conv2d_16 with up = 1 takes the phase form (and this pass) for 3 x 3 weights without a residual on images of a
+ * multiple of 256 pixels, unless the environment says CYCLEDIFF_UP_PHASE=0 at the time of the call. */
+int cd_op_up_phase_reorder(cd_handle h, const float* x, int B, int C, int H, int W, float* y);
 int cd_op_groupnorm(cd_handle h, const float* x, int B, int C, int H, int W, int G, float eps,
                     const float* gamma, const float* beta, const float* film, int silu, float* y);
 int cd_op_layernorm(cd_handle h, const float* x, int rows, int C, const float* gamma, const float* beta,
