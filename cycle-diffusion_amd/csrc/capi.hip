@@ -408,8 +408,8 @@ MaskBlend mask_blend_of(const MaskArgs& m, const float2* qtab, int k, int slot, 
   b.mask = m.mask; b.mask_bmod = m.B_mask;
   b.src = m.x0; b.src_bmod = m.B_mask;
   b.qtab = qtab; b.qrow = k;
-  b.noise = m.noise ? m.noise + (int64_t)slot * n : nullptr;
-  b.seed = m.seed; b.stream = (uint32_t)(0x4000 + slot);
+  b.gauss.noise = m.noise ? m.noise + (int64_t)slot * n : nullptr;
+  b.gauss.seed = m.seed; b.gauss.stream = (uint32_t)(0x4000 + slot);
   return b;
 }
 
@@ -418,13 +418,13 @@ struct SamplerState {
   int B = 0, Bn = 0, C = 0, HW = 0, cpad = 0, out_ld = 0;
   bool cfg = false;
   bool f32 = false;  // CD_PREC_F32 network: its NHWC input is fp32 and is rebuilt from xt before every forward
-  bf16_t* xin16() const { return f32 ? nullptr : xin; }
   float g = 1.f;
   float* xt = nullptr;
   bf16_t* xin = nullptr;
   float* eh = nullptr;
-  StepCoef* tab = nullptr;
-  EpsHat ehv;
+  // what the step launches of one call share: xt, the view of eh, B / C / HW, the 16-bit input of the next forward (none for
+  // an f32 network). The loops add the table and, per step, the row, the draw and the eps / z pointers.
+  StepArgs args;
 };
 
 SamplerState setup_sampler(cd_engine* h, int net, const float* ctx_c, const float* ctx_uc, int ctx_len,
@@ -451,8 +451,12 @@ SamplerState setup_sampler(cd_engine* h, int net, const float* ctx_c, const floa
   s.xin = (bf16_t*)h->arena.alloc((size_t)s.Bn * s.HW * s.cpad * esz);
   HIP_CHECK(hipMemsetAsync(s.xin, 0, (size_t)s.Bn * s.HW * s.cpad * esz, h->st));
   s.eh = (float*)h->arena.alloc((size_t)s.Bn * s.HW * s.out_ld * 4);
-  s.ehv.p = s.eh; s.ehv.sb = (int64_t)s.HW * s.out_ld; s.ehv.sc = 1; s.ehv.sp = s.out_ld;
-  s.ehv.cfg = s.cfg ? 1 : 0; s.ehv.g = guidance;
+  StepArgs& a = s.args;
+  a.xt = s.xt;
+  a.eh.p = s.eh; a.eh.sb = (int64_t)s.HW * s.out_ld; a.eh.sc = 1; a.eh.sp = s.out_ld;
+  a.eh.cfg = s.cfg ? 1 : 0; a.eh.g = guidance;
+  a.geom.B = B; a.geom.C = s.C; a.geom.HW = s.HW;
+  a.xin.xin = s.f32 ? nullptr : s.xin; a.xin.cpad = s.cpad; a.xin.dup = s.cfg ? 1 : 0;
   return s;
 }
 
@@ -465,7 +469,7 @@ void run_unet(cd_engine* h, SamplerState& s, int step) {
                               s.u->x3 ? 1 : 0, h->overflow_dev);
   }
   UNetIO io;
-  io.xin = s.xin; io.B = s.Bn; io.tab = s.tab; io.step = step; io.t_shared = true;
+  io.xin = s.xin; io.B = s.Bn; io.tab = s.args.geom.tab; io.step = step; io.t_shared = true;
   io.cfg_dup = s.cfg;
   io.out = s.eh; io.out_ld = s.out_ld;
   s.u->forward(c, io);
@@ -610,18 +614,21 @@ int cd_dpm_encode(cd_handle h, int net, int sched_kind, const float* x0, const f
   // the 'ddpm' posterior kernels carry no classifier-free-guidance combine (the pixel DDPMs that use them are unconditional,
   // ddpm_ddim_wrapper.py:230-238): a guided call would silently run unguided
   CD_CHECK(sched_kind == CD_SCHED_DDIM || !s.cfg, "classifier-free guidance is only implemented for sched_kind = CD_SCHED_DDIM");
-  s.tab = upload_coef(h, coef_host, K + 1);
+  StepArgs& a = s.args;
+  a.geom.tab = upload_coef(h, coef_host, K + 1);
   const int64_t chw = (int64_t)s.C * s.HW, n = (int64_t)B * chw;
   const int64_t zbs = (int64_t)(K + 1) * chw;
-  launch_init_xt(h->st, x0, noise, seed, 0u, s.xt, z_out, zbs, B, s.C, s.HW, s.tab, K, s.xin16(), s.cpad,
-                 s.cfg ? 1 : 0);
+  a.x0 = x0; a.gauss.seed = seed; a.z.bstride = zbs;
+  a.geom.step = K; a.gauss.noise = noise; a.gauss.stream = 0u; a.z.p = z_out;
+  launch_init_xt(h->st, a);
   for (int i = 0; i < K; ++i) {
     const int k = K - 1 - i;
     run_unet(h, s, k);
     const int is_last = (last_uses_x0 && k == 0) ? 1 : 0;
     const float* nz = (noise && !is_last) ? noise + (int64_t)(1 + i) * n : nullptr;
-    launch_encode_step(h->st, sched_kind, x0, s.xt, s.ehv, nz, seed, (uint32_t)(1 + i), z_out + (1 + i) * chw,
-                       zbs, B, s.C, s.HW, s.tab, nullptr, k, is_last, s.xin16(), s.cpad, s.cfg ? 1 : 0);
+    a.geom.step = k; a.is_last = is_last;
+    a.gauss.noise = nz; a.gauss.stream = (uint32_t)(1 + i); a.z.p = z_out + (1 + i) * chw;
+    launch_encode_step(h->st, sched_kind, a);
     h->pacer.tick(h->st);
   }
   CD_API_END
@@ -640,29 +647,33 @@ static void ddim_decode_impl(cd_handle h, int net, int sched_kind, const float* 
   CD_CHECK(sched_kind == CD_SCHED_DDIM || !s.cfg, "classifier-free guidance is only implemented for sched_kind = CD_SCHED_DDIM");
   if (gvec) {
     CD_CHECK(s.cfg, "per-sample guidance needs the classifier-free-guidance batch (both contexts)");
-    s.ehv.gvec = gvec;
+    s.args.eh.gvec = gvec;
   }
-  s.tab = upload_coef(h, coef_host, K);
+  StepArgs& a = s.args;
+  a.geom.tab = upload_coef(h, coef_host, K);
   const int64_t chw = (int64_t)s.C * s.HW, n = (int64_t)B * chw;
   const int64_t zbs = (int64_t)z_slots * chw;
+  a.eps.bstride = zbs; a.gauss.seed = seed;
   // x = z[:, 0]  (sd_wrapper:153; ddpm_ddim_wrapper.py:404)
   HIP_CHECK(hipMemcpy2DAsync(s.xt, chw * 4, z, zbs * 4, chw * 4, B, hipMemcpyDeviceToDevice, h->st));
   const float2* qtab = nullptr;
   if (mk) {  // img = q_sample(x0, ts) * mask + (1. - mask) * img ahead of the first forward too (ddim.py:427-430)
     qtab = (const float2*)upload_table(h, mk->qcoef_host, (size_t)K * 2 * sizeof(float));
-    launch_mask_blend_init(h->st, s.xt, mask_blend_of(*mk, qtab, K - 1, 0, n), B, s.C, s.HW, s.xin16(), s.cpad, s.cfg ? 1 : 0);
+    launch_mask_blend_init(h->st, a, mask_blend_of(*mk, qtab, K - 1, 0, n));
   } else if (!s.f32) launch_nchw_to_nhwc(h->st, s.xt, s.xin, B, s.C, s.HW, s.cpad, 1.f, 0.f, s.cfg ? 1 : 0);
   for (int i = 0; i < K; ++i) {
     const int k = K - 1 - i;
     run_unet(h, s, k);
     const float* eps = (i < n_eps) ? z + (int64_t)(1 + i) * chw : nullptr;
     const float* nz = (!eps && noise_tail) ? noise_tail + (int64_t)(i - n_eps) * n : nullptr;
-    if (mk)
-      launch_decode_step_masked(h->st, s.xt, s.ehv, eps, zbs, nz, seed, (uint32_t)(0x1000 + i), B, s.C, s.HW, s.tab, nullptr, k,
-                                s.xin16(), s.cpad, s.cfg ? 1 : 0, 0, mask_blend_of(*mk, qtab, k - 1, i + 1, n), k > 0 ? 1 : 0);
-    else
-    launch_decode_step(h->st, sched_kind, s.xt, s.ehv, eps, zbs, nz, seed, (uint32_t)(0x1000 + i), B, s.C,
-                       s.HW, s.tab, nullptr, k, s.xin16(), s.cpad, s.cfg ? 1 : 0, nullptr);
+    a.geom.step = k; a.eps.p = eps;
+    a.gauss.noise = nz; a.gauss.stream = (uint32_t)(0x1000 + i);
+    if (mk) {
+      const MaskBlend next = mask_blend_of(*mk, qtab, k - 1, i + 1, n);
+      launch_decode_step(h->st, sched_kind, a, &next, /*blend=*/k > 0);
+    } else {
+      launch_decode_step(h->st, sched_kind, a);
+    }
     h->pacer.tick(h->st);
   }
   HIP_CHECK(hipMemcpyAsync(x_out, s.xt, (size_t)n * 4, hipMemcpyDeviceToDevice, h->st));
@@ -691,7 +702,7 @@ int cd_ddim_decode_v(cd_handle h, int net, int sched_kind, const float* z, int z
 }
 
 // Region-keeping decode: DDIMSampler.sample_with_eps(mask=, x0=) (ddim.py:170-228, 427-430). One launch per sampler step: the
-// blend ahead of the forward of level k-1 is the tail of decode step k (sched.hip k_decode_step_ddim_masked).
+// blend ahead of the forward of level k-1 is the tail of decode step k (sched.hip k_decode_step_ddim<true>).
 int cd_ddim_decode_masked(cd_handle h, int net, int sched_kind, const float* z, int z_slots, int n_eps, const float* ctx_c,
                           const float* ctx_uc, int ctx_len, float guidance, const float* guidance_per_sample, int B, int K,
                           const cd_step_coef* coef_host, const float* noise_tail, uint64_t seed, const float* mask,
@@ -712,7 +723,7 @@ int cd_ddim_decode_masked(cd_handle h, int net, int sched_kind, const float* z, 
 // Deterministic DDIM inversion (DDIB's encoder): DiffusionCLIP's denoising_step(..., eta=0, sampling_type='ddim') walked with
 // t_next > t (model/lib/ddpm_ddim/utils/diffusion_utils.py:114-121). With eta = 0 that step is
 //   x0_hat = (x - sqrt(1-a_in)*e)/sqrt(a_in) ;  x <- sqrt(a_out)*x0_hat + sqrt(1-a_out)*e
-// which is k_decode_step_ddim with sigma = 0 in the same operation order (a sigma = 0 row draws no noise and adds +0), so the
+// which is k_decode_step_ddim<false> with sigma = 0 in the same operation order (a sigma = 0 row draws no noise and adds +0), so the
 // decode kernel - including its fused write of the next forward's input - runs every step. Rows are in loop order: row j is
 // step j, its `t` the timestep of the input's level.
 int cd_ddim_invert(cd_handle h, int net, int sched_kind, const float* x0, const float* ctx_c, const float* ctx_uc,
@@ -726,14 +737,15 @@ int cd_ddim_invert(cd_handle h, int net, int sched_kind, const float* x0, const 
     CD_CHECK(coef_host[j].sigma == 0.f && coef_host[j].sa > 0.f, "inversion row %d: sigma must be 0 and sa > 0", j);
   ArenaScope arena_scope(h->arena);
   SamplerState s = setup_sampler(h, net, ctx_c, ctx_uc, ctx_len, guidance, B);
-  s.tab = upload_coef(h, coef_host, K);
+  StepArgs& a = s.args;
+  a.geom.tab = upload_coef(h, coef_host, K);
   const int64_t n = (int64_t)B * s.C * s.HW;
   HIP_CHECK(hipMemcpyAsync(s.xt, x0, (size_t)n * 4, hipMemcpyDeviceToDevice, h->st));
   if (!s.f32) launch_nchw_to_nhwc(h->st, s.xt, s.xin, B, s.C, s.HW, s.cpad, 1.f, 0.f, s.cfg ? 1 : 0);
   for (int j = 0; j < K; ++j) {
     run_unet(h, s, j);
-    launch_decode_step(h->st, CD_SCHED_DDIM, s.xt, s.ehv, nullptr, 0, nullptr, 0, (uint32_t)(0x3000 + j), B, s.C, s.HW,
-                       s.tab, nullptr, j, s.xin16(), s.cpad, s.cfg ? 1 : 0, nullptr);
+    a.geom.step = j; a.gauss.stream = (uint32_t)(0x3000 + j);
+    launch_decode_step(h->st, CD_SCHED_DDIM, a);
     if (traj_out) HIP_CHECK(hipMemcpyAsync(traj_out + (int64_t)j * n, s.xt, (size_t)n * 4, hipMemcpyDeviceToDevice, h->st));
     h->pacer.tick(h->st);
   }
@@ -792,15 +804,25 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
   const size_t row_in = (size_t)HW * cpad * esz;  // bytes of one sample of the network input
   bf16_t* xin_e = f32 ? nullptr : (bf16_t*)xin;
   bf16_t* xin_d = f32 ? nullptr : (bf16_t*)(xin + (size_t)Ben * row_in);
-  EpsHat eh_e, eh_d;
+  StepArgs enc, dec;  // the step launches of the encoder's and of the decoder's rows
+  EpsHat &eh_e = enc.eh, &eh_d = dec.eh;
   eh_e.p = eh; eh_e.sb = (int64_t)HW * out_ld; eh_e.sc = 1; eh_e.sp = out_ld; eh_e.cfg = ge.cfg ? 1 : 0; eh_e.g = enc_guidance;
   eh_d = eh_e; eh_d.p = eh + (int64_t)Ben * HW * out_ld; eh_d.cfg = gd.cfg ? 1 : 0; eh_d.g = dec_guidance;
   eh_d.gvec = dec_guidance_per_sample;
   StepCoef* tab_e = upload_coef(h, coef_enc_host, K + 1);
   StepCoef* tab_d = upload_coef(h, coef_dec_host, K);
   const int64_t zbs = (int64_t)(K + 1) * chw;
+  enc.x0 = x0; enc.xt = xt_e;
+  enc.geom.B = B; enc.geom.C = C; enc.geom.HW = HW; enc.geom.tab = tab_e;
+  enc.xin.xin = xin_e; enc.xin.cpad = cpad; enc.xin.dup = ge.cfg ? 1 : 0;
+  enc.gauss.seed = seed; enc.z.bstride = zbs;
+  dec.xt = xt_d;
+  dec.geom.B = Bd; dec.geom.C = C; dec.geom.HW = HW; dec.geom.tab = tab_d;
+  dec.xin.xin = xin_d; dec.xin.cpad = cpad; dec.xin.dup = gd.cfg ? 1 : 0;
+  dec.gauss.seed = seed; dec.eps.bstride = zbs; dec.eps.bmod = n_dec > 1 ? B : 0;
   // x_T (ddim.py:477-479), z[:, 0]; the decoder starts from the same tensor (sd_wrapper:153), once per decoder scale
-  launch_init_xt(h->st, x0, noise, seed, 0u, xt_e, z_out, zbs, B, C, HW, tab_e, K, xin_e, cpad, ge.cfg ? 1 : 0);
+  enc.geom.step = K; enc.gauss.noise = noise; enc.gauss.stream = 0u; enc.z.p = z_out;
+  launch_init_xt(h->st, enc);
   for (int j = 0; j < n_dec; ++j)
     HIP_CHECK(hipMemcpyAsync(xt_d + (int64_t)j * n, xt_e, (size_t)n * 4, hipMemcpyDeviceToDevice, h->st));
   // the keep-mask blend of level k for the decoder rows: q_sample(x0) with the draw of iteration `slot`, or - "encoder" - the
@@ -812,7 +834,7 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     if (mk->source == CD_MASK_ENCODER) { b.src = xt_e; b.src_bmod = B; }
     return b;
   };
-  if (mk) launch_mask_blend_init(h->st, xt_d, blend_of(K - 1, 0), Bd, C, HW, xin_d, cpad, gd.cfg ? 1 : 0);
+  if (mk) launch_mask_blend_init(h->st, dec, blend_of(K - 1, 0));
   else if (!f32) launch_nchw_to_nhwc(h->st, xt_d, xin_d, Bd, C, HW, cpad, 1.f, 0.f, gd.cfg ? 1 : 0);
   // rows that repeat the rows just ahead of them (the decoder's cond half repeats its uncond half): the network computes
   // everything ahead of the first cross-attention once for them - only when the encoder half has no such pair of its own
@@ -835,14 +857,16 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     const int is_last = (last_uses_x0 && k == 0) ? 1 : 0;
     const float* nz = (noise && !is_last) ? noise + (int64_t)(1 + i) * n : nullptr;
     float* zslot = z_out + (1 + i) * chw;
-    launch_encode_step(h->st, sched_kind, x0, xt_e, eh_e, nz, seed, (uint32_t)(1 + i), zslot, zbs, B, C, HW, tab_e, nullptr, k,
-                       is_last, xin_e, cpad, ge.cfg ? 1 : 0);
-    if (mk)
-      launch_decode_step_masked(h->st, xt_d, eh_d, zslot, zbs, nullptr, seed, (uint32_t)(0x1000 + i), Bd, C, HW, tab_d, nullptr, k,
-                                xin_d, cpad, gd.cfg ? 1 : 0, /*eps_bmod=*/n_dec > 1 ? B : 0, blend_of(k - 1, i + 1), k > 0 ? 1 : 0);
-    else
-    launch_decode_step(h->st, sched_kind, xt_d, eh_d, zslot, zbs, nullptr, seed, (uint32_t)(0x1000 + i), Bd, C, HW, tab_d,
-                       nullptr, k, xin_d, cpad, gd.cfg ? 1 : 0, nullptr, /*eps_bmod=*/n_dec > 1 ? B : 0);
+    enc.geom.step = k; enc.is_last = is_last;
+    enc.gauss.noise = nz; enc.gauss.stream = (uint32_t)(1 + i); enc.z.p = zslot;
+    launch_encode_step(h->st, sched_kind, enc);
+    dec.geom.step = k; dec.eps.p = zslot; dec.gauss.stream = (uint32_t)(0x1000 + i);
+    if (mk) {
+      const MaskBlend next = blend_of(k - 1, i + 1);
+      launch_decode_step(h->st, sched_kind, dec, &next, /*blend=*/k > 0);
+    } else {
+      launch_decode_step(h->st, sched_kind, dec);
+    }
     h->pacer.tick(h->st);
   }
   HIP_CHECK(hipMemcpyAsync(x_out, xt_d, (size_t)Bd * chw * 4, hipMemcpyDeviceToDevice, h->st));
@@ -889,15 +913,18 @@ int cd_pix_refine(cd_handle h, int net, int sched_kind, float* x, int B, int R, 
   CD_CHECK(h && x && coef_host && B > 0 && R > 0, "bad argument");
   ArenaScope arena_scope(h->arena);
   SamplerState s = setup_sampler(h, net, nullptr, nullptr, 0, 1.f, B);
-  s.tab = upload_coef(h, coef_host, R + 1);
+  StepArgs& a = s.args;
+  a.geom.tab = upload_coef(h, coef_host, R + 1);
   const int64_t n = (int64_t)B * s.C * s.HW;
-  launch_init_xt(h->st, x, noise, seed, 0x2000u, s.xt, nullptr, 0, B, s.C, s.HW, s.tab, R, s.xin16(), s.cpad, 0);
+  a.x0 = x; a.gauss.seed = seed;
+  a.geom.step = R; a.gauss.noise = noise; a.gauss.stream = 0x2000u;
+  launch_init_xt(h->st, a);
   for (int i = 0; i < R; ++i) {
     const int k = R - 1 - i;
     run_unet(h, s, k);
     const float* nz = noise ? noise + (int64_t)(1 + i) * n : nullptr;
-    launch_decode_step(h->st, sched_kind, s.xt, s.ehv, nullptr, 0, nz, seed, (uint32_t)(0x2001 + i), B, s.C,
-                       s.HW, s.tab, nullptr, k, s.xin16(), s.cpad, 0, nullptr);
+    a.geom.step = k; a.gauss.noise = nz; a.gauss.stream = (uint32_t)(0x2001 + i);
+    launch_decode_step(h->st, sched_kind, a);
     h->pacer.tick(h->st);
   }
   HIP_CHECK(hipMemcpyAsync(x, s.xt, (size_t)n * 4, hipMemcpyDeviceToDevice, h->st));
@@ -1097,7 +1124,7 @@ int cd_op_timestep_embedding(cd_handle h, const float* t, int B, int dim, int mo
   CD_API_BEGIN
   enter_engine(h);
   CD_CHECK(h && t && out, "bad argument");
-  launch_timestep_embedding(h->st, nullptr, nullptr, 0, t, out, B, dim, mode);
+  launch_timestep_embedding(h->st, nullptr, 0, t, out, B, dim, mode);
   CD_API_END
 }
 
@@ -1108,23 +1135,23 @@ int cd_op_sched_step(cd_handle h, int mode, int sched_kind, const cd_step_coef* 
   enter_engine(h);
   CD_CHECK(h && coef_host && xt, "bad argument");
   ArenaScope arena_scope(h->arena);
-  StepCoef* tab = upload_coef(h, coef_host, 1);
   const int64_t chw = (int64_t)C * HW;
-  EpsHat eh; eh.p = eps_hat; eh.sb = chw; eh.sc = HW; eh.sp = 1; eh.cfg = cfg; eh.g = guidance;  // NCHW view
-  if (mode == 0) {
-    launch_init_xt(h->st, x0, noise, 0, 0, xt, z_slot, chw, B, C, HW, tab, 0, nullptr, 0, 0);
-  } else if (mode == 1) {
-    launch_encode_step(h->st, sched_kind, x0, xt, eh, noise, 0, 0, z_slot, chw, B, C, HW, tab, nullptr, 0,
-                       is_last, nullptr, 0, 0);
-  } else {
-    launch_decode_step(h->st, sched_kind, xt, eh, eps_in, chw, noise, 0, 0, B, C, HW, tab, nullptr, 0, nullptr,
-                       0, 0, nullptr);
-  }
+  StepArgs a;
+  a.x0 = x0; a.xt = xt;
+  a.eh.p = eps_hat; a.eh.sb = chw; a.eh.sc = HW; a.eh.sp = 1; a.eh.cfg = cfg; a.eh.g = guidance;  // NCHW view
+  a.geom.B = B; a.geom.C = C; a.geom.HW = HW; a.geom.tab = upload_coef(h, coef_host, 1);
+  a.gauss.noise = noise;
+  a.eps.p = eps_in; a.eps.bstride = chw;
+  a.z.p = z_slot; a.z.bstride = chw;
+  a.is_last = is_last;
+  if (mode == 0) launch_init_xt(h->st, a);
+  else if (mode == 1) launch_encode_step(h->st, sched_kind, a);
+  else launch_decode_step(h->st, sched_kind, a);
   HIP_CHECK(hipStreamSynchronize(h->st));
   CD_API_END
 }
 
-// the masked step kernels on explicit tensors: mode 0 = k_mask_blend_init, 2 = k_decode_step_ddim_masked (blend = 0: last step)
+// the masked step kernels on explicit tensors: mode 0 = k_mask_blend_init, 2 = k_decode_step_ddim<true> (blend = 0: last step)
 int cd_op_sched_step_masked(cd_handle h, int mode, const cd_step_coef* coef_host, float* x, const float* eps_hat, int cfg,
                             float guidance, const float* eps_in, const float* mask, const float* src, int B_mask,
                             int mask_source, float qa, float qb, const float* mask_noise, int blend, int B, int C, int HW,
@@ -1137,19 +1164,23 @@ int cd_op_sched_step_masked(cd_handle h, int mode, const cd_step_coef* coef_host
   ArenaScope arena_scope(h->arena);
   const int64_t chw = (int64_t)C * HW;
   MaskBlend mk;
-  mk.mask = mask; mk.src = src; mk.mask_bmod = mk.src_bmod = B_mask; mk.noise = mask_noise;
+  mk.mask = mask; mk.src = src; mk.mask_bmod = mk.src_bmod = B_mask; mk.gauss.noise = mask_noise;
   if (mask_source == CD_MASK_QSAMPLE) {
     CD_CHECK(mask_noise, "q_sample mode needs the noise tensor here");
     const float q[2] = {qa, qb};
     mk.qtab = (const float2*)upload_table(h, q, sizeof(q));
   }
+  StepArgs a;
+  a.xt = x;
+  a.geom.B = B; a.geom.C = C; a.geom.HW = HW;
+  a.xin.xin = (bf16_t*)xin16_out; a.xin.cpad = C; a.xin.dup = cfg_dup;
   if (mode == 0) {
-    launch_mask_blend_init(h->st, x, mk, B, C, HW, (bf16_t*)xin16_out, C, cfg_dup);
+    launch_mask_blend_init(h->st, a, mk);
   } else {
-    StepCoef* tab = upload_coef(h, coef_host, 1);
-    EpsHat eh; eh.p = eps_hat; eh.sb = chw; eh.sc = HW; eh.sp = 1; eh.cfg = cfg; eh.g = guidance;  // NCHW view
-    launch_decode_step_masked(h->st, x, eh, eps_in, chw, nullptr, 0, 0, B, C, HW, tab, nullptr, 0, (bf16_t*)xin16_out, C,
-                              cfg_dup, 0, mk, blend);
+    a.geom.tab = upload_coef(h, coef_host, 1);
+    a.eh.p = eps_hat; a.eh.sb = chw; a.eh.sc = HW; a.eh.sp = 1; a.eh.cfg = cfg; a.eh.g = guidance;  // NCHW view
+    a.eps.p = eps_in; a.eps.bstride = chw;
+    launch_decode_step(h->st, CD_SCHED_DDIM, a, &mk, blend != 0);
   }
   HIP_CHECK(hipStreamSynchronize(h->st));
   CD_API_END

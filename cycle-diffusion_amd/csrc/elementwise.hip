@@ -60,15 +60,15 @@ __global__ void k_nhwc_to_nchw(const void* __restrict__ x, int x_f32, int ldx, f
   }
 }
 
-__global__ void k_timestep_embedding(const StepCoef* tab, const int* step_ptr, int step,
-                                     const float* t_explicit, float* out, int B, int dim, int mode) {
+__global__ void k_timestep_embedding(const StepCoef* tab, int step, const float* t_explicit,
+                                     float* out, int B, int dim, int mode) {
   const int half = dim / 2;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * half) return;
   const int b = i / half, k = i % half;
   float t;
   if (t_explicit) t = t_explicit[b];
-  else t = (float)tab[step_ptr ? *step_ptr : step].t;
+  else t = (float)tab[step].t;
   float* o = out + (int64_t)b * dim;
   if (mode == 0) {
     // util.py:162-167: freqs = exp(-log(1e4) * arange(half)/half); cat([cos, sin])
@@ -337,11 +337,11 @@ void launch_nhwc_to_nchw(hipStream_t st, const void* x, int x_f32, int ldx, floa
   hipLaunchKernelGGL(k_nhwc_to_nchw, dim3(ew_grid(n)), dim3(256), 0, st, x, x_f32, ldx, y, B, C, HW,
                      scale, shift);
 }
-void launch_timestep_embedding(hipStream_t st, const StepCoef* tab, const int* step_ptr, int step,
-                               const float* t_explicit, float* out, int B, int dim, int mode) {
+void launch_timestep_embedding(hipStream_t st, const StepCoef* tab, int step, const float* t_explicit,
+                               float* out, int B, int dim, int mode) {
   const int n = B * (dim / 2);
-  hipLaunchKernelGGL(k_timestep_embedding, dim3(ceil_div(n, 256)), dim3(256), 0, st, tab, step_ptr,
-                     step, t_explicit, out, B, dim, mode);
+  hipLaunchKernelGGL(k_timestep_embedding, dim3(ceil_div(n, 256)), dim3(256), 0, st, tab, step,
+                     t_explicit, out, B, dim, mode);
 }
 void launch_vec_linear(hipStream_t st, const float* x, int ldx, const float* W, const float* bias,
                        float* y, int ldy, int B, int K, int N, int silu_in, int silu_out) {

@@ -218,8 +218,8 @@ struct TimeEmb {  // shared by all U-Nets: sinusoid -> MLP -> per-ResBlock proje
 struct UNetIO {
   const bf16_t* xin = nullptr;   // NHWC bf16 [B][H][W][Cpad_in]
   int B = 0;
-  // timestep source: either a schedule table row (device step counter or immediate) or explicit floats
-  const StepCoef* tab = nullptr; const int* step_ptr = nullptr; int step = 0;
+  // timestep source: either a schedule table row or explicit floats
+  const StepCoef* tab = nullptr; int step = 0;
   const float* t_explicit = nullptr;  // [B] device, or null
   bool t_shared = true;               // all samples share one timestep -> embed once
   // classifier-free-guidance batch [uncond B/2 | cond B/2] built from ONE x_t (ddim.py:553-559 th.cat([x] * 2)): rows

@@ -20,28 +20,52 @@ struct StepCoef {
 enum { SCHED_DDIM = 0, SCHED_DDPM = 1 };
 
 struct EpsHat {  // network output view: element (b,c,p) at p[b*sb + c*sc + p*sp]
-  const float* p;
-  int64_t sb, sc, sp;
-  int cfg;   // 1: batch is [uncond B | cond B], combine with guidance scale g
-  float g;
+  const float* p = nullptr;
+  int64_t sb = 0, sc = 0, sp = 0;
+  int cfg = 0;   // 1: batch is [uncond B | cond B], combine with guidance scale g
+  float g = 1.f;
   const float* gvec = nullptr;  // per-sample guidance scales [B] (device) instead of g: ensemble members that differ only
                                 // in their decoder scale share one launch set
 };
 
-void launch_init_xt(hipStream_t st, const float* x0, const float* noise, uint64_t seed,
-                    uint32_t stream, float* xt, float* z, int64_t z_bstride, int B, int C, int HW,
-                    const StepCoef* tab, int step, bf16_t* xin, int xin_cpad, int cfg_dup);
-void launch_encode_step(hipStream_t st, int kind, const float* x0, float* xt, const EpsHat& eh,
-                        const float* noise, uint64_t seed, uint32_t stream, float* z,
-                        int64_t z_bstride, int B, int C, int HW, const StepCoef* tab,
-                        const int* step_ptr, int step, int is_last, bf16_t* xin, int xin_cpad,
-                        int cfg_dup_next);
-void launch_decode_step(hipStream_t st, int kind, float* x, const EpsHat& eh, const float* eps,
-                        int64_t eps_bstride, const float* noise, uint64_t seed, uint32_t stream,
-                        int B, int C, int HW, const StepCoef* tab, const int* step_ptr, int step,
-                        bf16_t* xin, int xin_cpad, int cfg_dup_next, float* x0_pred, int eps_bmod = 0);
-// eps_bmod > 0: sample b takes its injected eps from slot sample b % eps_bmod (the coupled loop decodes several guidance scales
-// of the same eps_bmod encoder samples in one batch)
+// Arguments of the step kernels, passed to them by value; every default means "off".
+struct StepGeom {  // the batch and this step's row of the device-resident coefficient table
+  int B = 0, C = 0, HW = 0;
+  const StepCoef* tab = nullptr;
+  int step = 0;
+};
+struct GaussSrc {  // a standard-normal draw per element: the tensor [B, C, HW], or null -> Philox(seed, stream)
+  const float* noise = nullptr;
+  uint64_t seed = 0;
+  uint32_t stream = 0;
+};
+struct XinOut {  // the next forward's 16-bit NHWC input [B, HW, cpad], or null -> not written
+  bf16_t* xin = nullptr;
+  int cpad = 0;
+  int dup = 0;  // 1: written again B samples on (the classifier-free-guidance batch [uncond | cond] of one x_t)
+};
+struct EpsIn {  // injected eps (decode only): sample b at p[b * bstride], or null -> drawn from the GaussSrc
+  const float* p = nullptr;
+  int64_t bstride = 0;
+  int bmod = 0;  // > 0: sample b takes the eps of sample b % bmod (the coupled loop decodes several guidance scales of the
+                 // same bmod encoder samples in one batch)
+};
+struct ZSlot {  // where init / encode store x_T / eps (sample b at p[b * bstride]); init: null -> not stored
+  float* p = nullptr;
+  int64_t bstride = 0;
+};
+struct StepArgs {
+  const float* x0 = nullptr;  // init / encode: the clean sample
+  float* xt = nullptr;        // the running latent, updated in place
+  EpsHat eh;                  // encode / decode
+  StepGeom geom;
+  GaussSrc gauss;
+  XinOut xin;
+  EpsIn eps;       // decode
+  ZSlot z;         // init / encode
+  int is_last = 0; // encode ('ddim'): x_next = x0 without a draw
+};
+
 // region-keeping decode (ddim.py:427-430): what the masked step kernels blend into the decoder's latent ahead of a forward
 struct MaskBlend {
   const float* mask = nullptr;   // [mask_bmod, 1, HW], 1 = keep the source
@@ -49,19 +73,15 @@ struct MaskBlend {
   int mask_bmod = 1, src_bmod = 1;
   const float2* qtab = nullptr;  // "q_sample": (sqrt_alphas_cumprod, sqrt_one_minus_alphas_cumprod)[tau[k]] by row k; else null
   int qrow = 0;                  // row of the level being blended
-  const float* noise = nullptr;  // "q_sample": that level's draw [B, C, HW], or null -> Philox(seed, stream)
-  uint64_t seed = 0;
-  uint32_t stream = 0;
+  GaussSrc gauss;                // "q_sample": that level's draw
 };
-void launch_mask_blend_init(hipStream_t st, float* x, const MaskBlend& mk, int B, int C, int HW, bf16_t* xin, int xin_cpad,
-                            int cfg_dup);
-// SCHED_DDIM only; blend = 0 on the last step (nothing is blended after it)
-void launch_decode_step_masked(hipStream_t st, float* x, const EpsHat& eh, const float* eps, int64_t eps_bstride,
-                               const float* noise, uint64_t seed, uint32_t stream, int B, int C, int HW,
-                               const StepCoef* tab, const int* step_ptr, int step, bf16_t* xin, int xin_cpad,
-                               int cfg_dup_next, int eps_bmod, const MaskBlend& mk, int blend);
-void launch_set_int(hipStream_t st, int* p, int v);
-void launch_add_int(hipStream_t st, int* p, int d);
+
+void launch_init_xt(hipStream_t st, const StepArgs& a);
+void launch_encode_step(hipStream_t st, int kind, const StepArgs& a);
+// mk: SCHED_DDIM only, the step is followed by the blend of the next level unless blend is false (the last step)
+void launch_decode_step(hipStream_t st, int kind, const StepArgs& a, const MaskBlend* mk = nullptr, bool blend = false);
+// a.xt <- blend(a.xt) ahead of the first forward; uses a.geom and a.xin beside it
+void launch_mask_blend_init(hipStream_t st, const StepArgs& a, const MaskBlend& mk);
 
 // ---------------------------------------------------------------- implicit-GEMM conv / GEMM (conv_gemm.hip)
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_GEGLU = 3, ACT_QGELU = 4, ACT_RELU = 5 };  // QGELU: x*sigmoid(1.702x) (CLIP)
@@ -294,8 +314,8 @@ void launch_nhwc_to_nchw(hipStream_t st, const void* x, int x_f32, int ldx, floa
                          int HW, float scale, float shift);
 // sinusoidal timestep embedding -> fp32 [B][dim]; mode 0: [cos|sin], freq = exp(-ln(1e4)*k/half)
 // (util.py:152-172); mode 1: [sin|cos], divisor half-1 (ddpm/diffusion.py:6-24)
-void launch_timestep_embedding(hipStream_t st, const StepCoef* tab, const int* step_ptr, int step,
-                               const float* t_explicit, float* out, int B, int dim, int mode);
+void launch_timestep_embedding(hipStream_t st, const StepCoef* tab, int step, const float* t_explicit,
+                               float* out, int B, int dim, int mode);
 // small dense layer on fp32 vectors: y[b][n] = act_out(sum_k act_in(x[b][k])*W[n][k] + bias[n]); W bf16 or f32
 void launch_vec_linear(hipStream_t st, const float* x, int ldx, const float* W, const float* bias,
                        float* y, int ldy, int B, int K, int N, int silu_in, int silu_out);

@@ -398,7 +398,7 @@ void UNetHo::forward(Ctx& c, const UNetIO& io) {
   float* e1 = (float*)c.arena->alloc((size_t)tB * temb_ch_ * 4);
   float* emb = (float*)c.arena->alloc((size_t)tB * temb_ch_ * 4);
   float* proj = (float*)c.arena->alloc((size_t)tB * te_.proj_total * 4);
-  launch_timestep_embedding(c.st, io.tab, io.step_ptr, io.step, io.t_explicit, sinu, tB, ch_, 1);
+  launch_timestep_embedding(c.st, io.tab, io.step, io.t_explicit, sinu, tB, ch_, 1);
   launch_vec_linear(c.st, sinu, ch_, te_.w0, te_.b0, e1, temb_ch_, tB, ch_, temb_ch_, 0, 1);
   launch_vec_linear(c.st, e1, temb_ch_, te_.w1, te_.b1, emb, temb_ch_, tB, temb_ch_, temb_ch_, 0, 0);
   launch_vec_linear(c.st, emb, temb_ch_, te_.proj_w, te_.proj_b, proj, te_.proj_total, tB, temb_ch_,

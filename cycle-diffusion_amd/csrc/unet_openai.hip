@@ -677,7 +677,7 @@ void UNetOpenAI::forward(Ctx& c, const UNetIO& io) {
   float* e1 = (float*)c.arena->alloc((size_t)tB * hidden_ * 4);
   float* emb = (float*)c.arena->alloc((size_t)tB * hidden_ * 4);
   float* proj = (float*)c.arena->alloc((size_t)tB * te_.proj_total * 4);
-  launch_timestep_embedding(c.st, io.tab, io.step_ptr, io.step, io.t_explicit, sinu, tB, mc_, 0);
+  launch_timestep_embedding(c.st, io.tab, io.step, io.t_explicit, sinu, tB, mc_, 0);
   launch_vec_linear(c.st, sinu, mc_, te_.w0, te_.b0, e1, hidden_, tB, mc_, hidden_, 0, 1);
   launch_vec_linear(c.st, e1, hidden_, te_.w1, te_.b1, emb, hidden_, tB, hidden_, hidden_, 0, 0);
   launch_vec_linear(c.st, emb, hidden_, te_.proj_w, te_.proj_b, proj, te_.proj_total, tB, hidden_,

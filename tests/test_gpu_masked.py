@@ -71,7 +71,7 @@ def _step_masked(engine, mode, row, x, eh, cfg, g, eps, mask, src, source, qa, q
 @pytest.mark.parametrize("cfg", [False, True], ids=["nocfg", "cfg"])
 @pytest.mark.parametrize("source", ["q_sample", "encoder"])
 def test_masked_step_kernel_bit_exact(engine, cfg, source):
-    """k_decode_step_ddim_masked / k_mask_blend_init against the torch fp32 restatement of the blended step: hard and soft mask
+    """k_decode_step_ddim<true> / k_mask_blend_init against the torch fp32 restatement of the blended step: hard and soft mask
     rows, x and the 16-bit NHWC input of the next forward (with its classifier-free-guidance duplicate)"""
     from test_gpu_ops import _coef
     g = torch.Generator().manual_seed(41)

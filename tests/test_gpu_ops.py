@@ -502,10 +502,8 @@ def _coef(a_t, a_prev, sigma):
             np.sqrt(f(1) - a_t), f(1), 0)
 
 
-def test_sched_steps_bit_exact(engine, report):
-    """fp32 scheduler kernels vs the reference's tensor expressions (ddim.py:576-600, 634-645)."""
+def _ddim_steps_bit_exact(engine, B, C, H, W):
     g = torch.Generator().manual_seed(23)
-    B, C, H, W = 2, 4, 16, 16
     x0, xt, e_u, e_c, nz, eps = [torch.randn(B, C, H, W, generator=g) for _ in range(6)]
     a_t, a_prev, sig = 0.4321, 0.4876, 0.0123
     co = _coef(a_t, a_prev, sig)
@@ -535,7 +533,72 @@ def test_sched_steps_bit_exact(engine, report):
     # last encode step returns x0 without a draw
     got_xn, _ = _ops.sched_step(engine, 1, 0, co, x0=x0, xt=xt, eps_hat=e_c, noise=None, is_last=True)
     assert torch.equal(got_xn, x0)
+
+
+def test_sched_steps_bit_exact(engine, report):
+    """fp32 scheduler kernels vs the reference's tensor expressions (ddim.py:576-600, 634-645)."""
+    _ddim_steps_bit_exact(engine, 2, 4, 16, 16)
     report.add("sched_steps_bit_exact", ok=True)
+
+
+@pytest.mark.parametrize("shape", [(3, 3, 5, 7), (2, 4, 256, 260)], ids=["odd_315", "grid_stride_wrap"])
+def test_sched_steps_bit_exact_index_decode(engine, shape):
+    """The same checks where the element loop can go wrong. 3 x 3 x 5 x 7 = 315 elements: one full block of 256 and a ragged
+    one, an odd channel count, HW no power of two - the (b, c, p) decode of the element index and the batch offset of the
+    guidance pair. 2 x 4 x 256 x 260 = 532 480 elements, above the 2048 x 256 = 524 288 threads a step launch is capped at:
+    some threads run a second iteration of the grid-stride loop."""
+    _ddim_steps_bit_exact(engine, *shape)
+
+
+def test_sched_decode_sigma_zero_row_reads_no_eps(engine):
+    """A table row with sigma = 0 (the eta = 0 tables cd_ddim_invert and the DDIB decode stand on): the step is
+    sap * pred_x0 + dirc * e exactly, and the injected eps - here all NaN - is not read."""
+    g = torch.Generator().manual_seed(31)
+    B, C, H, W = 2, 4, 16, 16
+    xt, e_u, e_c = [torch.randn(B, C, H, W, generator=g) for _ in range(3)]
+    co = _coef(0.4321, 0.4876, 0.0)
+    assert co[4] == 0.0
+    sa, sap, dirc, r = (torch.tensor(np.float32(co[k])) for k in (0, 2, 3, 5))  # the row's own values, as the kernel reads them
+    nan = torch.full((B, C, H, W), float("nan"))
+    for cfg, gs in ((False, 1.0), (True, 3.0)):
+        e_t = e_u + gs * (e_c - e_u) if cfg else e_c
+        eh = torch.cat([e_u, e_c], 0) if cfg else e_c
+        pred_x0 = (xt - r * e_t) / sa
+        want = sap * pred_x0 + dirc * e_t
+        got, _ = _ops.sched_step(engine, 2, 0, co, xt=xt, eps_hat=eh, cfg=cfg, g=gs, eps_in=nan, noise=None)
+        assert not torch.isnan(got).any()
+        assert torch.equal(got, want), (got - want).abs().max()
+
+
+def test_sched_steps_ddpm_posterior_bit_exact(engine):
+    """sched_kind = 1, the pixel 'ddpm' posterior forms (ddpm_ddim_wrapper.py:291-298, 264-269, 202-210) in the slot meaning
+    documented above k_encode_step_ddpm: x_next = sa*x0 + s1a*x_t + sap*n, mean = r*(x_t - dirc*e),
+    eps = (x_next - mean)/sigma; decode x = mean + t_mask*sigma*eps. Rows of a 20-step PixelSchedule: a middle one and the
+    t = 0 row, whose t_mask is 0."""
+    from cycle_diffusion_amd import schedule
+    g = torch.Generator().manual_seed(37)
+    B, C, H, W = 2, 3, 16, 16
+    x0, xt, e, nz, eps = [torch.randn(B, C, H, W, generator=g) for _ in range(5)]
+    sch = schedule.PixelSchedule(20, 20, sample_type="ddpm", eta=None)
+    ce, cd = sch.coef_encode(), sch.coef_decode()
+    assert sch.kind == 1 and cd[0]["t_mask"] == 0.0 and cd[10]["t_mask"] == 1.0 and ce[9]["t_mask"] == 1.0
+    for row in (ce[9], cd[10], cd[0]):
+        sa, s1a, sap, dirc, sigma, r, t_mask = (torch.tensor(np.float32(row[k])) for k in
+                                                ("sa", "s1a", "sap", "dirc", "sigma", "r", "t_mask"))
+        mean = r * (xt - dirc * e)
+        # encode: x and z
+        x_next = sa * x0 + s1a * xt + sap * nz
+        ref_eps = (x_next - mean) / sigma
+        got_xn, got_eps = _ops.sched_step(engine, 1, 1, tuple(row), x0=x0, xt=xt, eps_hat=e, noise=nz)
+        assert torch.equal(got_xn, x_next), (got_xn - x_next).abs().max()
+        assert torch.equal(got_eps, ref_eps), (got_eps - ref_eps).abs().max()
+        # decode with injected eps, and with a drawn one
+        for kw in (dict(eps_in=eps), dict(noise=eps)):
+            x_prev = mean + t_mask * sigma * eps
+            got_xp, _ = _ops.sched_step(engine, 2, 1, tuple(row), xt=xt, eps_hat=e, **kw)
+            assert torch.equal(got_xp, x_prev), (got_xp - x_prev).abs().max()
+    assert torch.equal(_ops.sched_step(engine, 2, 1, tuple(cd[0]), xt=xt, eps_hat=e, eps_in=eps)[0],
+                       torch.tensor(np.float32(cd[0]["r"])) * (xt - torch.tensor(np.float32(cd[0]["dirc"])) * e))
 
 
 def test_sustained_mfma_rate_diagnostic_is_consistent(engine):
