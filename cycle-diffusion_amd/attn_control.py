@@ -1,0 +1,100 @@
+"""Host side of the cross-attention control (prompt-to-prompt, Hertz et al. 2022, on the coupled translate loop).
+
+build_control() turns the token ids of a source and a target prompt into what cd_cycle_translate_ctrl consumes:
+    M [B, L, L]   mapper: (P_src . M)[j] = sum_i P_src[i] M[i, j] - the source attention map seen from target position j
+    alpha [B, L]  1 where target position j takes the mapped source map, 0 where it keeps its own
+    w [B, L]      re-weighting of target position j (1 = unchanged)
+It works on id arrays, not on strings: any tokenizer that pads to a fixed length and marks the end of the prompt with one id
+will do (the CLIP BPE, the BERT WordPiece and the hash stand-ins of gan_wrapper/text_encoders.py).
+
+The alignment is the global (Needleman-Wunsch) alignment of prompt-to-prompt's seq_aligner: match +1, gap 0, mismatch -1,
+ties resolved in its order (gap in the source, gap in the target, diagonal). With these scores a substituted token never
+aligns diagonally (two gaps score 0 > -1): it shows up as one source token left out and one target token inserted.
+"""
+import numpy as np
+
+CLIP_EOS = 49407
+MODES = ("refine", "replace")
+
+
+def prompt_length(ids, eos_id):
+    """index of the end token of one padded id row (its last position when the row has none)"""
+    hit = np.nonzero(np.asarray(ids) == eos_id)[0]
+    return int(hit[0]) if len(hit) else len(ids) - 1
+
+
+def align(src, tgt):
+    """Needleman-Wunsch (match 1, gap 0, mismatch -1) -> for every target token the index of the source token it is aligned
+    with, or -1 for an inserted one. Aligned pairs are not necessarily equal tokens in general; with these scores they are."""
+    n, m = len(src), len(tgt)
+    score = np.zeros((n + 1, m + 1), dtype=np.int64)
+    trace = np.zeros((n + 1, m + 1), dtype=np.int8)
+    trace[0, 1:] = 1
+    trace[1:, 0] = 2
+    for i in range(1, n + 1):
+        for j in range(1, m + 1):
+            left, up = score[i, j - 1], score[i - 1, j]
+            diag = score[i - 1, j - 1] + (1 if src[i - 1] == tgt[j - 1] else -1)
+            best = max(left, up, diag)
+            score[i, j] = best
+            trace[i, j] = 1 if best == left else (2 if best == up else 3)
+    out = [-1] * m
+    i, j = n, m
+    while i > 0 or j > 0:
+        if trace[i, j] == 3:
+            i, j = i - 1, j - 1
+            out[j] = i
+        elif trace[i, j] == 1:
+            j -= 1
+        else:
+            i -= 1
+    return out
+
+
+def build_control(src_ids, tgt_ids, mode="refine", reweight=None, eos_id=CLIP_EOS):
+    """src_ids, tgt_ids: integer arrays [B, L] (start token, prompt, end token, padding). Returns float32 (M [B, L, L],
+    alpha [B, L], w [B, L]).
+      refine   a target token aligned with an EQUAL source token takes that token's map (M[i, j] = 1, alpha_j = 1); inserted and
+               substituted tokens keep their own attention (alpha_j = 0, column j of M empty)
+      replace  the prompts must have the same number of tokens; every position takes the source map of the same position,
+               substituted ones included (alpha_j = 1)
+    In both modes the start token maps to the start token, and the positions from the target's end token onward map in order
+    to the source positions from the source's end token onward (clipped to L - 1), alpha = 1.
+    reweight: {key: scale}; a key below L is a target position, any other key a token id (every occurrence ahead of the
+    target's end token); w is 1 elsewhere."""
+    if mode not in MODES:
+        raise ValueError("mode must be one of %s" % (MODES,))
+    src_ids, tgt_ids = np.asarray(src_ids), np.asarray(tgt_ids)
+    if src_ids.ndim != 2 or src_ids.shape != tgt_ids.shape:
+        raise ValueError("src_ids and tgt_ids must both be [B, L], got %s and %s" % (src_ids.shape, tgt_ids.shape))
+    B, L = src_ids.shape
+    M = np.zeros((B, L, L), dtype=np.float32)
+    alpha = np.zeros((B, L), dtype=np.float32)
+    w = np.ones((B, L), dtype=np.float32)
+    for b in range(B):
+        s, t = src_ids[b], tgt_ids[b]
+        ns, nt = prompt_length(s, eos_id), prompt_length(t, eos_id)
+        M[b, 0, 0] = 1.0
+        alpha[b, 0] = 1.0
+        if mode == "replace":
+            if ns != nt:
+                raise ValueError("mode = 'replace' needs prompts of the same number of tokens (sample %d: %d against %d); "
+                                 "use mode = 'refine'" % (b, ns - 1, nt - 1))
+            for j in range(1, nt):
+                M[b, j, j] = 1.0
+                alpha[b, j] = 1.0
+        else:
+            for jj, ii in enumerate(align(list(s[1:ns]), list(t[1:nt]))):
+                if ii >= 0 and s[1 + ii] == t[1 + jj]:
+                    M[b, 1 + ii, 1 + jj] = 1.0
+                    alpha[b, 1 + jj] = 1.0
+        for k in range(L - nt):
+            M[b, min(ns + k, L - 1), nt + k] = 1.0
+            alpha[b, nt + k] = 1.0
+        for key, scale in (reweight or {}).items():
+            key = int(key)
+            if 0 <= key < L:
+                w[b, key] = float(scale)
+            else:
+                w[b, 1:nt][t[1:nt] == key] = float(scale)
+    return M, alpha, w

@@ -617,7 +617,210 @@ __global__ __launch_bounds__(256) void k_transpose_v(const bf16_t* __restrict__ 
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Cross-attention control: O = softmax(Q_src K_src^T) V_a + softmax(Q_own K_own^T) V_b for the decoder's
+// conditional rows of the coupled loop, the source operands taken from encoder row b % B_src of the same forward.
+// The context is short (77 keys), so ALL keys of both sources are resident: K_src, K_own [96][DQK] and V_a, V_b [96][VS]
+// (token-major, read through the LDS transpose reads of k_attention's VTOK form) are staged once, one barrier, and each
+// source is a plain two-pass softmax in registers: 96 scores per query in three accumulator blocks, maximum, exp2, sum,
+// normalise, pack, PV. Keys L .. 95 are masked to -inf ahead of the maximum (probability exactly 0) and their LDS rows
+// are zeros, whatever follows the caller's tensors. Both PV products accumulate into one fp32 accumulator: the
+// probabilities are therefore normalised BEFORE the product (to 2^8 / l, the range pack2_prob converts exactly as
+// k_attention's deferred maximum uses it; the epilogue takes the 2^-8 back). Same fragment layouts as k_attention.
+template <int DQK, int DV>
+__global__ __launch_bounds__(256, DV <= 96 ? 2 : 1) void k_cross_attention_ctrl(CtrlAttnParams p) {
+  constexpr int NT = 256, CK = kCtrlKeys, NG = CK / 32;
+  constexpr int KLD = DQK + 8, NKS = DQK / 16, NDT = DV / 32, CPR = DQK / 8;
+  constexpr int VS = DV <= 32 ? 32 : (DV <= 96 ? 96 : 160), CPV = VS / 8;
+  __shared__ __attribute__((aligned(16))) bf16_t Ks[2][CK * KLD];
+  __shared__ __attribute__((aligned(16))) bf16_t Vs[2][CK * VS];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qi = lane & 31, half = lane >> 5;
+  const int h = blockIdx.y, b = blockIdx.z, bs = b % p.B_src;
+  const int q0 = blockIdx.x * 128 + wave * 32;
+  const int D = p.D, L = p.L;
+
+  // ---- stage K_src | K_own and V_a | V_b of this head: rows >= L and columns >= D are zeros
+#pragma unroll
+  for (int src = 0; src < 2; ++src) {
+    const bf16_t* kb = (src == 0 ? p.k_src + (int64_t)bs * p.k_bs : p.k_own + (int64_t)b * p.k_bs) + h * D;
+    const bf16_t* vb = (src == 0 ? p.va : p.vb) + (int64_t)b * p.v_bs + h * D;
+    for (int id = tid; id < CK * CPR; id += NT) {
+      const int row = id / CPR, ch = id % CPR;
+      uint4 raw = make_uint4(0, 0, 0, 0);
+      if (row < L && ch * 8 < D) raw = *(const uint4*)(kb + (int64_t)row * p.ldk + ch * 8);
+      *(uint4*)(&Ks[src][row * KLD + ch * 8]) = raw;
+    }
+    for (int id = tid; id < CK * CPV; id += NT) {
+      const int row = id / CPV, ch = id % CPV;
+      uint4 raw = make_uint4(0, 0, 0, 0);
+      if (row < L && ch * 8 < D) raw = *(const uint4*)(vb + (int64_t)row * p.ldv + ch * 8);
+      *(uint4*)(&Vs[src][row * VS + ch * 8]) = raw;
+    }
+  }
+  __syncthreads();
+
+  const int vtr_off = ((4 * half + ((lane & 15) >> 2)) * VS + 16 * ((lane >> 4) & 1) + 4 * (lane & 3));
+  const float qsc = p.scale * 1.44269504088896340736f;
+  f32x16 o[NDT];
+#pragma unroll
+  for (int i = 0; i < NDT; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
+
+#pragma unroll
+  for (int src = 0; src < 2; ++src) {
+    // Q fragments (B operand of S^T = K Q^T): lane holds Q[q][ks*16 + 8*half .. +7], in log2 score units
+    const bf16_t* qb = (src == 0 ? p.q_src + (int64_t)bs * p.q_bs : p.q_own + (int64_t)b * p.q_bs) + h * D;
+    bf16x8 qf[NKS];
+    {
+      const int q = q0 + qi;
+#pragma unroll
+      for (int ks = 0; ks < NKS; ++ks) {
+        const int d0 = ks * 16 + 8 * half;
+        uint4 raw = make_uint4(0, 0, 0, 0);
+        if (q < p.Tq && d0 < D) raw = *(const uint4*)(qb + (int64_t)q * p.ldq + d0);
+        if (!p.q_log2) {
+          float f[8];
+          unpack8(raw, f);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) f[e] *= qsc;
+          raw = pack8(f);
+        }
+        qf[ks] = *(bf16x8*)&raw;
+      }
+    }
+    const bf16_t* Kt = Ks[src];
+    const bf16_t* Vt = Vs[src];
+    // ---- S^T = K Q^T over all 96 keys
+    f32x16 s[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[g][r] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < NKS; ++ks) {
+        const bf16x8 kf = *(const bf16x8*)(Kt + (g * 32 + qi) * KLD + ks * 16 + 8 * half);
+        s[g] = CD_MFMA_32x32x16(kf, qf[ks], s[g]);
+      }
+    }
+    // ---- pass 1: keys beyond L out, maximum of the query (a lane holds 48 of its 96 scores, lane ^ 32 the others)
+    float mx = -INFINITY;
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = g * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        s[g][r] = key < L ? s[g][r] : -INFINITY;
+        mx = fmaxf(mx, s[g][r]);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    // ---- pass 2: exp2(s - max) (<= 1, a masked key gives exactly 0), row sum, normalise to 2^8 / l
+    float ps = 0.f;
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        s[g][r] = __builtin_amdgcn_exp2f(s[g][r] - mx);
+        ps += s[g][r];
+      }
+    ps += __shfl_xor(ps, 32);
+    const float inv = 256.0f / ps;  // ps >= 1: the maximum's own term
+    // ---- O^T += V^T P^T
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      uint32_t pw[8];
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) pw[r >> 1] = pack2_prob(s[g][r] * inv, s[g][r + 1] * inv);
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        const uint4 praw = make_uint4(pw[4 * s2], pw[4 * s2 + 1], pw[4 * s2 + 2], pw[4 * s2 + 3]);
+        const bf16x8 pf = __builtin_bit_cast(bf16x8, praw);
+        const int k16 = g * 32 + 16 * s2;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) {
+          typedef __attribute__((address_space(3))) bf16x4* lds4_t;
+          const bf16_t* vr = Vt + vtr_off + k16 * VS + dt * 32;
+          const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)vr);
+          const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t)(vr + 8 * VS));
+          const bf16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+          o[dt] = CD_MFMA_32x32x16(vf, pf, o[dt]);
+        }
+      }
+    }
+  }
+
+  // ---- store: lane owns query q0+qi and 4 consecutive d per register quad
+  const int q = q0 + qi;
+  if (q < p.Tq) {
+    constexpr float kUnscale = 1.0f / 256.0f;
+    bf16_t* ob = p.o + (int64_t)b * p.o_bs + (int64_t)q * p.ldo + h * D;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        const int d0 = dt * 32 + 8 * rq + 4 * half;
+        if (d0 < D) {
+          uint2 pk;
+          pk.x = pack2(o[dt][rq * 4 + 0] * kUnscale, o[dt][rq * 4 + 1] * kUnscale);
+          pk.y = pack2(o[dt][rq * 4 + 2] * kUnscale, o[dt][rq * 4 + 3] * kUnscale);
+          *(uint2*)(ob + d0) = pk;
+        }
+      }
+  }
+}
+
+// the step-invariant value tensors of the control: grid (L, rows), threads over the channels
+__global__ __launch_bounds__(256) void k_ctrl_values(const bf16_t* __restrict__ v, const float* __restrict__ M,
+                                                     const float* __restrict__ alpha, const float* __restrict__ w, int B_ctrl,
+                                                     int L, int C, bf16_t* __restrict__ va, bf16_t* __restrict__ vb) {
+  const int i = blockIdx.x, r = blockIdx.y, s = r % B_ctrl;
+  const float* Mi = M + ((int64_t)s * L + i) * L;
+  const float* al = alpha + (int64_t)s * L;
+  const float* ww = w + (int64_t)s * L;
+  const bf16_t* vr = v + (int64_t)r * L * C;
+  const float bi = (1.0f - al[i]) * ww[i];
+  for (int c = threadIdx.x; c < C; c += 256) {
+    float acc = 0.f;
+    for (int j = 0; j < L; ++j) {
+      const float m = Mi[j] * al[j] * ww[j];
+      if (m != 0.f) acc = fmaf(m, bf2f(vr[(int64_t)j * C + c]), acc);
+    }
+    va[((int64_t)r * L + i) * C + c] = f2bf(acc);
+    vb[((int64_t)r * L + i) * C + c] = f2bf(bi * bf2f(vr[(int64_t)i * C + c]));
+  }
+}
+
 }  // namespace
+
+void launch_cross_attention_ctrl(hipStream_t st, const CtrlAttnParams& p) {
+  CD_CHECK(p.B > 0 && p.B_src > 0 && p.H > 0 && p.Tq > 0, "cross-attention control: empty launch");
+  CD_CHECK(p.L > 0 && p.L <= kCtrlKeys, "cross-attention control: context length %d above the %d keys the kernel keeps resident",
+           p.L, kCtrlKeys);
+  CD_CHECK((p.ldq % 8) == 0 && (p.ldk % 8) == 0 && (p.ldv % 8) == 0 && (p.ldo % 4) == 0 && (p.q_bs % 8) == 0 &&
+               (p.k_bs % 8) == 0 && (p.v_bs % 8) == 0 && (p.o_bs % 4) == 0,
+           "cross-attention control: leading dims");
+  CD_CHECK((((uintptr_t)p.q_own | (uintptr_t)p.q_src | (uintptr_t)p.k_own | (uintptr_t)p.k_src | (uintptr_t)p.va |
+             (uintptr_t)p.vb) & 15) == 0 && ((uintptr_t)p.o & 7) == 0, "cross-attention control: pointer alignment");
+  const dim3 grid(ceil_div(p.Tq, 128), p.H, p.B);
+#define CD_CTRL(DQK, DV) hipLaunchKernelGGL((k_cross_attention_ctrl<DQK, DV>), grid, dim3(256), 0, st, p)
+  switch (p.D) {
+    case 32: CD_CTRL(32, 32); break;
+    case 40: CD_CTRL(48, 64); break;
+    case 64: CD_CTRL(64, 64); break;
+    case 80: CD_CTRL(80, 96); break;
+    case 160: CD_CTRL(160, 160); break;
+    default: CD_CHECK(false, "cross-attention control: head dim %d unsupported (32, 40, 64, 80, 160)", p.D);
+  }
+#undef CD_CTRL
+}
+
+void launch_ctrl_values(hipStream_t st, const bf16_t* v, const float* M, const float* alpha, const float* w, int rows,
+                        int B_ctrl, int L, int C, bf16_t* va, bf16_t* vb) {
+  CD_CHECK(rows > 0 && B_ctrl > 0 && L > 0 && C > 0, "control values: empty launch");
+  hipLaunchKernelGGL(k_ctrl_values, dim3(L, rows), dim3(256), 0, st, v, M, alpha, w, B_ctrl, L, C, va, vb);
+}
 
 void launch_attention(hipStream_t st, const AttnParams& p) {
   CD_CHECK(p.D % 8 == 0 && p.D <= 160, "attention: head dim %d unsupported by the fused kernel", p.D);

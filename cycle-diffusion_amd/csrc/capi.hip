@@ -413,6 +413,14 @@ MaskBlend mask_blend_of(const MaskArgs& m, const float2* qtab, int k, int slot, 
   return b;
 }
 
+// Arguments of the cross-attention control (cd_cycle_translate_ctrl), checked on the host before any launch
+struct CtrlArgs {
+  const float* mapper = nullptr;  // [B_ctrl, L, L]
+  const float* alpha = nullptr;   // [B_ctrl, L]
+  const float* weight = nullptr;  // [B_ctrl, L]
+  int B_ctrl = 0, n_ctrl = 0;
+};
+
 struct SamplerState {
   UNet* u = nullptr;
   int B = 0, Bn = 0, C = 0, HW = 0, cpad = 0, out_ld = 0;
@@ -762,17 +770,41 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
                        const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
                        float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
                        const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                       uint64_t seed, int last_uses_x0, float* z_out, float* x_out, const MaskArgs* mk) {
+                       uint64_t seed, int last_uses_x0, float* z_out, float* x_out, const MaskArgs* mk,
+                       const CtrlArgs* ck = nullptr) {
   CD_CHECK(h && x0 && coef_enc_host && coef_dec_host && z_out && x_out && B > 0 && n_dec > 0 && K > 0, "bad argument");
   ArenaScope arena_scope(h->arena);
   UNet* u = get_unet(h, net);
   const int Bd = B * n_dec;
   if (mk) check_mask_args(*mk, u, sched_kind, B, /*coupled=*/true);
+  const bool ctrl_on = ck && ck->n_ctrl != 0;
+  if (ck) {
+    // one forward serves both passes at the timestep of the DECODER's row k: the two tables must agree on it
+    for (int k = 0; k < K; ++k)
+      CD_CHECK(coef_enc_host[k].t == coef_dec_host[k].t, "cd_cycle_translate_ctrl: the encoder's and the decoder's tables disagree "
+               "on the timestep of row %d (%d against %d)", k, coef_enc_host[k].t, coef_dec_host[k].t);
+  }
+  if (ctrl_on) {
+    CD_CHECK(ck->n_ctrl > 0 && ck->n_ctrl <= K, "cross-attention control: n_ctrl = %d outside [0, K = %d]", ck->n_ctrl, K);
+    CD_CHECK(sched_kind == CD_SCHED_DDIM, "cross-attention control is only defined for sched_kind = CD_SCHED_DDIM");
+    CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer && (enc_ctx_c || enc_ctx_uc),
+             "cross-attention control needs a network with a text context (and the contexts of both passes)");
+    CD_CHECK(!u->f32, "cross-attention control is not built for fp32 / fp32x3 networks (their transformer blocks run the fp32 "
+                      "attention of st_f32.hip): use the 16-bit precision");
+    CD_CHECK(ctx_len <= kCtrlKeys, "cross-attention control: context length %d above the %d keys the kernel keeps resident",
+             ctx_len, kCtrlKeys);
+    CD_CHECK(ck->mapper && ck->alpha && ck->weight, "cross-attention control: mapper / alpha / weight is NULL");
+    CD_CHECK(ck->B_ctrl > 0 && B % ck->B_ctrl == 0, "cross-attention control shape mismatch: %d control rows for a batch of %d",
+             ck->B_ctrl, B);
+  }
   const int C = u->desc.in_channels, HW = u->image_size * u->image_size, cpad = u->in_cpad, out_ld = u->out_channels;
   const bool f32 = u->f32;
   Guidance ge = resolve_guidance(enc_ctx_c, enc_ctx_uc, enc_guidance);
   Guidance gd = resolve_guidance(dec_ctx_c, dec_ctx_uc, dec_guidance_per_sample ? 2.0f : dec_guidance);
   if (dec_guidance_per_sample) CD_CHECK(gd.cfg, "per-sample guidance needs the classifier-free-guidance batch (both contexts)");
+  if (ctrl_on)
+    CD_CHECK((ge.cfg || (enc_ctx_c && ge.ctx_single == enc_ctx_c)) && (gd.cfg || (dec_ctx_c && gd.ctx_single == dec_ctx_c)),
+             "cross-attention control needs conditional rows in both passes (a guidance scale of 0 runs none)");
   CD_CHECK(sched_kind == CD_SCHED_DDIM || (!ge.cfg && !gd.cfg), "classifier-free guidance is only implemented for sched_kind = CD_SCHED_DDIM");
   const bool has_ctx = enc_ctx_c || enc_ctx_uc;
   CD_CHECK(has_ctx == (dec_ctx_c || dec_ctx_uc), "cd_cycle_translate: contexts for both passes or for neither");
@@ -793,6 +825,14 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     u->set_context(c, (const bf16_t*)cx, Bn, ctx_len);
   } else {
     CD_CHECK(u->desc.context_dim <= 0 || !u->desc.use_spatial_transformer, "network expects a cross-attention context");
+  }
+  // the controlled rows are the decoder's conditional rows - the tail of the batch in either layout - and their source the
+  // encoder's conditional row of the same sample: V_a / V_b of every block once per call, next to the cached keys and values
+  AttnCtrl actl;
+  if (ctrl_on) {
+    actl.row0 = Bn - Bd; actl.rows = Bd;
+    actl.src_b0 = ge.cfg ? B : 0; actl.B_src = B;
+    u->build_attn_control(c, ck->mapper, ck->alpha, ck->weight, ck->B_ctrl, actl);
   }
   const size_t esz = f32 ? 4 : 2;
   const int64_t chw = (int64_t)C * HW, n = (int64_t)B * chw;
@@ -852,6 +892,7 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     UNetIO io;
     io.xin = (const bf16_t*)xin; io.B = Bn; io.tab = tab_d; io.step = k; io.t_shared = true;  // rows k of both tables carry the same t
     io.dup_tail = dup_tail;
+    io.ctrl = (ctrl_on && i < ck->n_ctrl) ? &actl : nullptr;
     io.out = eh; io.out_ld = out_ld;
     u->forward(c, io);
     const int is_last = (last_uses_x0 && k == 0) ? 1 : 0;
@@ -903,6 +944,28 @@ int cd_cycle_translate_masked(cd_handle h, int net, int sched_kind, const float*
   cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
                        dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
                        z_out, x_out, &mk);
+  CD_API_END
+}
+
+// The coupled loop with cross-attention control on its first n_ctrl iterations, with or without a keep-mask.
+int cd_cycle_translate_ctrl(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
+                            const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
+                            float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
+                            const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
+                            uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
+                            int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
+                            const float* mapper, const float* alpha, const float* weight, int B_ctrl, int n_ctrl,
+                            float* z_out, float* x_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  MaskArgs mk;
+  mk.mask = mask; mk.x0 = mask_x0; mk.B_mask = B_mask; mk.source = mask_source; mk.qcoef_host = qsample_coef_host;
+  mk.noise = mask_noise; mk.seed = mask_seed;
+  CtrlArgs ck;
+  ck.mapper = mapper; ck.alpha = alpha; ck.weight = weight; ck.B_ctrl = B_ctrl; ck.n_ctrl = n_ctrl;
+  cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
+                       dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
+                       z_out, x_out, mask ? &mk : nullptr, &ck);
   CD_API_END
 }
 
@@ -1105,6 +1168,38 @@ int cd_op_attention(cd_handle h, const float* q, const float* k, const float* v,
     p.v = vb; p.ldv = C; p.v_bs = (int64_t)Tk * C;
   }
   launch_attention(h->st, p);
+  launch_nhwc_to_nchw(h->st, ob, 0, C, o, B * Tq, C, 1, 1.f, 0.f);
+  CD_API_END
+}
+
+int cd_op_cross_attention_ctrl(cd_handle h, const float* q_own, const float* q_src, const float* k_own, const float* k_src,
+                               const float* v_own, const float* mapper, const float* alpha, const float* weight, int B,
+                               int B_src, int B_ctrl, int H, int Tq, int L, int L_buf, int D, float scale, float* o) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && q_own && q_src && k_own && k_src && v_own && mapper && alpha && weight && o, "bad argument");
+  CD_CHECK(B > 0 && B_src > 0 && B_ctrl > 0 && H > 0 && Tq > 0 && D > 0 && L > 0 && L_buf >= L, "bad argument");
+  ArenaScope arena_scope(h->arena);
+  const int C = H * D;
+  auto to16 = [&](const float* src, int64_t rows) {
+    bf16_t* d = (bf16_t*)h->arena.alloc((size_t)rows * C * 2);
+    launch_nchw_to_nhwc(h->st, src, d, (int)rows, C, 1, C, 1.f, 0.f, 0);
+    return d;
+  };
+  CtrlAttnParams p;
+  p.q_own = to16(q_own, (int64_t)B * Tq); p.q_src = to16(q_src, (int64_t)B_src * Tq);
+  p.k_own = to16(k_own, (int64_t)B * L_buf); p.k_src = to16(k_src, (int64_t)B_src * L_buf);
+  const bf16_t* vb16 = to16(v_own, (int64_t)B * L);
+  bf16_t* va = (bf16_t*)h->arena.alloc((size_t)B * L * C * 2);
+  bf16_t* vb = (bf16_t*)h->arena.alloc((size_t)B * L * C * 2);
+  launch_ctrl_values(h->st, vb16, mapper, alpha, weight, B, B_ctrl, L, C, va, vb);
+  bf16_t* ob = (bf16_t*)h->arena.alloc((size_t)B * Tq * C * 2);
+  p.va = va; p.vb = vb; p.o = ob;
+  p.B = B; p.B_src = B_src; p.H = H; p.Tq = Tq; p.L = L; p.D = D;
+  p.ldq = C; p.ldk = C; p.ldv = C; p.ldo = C;
+  p.q_bs = (int64_t)Tq * C; p.k_bs = (int64_t)L_buf * C; p.v_bs = (int64_t)L * C; p.o_bs = (int64_t)Tq * C;
+  p.scale = scale;
+  launch_cross_attention_ctrl(h->st, p);
   launch_nhwc_to_nchw(h->st, ob, 0, C, o, B * Tq, C, 1, 1.f, 0.f);
   CD_API_END
 }

@@ -215,6 +215,15 @@ struct TimeEmb {  // shared by all U-Nets: sinusoid -> MLP -> per-ResBlock proje
   int proj_total = 0;
 };
 
+// Cross-attention control of one forward (UNet::build_attn_control fills it once per call): rows
+// [row0, row0 + rows) of the batch - always its tail - run k_cross_attention_ctrl in every text cross-attention, with the
+// to_q output and the cached keys of row src_b0 + (r - row0) % B_src as the source; every other row runs k_attention.
+struct AttnCtrl {
+  std::vector<const bf16_t*> va, vb;  // per transformer block, [rows][L][C] (stored like the cached context values)
+  int row0 = 0, rows = 0;
+  int src_b0 = 0, B_src = 0;
+};
+
 struct UNetIO {
   const bf16_t* xin = nullptr;   // NHWC bf16 [B][H][W][Cpad_in]
   int B = 0;
@@ -230,6 +239,7 @@ struct UNetIO {
   // dup_tail rows that repeat the dup_tail rows just ahead of them], e.g. [encoder rows | decoder uncond | decoder cond]
   // with dup_tail = the decoder's sample count. cfg_dup is the case dup_tail = B / 2. 0 = no repeated rows.
   int dup_tail = 0;
+  const AttnCtrl* ctrl = nullptr;     // cross-attention control of this forward, or null (16-bit path only)
   float* out = nullptr;               // fp32 [B*H*W][out_ld]
   int out_ld = 0;
 };
@@ -239,6 +249,12 @@ class UNet : public Net {
   virtual void forward(Ctx& c, const UNetIO& io) = 0;
   // cross-attention K / V^T of the context are step-invariant: computed once per call
   virtual void set_context(Ctx& c, const bf16_t* ctx, int B, int L) { (void)c; (void)ctx; (void)B; (void)L; }
+  // after set_context: V_a / V_b of every transformer block for rows [ctrl.row0, ctrl.row0 + ctrl.rows) of that context, from
+  // the device tensors mapper [B_ctrl][L][L], alpha / weight [B_ctrl][L] (row r uses entry (r - row0) % B_ctrl); fills
+  // ctrl.va / ctrl.vb, allocated from the arena (they live as long as the caller's arena scope).
+  virtual void build_attn_control(Ctx&, const float*, const float*, const float*, int, AttnCtrl&) {
+    CD_CHECK(false, "cross-attention control: the network has no text cross-attention");
+  }
   int in_cpad = 32;
   int out_channels = 0;
   int image_size = 0;

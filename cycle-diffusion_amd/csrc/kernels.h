@@ -297,6 +297,30 @@ struct AttnParams {
   int causal = 0;                // 1: key j is visible to query i only if j <= i (CLIP text transformer)
 };
 void launch_attention(hipStream_t st, const AttnParams& p);
+// Cross-attention control (prompt-to-prompt on the coupled loop): controlled row b takes
+//   O = softmax(Q_src K_src^T) V_a + softmax(Q_own K_own^T) V_b
+// with the source tensors of row src = b % B_src. V_a / V_b carry the mapper, alpha and the re-weighting
+// (launch_ctrl_values); neither softmax is renormalised afterwards.
+constexpr int kCtrlKeys = 96;  // keys resident in LDS per source: the context length may not exceed it
+struct CtrlAttnParams {
+  const bf16_t* q_own = nullptr;  // [B][Tq][ldq], head h at column h*D
+  const bf16_t* q_src = nullptr;  // [B_src][Tq][ldq]
+  const bf16_t* k_own = nullptr;  // [B][L][ldk]
+  const bf16_t* k_src = nullptr;  // [B_src][L][ldk]
+  const bf16_t* va = nullptr;     // [B][L][ldv] token-major
+  const bf16_t* vb = nullptr;     // [B][L][ldv]
+  bf16_t* o = nullptr;            // [B][Tq][ldo]
+  int B = 0, B_src = 0, H = 0, Tq = 0, L = 0, D = 0;
+  int ldq = 0, ldk = 0, ldv = 0, ldo = 0;
+  int64_t q_bs = 0, k_bs = 0, v_bs = 0, o_bs = 0;
+  float scale = 1.0f;  // softmax scale; ignored when q_log2 is set
+  int q_log2 = 0;
+};
+void launch_cross_attention_ctrl(hipStream_t st, const CtrlAttnParams& p);
+// V_a[r][i][:] = sum_j M[s][i][j] alpha[s][j] w[s][j] V[r][j][:], V_b[r][j][:] = (1 - alpha[s][j]) w[s][j] V[r][j][:] with
+// s = r % B_ctrl; fp32 accumulation, one rounding. v / va / vb [rows][L][C] dense; M [B_ctrl][L][L], alpha / w [B_ctrl][L] fp32
+void launch_ctrl_values(hipStream_t st, const bf16_t* v, const float* M, const float* alpha, const float* w, int rows,
+                        int B_ctrl, int L, int C, bf16_t* va, bf16_t* vb);
 // V [B][Tk][ldv] (head h at column h*D) -> Vt [B][H][Dpad][Tpad], zero padded
 void launch_transpose_v(hipStream_t st, const bf16_t* v, int ldv, int64_t v_bs, bf16_t* vt, int B,
                         int H, int Tk, int D, int Dpad, int Tpad);

@@ -61,6 +61,8 @@ class UNetOpenAI : public UNet {
   int kind() const override { return CD_NET_UNET_OPENAI; }
   void forward(Ctx& c, const UNetIO& io) override;
   void set_context(Ctx& c, const bf16_t* ctx, int B, int L) override;
+  void build_attn_control(Ctx& c, const float* mapper, const float* alpha, const float* weight, int B_ctrl,
+                          AttnCtrl& ctrl) override;
   size_t workspace_hint(int B) const override;
 
  private:
@@ -75,6 +77,7 @@ class UNetOpenAI : public UNet {
   ConvW* out_conv_ = nullptr;
   int ctx_B_ = 0, ctx_L_ = 0;
   std::vector<void*> ctx_allocs_;
+  const AttnCtrl* ctrl_ = nullptr;  // the control of the running forward (UNetIO::ctrl), else null
 
   int add_res(const std::string& pfx, int cin, int cout, bool up, bool down);
   int add_st(const std::string& pfx, int C, int heads, int dh);
@@ -400,6 +403,28 @@ void UNetOpenAI::set_context(Ctx& c, const bf16_t* ctx, int B, int L) {
   c.f32 = keep_f32; c.x3 = keep_x3;
 }
 
+void UNetOpenAI::build_attn_control(Ctx& c, const float* mapper, const float* alpha, const float* weight, int B_ctrl,
+                                    AttnCtrl& ctrl) {
+  CD_CHECK(!st_.empty() && st_[0].k2c, "cross-attention control: the network has no cross-attention context set");
+  CD_CHECK(!f32, "cross-attention control is not built for fp32 / fp32x3 networks (their transformer blocks run the fp32 "
+                 "attention of st_f32.hip): use the 16-bit precision");
+  CD_CHECK(ctx_L_ <= kCtrlKeys, "cross-attention control: context length %d above the %d keys the kernel keeps resident",
+           ctx_L_, kCtrlKeys);
+  CD_CHECK(ctrl.rows > 0 && ctrl.row0 >= 0 && ctrl.row0 + ctrl.rows == ctx_B_, "cross-attention control: rows %d + %d of a "
+           "batch of %d (the controlled rows are the tail of the batch)", ctrl.row0, ctrl.rows, ctx_B_);
+  CD_CHECK(ctrl.B_src > 0 && ctrl.src_b0 >= 0 && ctrl.src_b0 + ctrl.B_src <= ctrl.row0, "cross-attention control: source rows");
+  CD_CHECK(mapper && alpha && weight && B_ctrl > 0, "cross-attention control: mapper / alpha / weight");
+  ctrl.va.clear(); ctrl.vb.clear();
+  for (auto& s : st_) {
+    const size_t bytes = (size_t)ctrl.rows * ctx_L_ * s.C * 2;
+    bf16_t* va = (bf16_t*)c.arena->alloc(bytes);
+    bf16_t* vb = (bf16_t*)c.arena->alloc(bytes);
+    launch_ctrl_values(c.st, s.v2c + (int64_t)ctrl.row0 * ctx_L_ * s.C, mapper, alpha, weight, ctrl.rows, B_ctrl, ctx_L_, s.C,
+                       va, vb);
+    ctrl.va.push_back(va); ctrl.vb.push_back(vb);
+  }
+}
+
 // rows [0, n) of src -> rows [0, n) of dst, and its last `tail` rows again -> rows [n, n + tail) (dense, `cols` 16-bit
 // elements per row)
 static void dup_rows(Ctx& c, const bf16_t* src, bf16_t* dst, int64_t n, int64_t tail, int cols) {
@@ -500,7 +525,7 @@ Act UNetOpenAI::st_fwd(Ctx& c, STW& s, const Act& x_in, int dup_tail) {
   // (DESIGN.md 8). Chunks of 16 images are 65 536 rows: 256 strips / row tiles, one full round of the chip per kernel.
   static const int st_chunk = [] { const char* e = getenv("CYCLEDIFF_ST_CHUNK"); return e ? atoi(e) : 0; }();
   c.arena->release(mk);
-  if (!dup && st_chunk > 0 && T >= 4096 && B >= 2 * st_chunk) {
+  if (!dup && !ctrl_ && st_chunk > 0 && T >= 4096 && B >= 2 * st_chunk) {
     for (int b0 = 0; b0 < B; b0 += st_chunk) {
       const int n = std::min(st_chunk, B - b0);
       auto view = [&](const Act& a) {
@@ -568,8 +593,34 @@ void UNetOpenAI::st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x, Act& o
       Act n2 = layernorm_fwd(c, s.ln2, h);
       q = conv_fwd(c, *s.q2, n2, nullptr, p0);
     }
-    Act a = attention_fwd(c, q.p, q.ld, k2c, C, v2c, C, B, s.heads, T, ctx_L_, s.dh, scale, x.H, x.W,
-                          /*q_log2=*/true);
+    Act a;
+    if (!ctrl_) {
+      a = attention_fwd(c, q.p, q.ld, k2c, C, v2c, C, B, s.heads, T, ctx_L_, s.dh, scale, x.H, x.W, /*q_log2=*/true);
+    } else {
+      // cross-attention control: the uncontrolled rows [0, row0) run the same launch as above, the controlled rows - the tail of
+      // the batch - k_cross_attention_ctrl; both write into one output tensor
+      const int Bu = ctrl_->row0;
+      CD_CHECK(b0 == 0 && Bu + ctrl_->rows == B, "cross-attention control: rows %d + %d of a batch of %d", Bu, ctrl_->rows, B);
+      const size_t bi = (size_t)(&s - st_.data());
+      CD_CHECK(bi < ctrl_->va.size(), "cross-attention control: no values for transformer block %d", (int)bi);
+      a = alloc_act(c, B, x.H, x.W, C);
+      AttnParams pu;
+      pu.q = q.p; pu.k = k2c; pu.v = v2c; pu.o = a.p;
+      pu.B = Bu; pu.H = s.heads; pu.Tq = T; pu.Tk = ctx_L_; pu.D = s.dh;
+      pu.ldq = q.ld; pu.ldk = C; pu.ldv = C; pu.ldo = a.ld;
+      pu.q_bs = (int64_t)T * q.ld; pu.k_bs = (int64_t)ctx_L_ * C; pu.v_bs = (int64_t)ctx_L_ * C; pu.o_bs = (int64_t)T * a.ld;
+      pu.scale = scale; pu.q_log2 = 1;
+      launch_attention(c.st, pu);
+      CtrlAttnParams p;
+      p.q_own = q.p + (int64_t)Bu * pu.q_bs; p.q_src = q.p + (int64_t)ctrl_->src_b0 * pu.q_bs;
+      p.k_own = k2c + (int64_t)Bu * pu.k_bs; p.k_src = k2c + (int64_t)ctrl_->src_b0 * pu.k_bs;
+      p.va = ctrl_->va[bi]; p.vb = ctrl_->vb[bi]; p.o = a.p + (int64_t)Bu * pu.o_bs;
+      p.B = ctrl_->rows; p.B_src = ctrl_->B_src; p.H = s.heads; p.Tq = T; p.L = ctx_L_; p.D = s.dh;
+      p.ldq = q.ld; p.ldk = C; p.ldv = C; p.ldo = a.ld;
+      p.q_bs = pu.q_bs; p.k_bs = pu.k_bs; p.v_bs = pu.v_bs; p.o_bs = pu.o_bs;
+      p.scale = scale; p.q_log2 = 1;
+      launch_cross_attention_ctrl(c.st, p);
+    }
     ConvOpts o; o.pad = 0; o.resid = &h; o.out = h.p; o.out_ld = h.ld;  // in-place residual update
     conv_fwd(c, *s.o2, a, nullptr, o);
     c.arena->release(m2);
@@ -669,6 +720,8 @@ void UNetOpenAI::forward(Ctx& c, const UNetIO& io) {
   const size_t mk0 = c.arena->mark();
   c.f32 = f32; c.x3 = x3;
   refresh_ln_folds(c);
+  CD_CHECK(!io.ctrl || (!f32 && io.ctrl->va.size() == st_.size()), "U-Net: cross-attention control on a network it was not built for");
+  ctrl_ = io.ctrl;
   const int B = io.B, R = image_size;
   // ---- time embedding: sinusoid -> Linear -> SiLU -> Linear, then every ResBlock's
   //      emb_layers (SiLU -> Linear) in one launch (openaimodel.py:506-511,723-724,263)
@@ -732,6 +785,7 @@ void UNetOpenAI::forward(Ctx& c, const UNetIO& io) {
   conv_fwd(c, *out_conv_, hn, nullptr, oo);
   c.arena->release(mk0);
   c.f32 = false; c.x3 = false;
+  ctrl_ = nullptr;
 }
 
 }  // namespace

@@ -568,6 +568,53 @@ class Engine:
         self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise)  # the launches read them asynchronously
         return z, x
 
+    def cycle_translate_ctrl(self, net, kind, x0, coef_enc, coef_dec, mapper, alpha, weight, n_ctrl, mask=None, mask_x0=None,
+                             qcoef=None, mask_noise=None, mask_seed=0, mask_source="q_sample", enc_ctx_c=None, enc_ctx_uc=None,
+                             enc_guidance=1.0, dec_ctx_c=None, dec_ctx_uc=None, dec_guidance=1.0, n_dec=1, noise=None, seed=0,
+                             last_uses_x0=True):
+        """cd_cycle_translate_ctrl: cycle_translate (mask=None) or cycle_translate_masked with cross-attention control on the
+        first n_ctrl iterations. mapper [B_ctrl, L, L], alpha / weight [B_ctrl, L] (attn_control.build_control), B_ctrl
+        dividing B; the decoder's conditional rows take P = w * (alpha * (P_src . M) + (1 - alpha) * P_own) in every text
+        cross-attention, P_src from the encoder's conditional row of the same sample in the same forward."""
+        x0 = self._f32(x0)
+        K = len(coef_dec)
+        assert len(coef_enc) == K + 1
+        B, Cc, H, W = x0.shape
+        Bm, src = 0, _ffi.CD_MASK_QSAMPLE
+        if mask is not None:
+            mask, mask_x0, Bm, src, qcoef, mask_noise = self._mask_args(mask, mask_x0, B, qcoef, mask_noise, mask_source, H, W,
+                                                                        Cc, K, b_noise=n_dec * B)
+        else:
+            mask_x0 = qcoef = mask_noise = None
+        z = torch.empty((B, K + 1, Cc, H, W), device=x0.device, dtype=torch.float32)
+        x = torch.empty((n_dec * B, Cc, H, W), device=x0.device, dtype=torch.float32)
+        coef_enc, coef_dec = np.ascontiguousarray(coef_enc), np.ascontiguousarray(coef_dec)
+        ctxs = [self._f32(t) if t is not None else None for t in (enc_ctx_c, enc_ctx_uc, dec_ctx_c, dec_ctx_uc)]
+        L = next((t.shape[1] for t in ctxs if t is not None), 0)
+        for t, rows in zip(ctxs, (B, B, n_dec * B, n_dec * B)):
+            assert t is None or t.shape[0] == rows, (t.shape, rows)
+        ctl = [torch.as_tensor(t, dtype=torch.float32).to(x0.device).contiguous() for t in (mapper, alpha, weight)]
+        Bc = ctl[0].shape[0]
+        if tuple(ctl[0].shape) != (Bc, L, L) or tuple(ctl[1].shape) != (Bc, L) or tuple(ctl[2].shape) != (Bc, L):
+            raise ValueError("control tensors must be mapper [B_ctrl, %d, %d], alpha / weight [B_ctrl, %d], got %s"
+                             % (L, L, L, [tuple(t.shape) for t in ctl]))
+        gvec, gscalar = None, 1.0
+        if isinstance(dec_guidance, (int, float)):
+            gscalar = float(dec_guidance)
+        else:
+            gvec = torch.as_tensor(dec_guidance, dtype=torch.float32).to(x0.device).contiguous()
+            if gvec.numel() != n_dec * B or bool(((gvec == 0) | (gvec == 1)).any()):
+                raise ValueError("per-sample guidance: n_dec * B scales, none of them 0 or 1")
+        nz = self._f32(noise) if noise is not None else None
+        check(self.lib.cd_cycle_translate_ctrl(
+            self.h, net, kind, ptr(x0), ptr(ctxs[0]), ptr(ctxs[1]), C.c_float(enc_guidance), ptr(ctxs[2]), ptr(ctxs[3]),
+            C.c_float(gscalar), ptr(gvec), L, B, n_dec, K, C.c_void_p(coef_enc.ctypes.data), C.c_void_p(coef_dec.ctypes.data),
+            ptr(nz), C.c_uint64(seed), int(last_uses_x0), ptr(mask), ptr(mask_x0), Bm, src,
+            C.c_void_p(qcoef.ctypes.data) if qcoef is not None else None, ptr(mask_noise), C.c_uint64(mask_seed),
+            ptr(ctl[0]), ptr(ctl[1]), ptr(ctl[2]), Bc, int(n_ctrl), ptr(z), ptr(x)))
+        self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise, ctl)  # the launches read them asynchronously
+        return z, x
+
     def pix_refine(self, net, kind, x, coef, noise=None, seed=0):
         x = self._f32(x).clone()
         R = len(coef) - 1

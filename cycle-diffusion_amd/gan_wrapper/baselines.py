@@ -81,7 +81,8 @@ class _LatentDDIBText(_LatentBaseline):
             raise ValueError("DDIB is deterministic: eta must be 0 or absent, got %r" % (eta,))
         if (n_trials or 1) != 1:
             raise ValueError("DDIB is deterministic: n_trials must be 1, got %r" % (n_trials,))
-        _reject("DDIB", white_box_steps=white_box_steps)  # the inversion is the whole chain; skip_steps shortens it
+        # the inversion is the whole chain (skip_steps shortens it); cross-attention control needs the coupled loop's source rows
+        _reject("DDIB", white_box_steps=white_box_steps, cac_steps=kw.pop("cac_steps", None), cac_mode=kw.pop("cac_mode", None))
         kw.setdefault("encoder_unconditional_guidance_scales", [1.0])
         kw.setdefault("decoder_unconditional_guidance_scales", [1.0])
         super().__init__(source_model_type, custom_steps, 0.0, -1, list(skip_steps), n_trials=1, couple=False, **kw)
@@ -129,7 +130,8 @@ class _LatentSDEditText(_LatentBaseline):
                 raise ValueError("sdedit strength %r gives t_enc = %d outside [1, %d]" % (s, t, custom_steps - 1))
         # no DPM-Encoder and no inversion: the strength alone sets where the decode starts
         _reject("SDEdit", skip_steps=skip_steps, white_box_steps=white_box_steps,
-                encoder_unconditional_guidance_scales=encoder_unconditional_guidance_scales)
+                encoder_unconditional_guidance_scales=encoder_unconditional_guidance_scales,
+                cac_steps=kw.pop("cac_steps", None), cac_mode=kw.pop("cac_mode", None))
         kw.setdefault("decoder_unconditional_guidance_scales", [1.0])
         super().__init__(source_model_type, custom_steps, eta, -1, [0], encoder_unconditional_guidance_scales=[1.0],
                          n_trials=n_trials or 1, couple=False, **kw)

@@ -24,7 +24,7 @@ import numpy as np
 
 import torch
 
-from .. import _ffi, schedule
+from .. import _ffi, attn_control, schedule
 from ..engine import kl_f8_vae_desc, ldm_text_unet_desc, sd_v1_unet_desc
 from ..runtime import get_engine, load_or_init_weights, read_checkpoint, synthetic_allowed
 
@@ -67,8 +67,17 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                  encoder_unconditional_guidance_scales=None, decoder_unconditional_guidance_scales=None,
                  n_trials=None, cond_stage=None, ranker=None, device=None, text_encoder=None,
                  noise_on_cpu=False, fold_ensemble=True, ranker_path=None, precision="fp16", couple=True,
-                 mask_source="q_sample"):
+                 mask_source="q_sample", cac_steps=0.0, cac_mode="refine"):
         super().__init__()
+        # `[gan] cac_steps` (0 = off, the default): cross-attention control (prompt-to-prompt on the coupled loop)
+        # on the first int(cac_steps * K) of the K decode steps a member runs; `cac_mode = refine | replace`: how the target
+        # prompt's tokens are matched to the source's (attn_control.build_control)
+        self.cac_steps = float(cac_steps)
+        if not 0.0 <= self.cac_steps <= 1.0:
+            raise ValueError("cac_steps must lie in [0, 1] (the controlled fraction of the decode steps), got %r" % (cac_steps,))
+        if str(cac_mode) not in attn_control.MODES:
+            raise ValueError("cac_mode must be one of %s" % (attn_control.MODES,))
+        self.cac_mode = str(cac_mode)
         # `[gan] mask_source`: what a keep-mask (forward / translate `mask=`) holds its region to - 'q_sample': a freshly noised
         # copy of the source latent per step, the reference's sample_with_eps(mask=, x0=) (ddim.py:427-430); 'encoder': the
         # DPM-Encoder's own x_t of every level (coupled loop only, no extra noise)
@@ -395,7 +404,7 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         return "cond" if scale == 1.0 else ("uncond" if scale == 0.0 else "cfg")
 
     # ---- encode + generate as ONE coupled loop (north_star; include/cyclediff.h cd_cycle_translate)
-    def translate(self, image, encode_text, decode_text, mask=None):
+    def translate(self, image, encode_text, decode_text, mask=None, attn_ctrl=None):
         """What Model.forward composes (model/text_unsupervised_translation.py:24-40): `self(encode(image, encode_text), image,
         encode_text, decode_text)`, with the DPM-Encoder and the decode of every ensemble member running as one loop - step k of
         both evaluates the same U-Net at the same timestep, and the decode step needs eps_k only after its forward, so each
@@ -403,7 +412,11 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         Same draws in the same order, same member order, same per-sample arithmetic as the two calls. Chains that leave part
         of the decode to fresh noise (white_box_steps shorter than the chain) take the two calls.
         `mask` (pixel-space [B, 1, R, R] in [0, 1], 1 = keep the source): the region-keeping edit, see _translate_masked;
-        without one every call below is the unmasked path's."""
+        without one every call below is the unmasked path's.
+        `attn_ctrl` (a prebuilt (M, alpha, w) of attn_control.build_control) or `[gan] cac_steps > 0`: cross-attention control,
+        see _translate_ctrl; with cac_steps = 0 and no attn_ctrl nothing below changes."""
+        if attn_ctrl is not None or self.cac_steps > 0:
+            return self._translate_ctrl(image, encode_text, decode_text, mask, attn_ctrl)
         if mask is not None:
             return self._translate_masked(image, encode_text, decode_text, mask)
         sch = self._schedule()
@@ -521,12 +534,109 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         img_ensemble = self.generate(z_ensemble, decode_text, latents=latents, mask=m, x0=x0, mask_noise=mask_noise)
         return self._select(img_ensemble, image, encode_text, decode_text)
 
+    def _control_ids(self, texts):
+        """token ids [B, L] of the prompts and the id that ends a prompt, from the text encoder's own tokenizer; a conditioning
+        stage without one (a callable embedder) falls back to the whitespace hash tokenizer, padded to the context length"""
+        from .text_encoders import EOS, BertHashTokenizer, BertWordPieceTokenizer, HashTokenizer
+        tok = getattr(self.cond_stage, "tokenizer", None)
+        if tok is None:
+            tok = HashTokenizer(getattr(self.cond_stage, "length", 77))
+        eos = BertHashTokenizer.SEP if isinstance(tok, (BertHashTokenizer, BertWordPieceTokenizer)) else EOS
+        return np.asarray(tok(list(texts))), eos
+
+    def _translate_ctrl(self, image, encode_text, decode_text, mask=None, attn_ctrl=None):
+        """translate() with cross-attention control: in the first n_ctrl = int(cac_steps * K) iterations of a member's K-step
+        loop the decoder's conditional rows take the source prompt's attention maps on the source image - recomputed from the
+        encoder's rows of the same forward - for the tokens both prompts share (attn_control.build_control; `attn_ctrl` replaces
+        the built (M, alpha, w)). The source rows only exist in the coupled loop, so this ALWAYS runs coupled; past
+        COUPLE_MAX_TOKENS it runs in chunks of samples, as mask_source = encoder does. Composes with a keep-mask of either
+        source. Draw order and member order are translate()'s."""
+        sch = self._schedule()
+        bsz = image.shape[0]
+        whole = all(self._white_box_loop(len(sch) - sk, sk) == len(sch) - sk for sk in self.skip_steps)
+        dec_scales = [float(sc) for sc in self.decoder_unconditional_guidance_scales]
+        n_dec = len(dec_scales)
+        kinds = [self._kind(sc) for sc in dec_scales]
+        main = "cfg" if "cfg" in kinds else kinds[0]
+        ride = [j for j in range(n_dec) if kinds[j] == main and (main == "cfg" or dec_scales[j] == dec_scales[kinds.index(main)])]
+        if not whole:
+            raise ValueError("cross-attention control needs the DPM-Encoder over the whole chain (white_box_steps = custom_steps "
+                             "+ 1): the steps past a shorter prefix have no source rows")
+        if len(ride) != n_dec or main == "uncond" or any(self._kind(float(sc)) == "uncond"
+                                                           for sc in self.encoder_unconditional_guidance_scales):
+            raise ValueError("cross-attention control: every decoder scale must ride in the coupled loop (all guided, or one "
+                             "unguided scale) and no scale may be 0 - the control acts on conditional rows")
+        m = self._latent_mask(mask, bsz) if mask is not None else None
+        encoder = m is not None and self.mask_source == "encoder"
+        enc_cfg = any(self._kind(float(sc)) == "cfg" for sc in self.encoder_unconditional_guidance_scales)
+        rows1 = (2 if enc_cfg else 1) + len(ride) * (2 if main == "cfg" else 1)  # rows of one sample of one member
+        tokens = self.image_size ** 2
+        fits = bsz * rows1 * tokens <= self.couple_max_tokens
+        self.last_translate_coupled = True
+        if attn_ctrl is None:
+            src_ids, eos = self._control_ids(encode_text)
+            tgt_ids, _ = self._control_ids(decode_text)
+            attn_ctrl = attn_control.build_control(src_ids, tgt_ids, self.cac_mode, eos_id=eos)
+        ctl = [torch.as_tensor(t, dtype=torch.float32).to(self.device) for t in attn_ctrl]
+        if ctl[0].shape[0] != bsz:
+            raise ValueError("attn_ctrl must carry one control per sample (%d), got %d" % (bsz, ctl[0].shape[0]))
+        x0, c_src, uc, members = self._encode_front(image, encode_text)
+        c_tgt, _ = self.get_condition(decode_text, bsz)
+        mask_noise = {}
+        if m is not None and not encoder:  # the reference's order: every member encoded, then member -> decoder scale, K draws
+            for i, mem in enumerate(members):
+                for j in range(n_dec):
+                    mask_noise[i * n_dec + j] = self._mask_draws(len(sch) - mem[1], bsz)[0]
+        bc = bsz if fits else max(1, self.couple_max_tokens // (rows1 * tokens))  # samples per coupled call
+        per_call = max(1, min(self.MAX_FOLD // (bc * (1 + len(ride))), self.couple_max_tokens // (bc * rows1 * tokens)))
+        z_parts, lat_parts = [[] for _ in members], {}
+        for s0 in range(0, bsz, bc):
+            sl = slice(s0, min(bsz, s0 + bc))
+            nb = sl.stop - sl.start
+            for grp in self._groups([(mm[0], mm[1]) for mm in members]):
+                enc_scale, skip = members[grp[0]][0], members[grp[0]][1]
+                n_ctrl = int(self.cac_steps * (len(sch) - skip))
+                for idx in self._chunks(grp, per_call):
+                    n, nr = len(idx), len(ride)
+                    if main == "cfg" and len({dec_scales[j] for j in ride}) > 1:
+                        guidance = torch.tensor([dec_scales[j] for j in ride for _ in range(n * nb)], dtype=torch.float32)
+                    else:
+                        guidance = dec_scales[ride[0]]
+                    kw = {}
+                    if m is not None:
+                        kw = dict(mask=m[sl].contiguous(), mask_source=self.mask_source)
+                        if not encoder:  # decoder row (jr * n + mi) * nb + b
+                            kw.update(mask_x0=x0[sl].contiguous(), qcoef=sch.coef_qsample(skip),
+                                      mask_noise=torch.cat([mask_noise[i * n_dec + j][:, sl] for j in ride for i in idx],
+                                                           dim=1).contiguous())
+                    z, x = self.engine.cycle_translate_ctrl(
+                        self.unet, _ffi.CD_SCHED_DDIM, x0[sl].repeat(n, 1, 1, 1), sch.coef_encode(skip), sch.coef_decode(skip),
+                        mapper=ctl[0][sl].contiguous(), alpha=ctl[1][sl].contiguous(), weight=ctl[2][sl].contiguous(),
+                        n_ctrl=n_ctrl, enc_ctx_c=c_src[sl].repeat(n, 1, 1), enc_ctx_uc=uc[sl].repeat(n, 1, 1),
+                        enc_guidance=enc_scale, dec_ctx_c=c_tgt[sl].repeat(n * nr, 1, 1), dec_ctx_uc=uc[sl].repeat(n * nr, 1, 1),
+                        dec_guidance=guidance, n_dec=nr, noise=torch.cat([members[i][2][:, sl] for i in idx], dim=1).contiguous(),
+                        last_uses_x0=True, **kw)
+                    for mi, i in enumerate(idx):
+                        z_parts[i].append(z[mi * nb:(mi + 1) * nb].reshape(nb, -1))
+                        for jr, j in enumerate(ride):
+                            lat_parts.setdefault(i * n_dec + j, []).append(x[(jr * n + mi) * nb:(jr * n + mi + 1) * nb])
+        z_ensemble = [torch.cat(p, 0) for p in z_parts]
+        latents = {k: torch.cat(v, 0) for k, v in lat_parts.items()}
+        if m is not None:
+            img_ensemble = self.generate(z_ensemble, decode_text, latents=latents, mask=m, x0=x0, mask_noise=mask_noise)
+        else:
+            img_ensemble = self.generate(z_ensemble, decode_text, latents=latents)
+        return self._select(img_ensemble, image, encode_text, decode_text)
+
     def forward(self, z_ensemble, original_img, encode_text, decode_text, mask=None):
         """`mask` (pixel-space [B, 1, R, R] in [0, 1], 1 = keep the source): the reference's sample_with_eps(mask=, x0=) decode.
         The blend's x0 is `original_img` re-encoded here with the posterior MEAN - no noise is drawn for it, whatever the
         family's encode() samples. Only mask_source 'q_sample' exists on this two-call path: the encoder's trajectory is gone
         once encode() has returned. The decoded image is not pasted over in pixel space: the kept region goes through the
         first stage like the rest."""
+        if getattr(self, "cac_steps", 0.0) > 0:
+            raise ValueError("cac_steps > 0 needs translate(): in encode() + forward() the source rows whose attention maps the "
+                             "control injects no longer exist; use translate(image, encode_text, decode_text)")
         if mask is None:
             return self._select(self.generate(z_ensemble, decode_text), original_img, encode_text, decode_text)
         if self.mask_source == "encoder":

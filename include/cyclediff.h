@@ -260,6 +260,28 @@ int cd_cycle_translate_masked(cd_handle h, int net, int sched_kind, const float*
                               int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
                               float* z_out, float* x_out);
 
+/* cd_cycle_translate(_masked) with cross-attention control (prompt-to-prompt on the coupled loop; the paper's "CycleDiffusion +
+ * CAC") on the first n_ctrl iterations (iteration 0 = the noisiest step). Arguments up to mask_seed as
+ * cd_cycle_translate_masked's, with mask = NULL for no keep-mask (the other mask arguments are then ignored). In every text
+ * cross-attention of those iterations, head h of decoder CONDITIONAL row r (sample b = r % B) computes
+ *     P = w * (alpha * (P_src . M) + (1 - alpha) * P_own),   O = P . V_own        (rows of P are not renormalised)
+ * where P_own is the row's own softmax(Q K^T * scale) and P_src that of the encoder's conditional row of sample b in the SAME
+ * forward against the source context; the products with alpha [L] and w [L] run over the key axis. mapper [B_ctrl,L,L],
+ * alpha / weight [B_ctrl,L] are fp32 device tensors, B a multiple of B_ctrl: sample b uses entry b % B_ctrl (members of a
+ * folded ensemble share their sample's control). Encoder rows, unconditional rows and iterations >= n_ctrl run exactly the
+ * kernels of cd_cycle_translate: z_out is bit-identical to the uncontrolled call's, and n_ctrl = 0 is that call.
+ * Refused (error text, nothing launched): coefficient tables whose rows k < K disagree on the timestep (checked for every
+ * n_ctrl), and for n_ctrl != 0: n_ctrl outside [0, K], sched_kind != CD_SCHED_DDIM, networks without a text context, networks
+ * of precision CD_PREC_F32 / CD_PREC_F32X3, ctx_len > 96, B % B_ctrl != 0, a pass without conditional rows (guidance 0). */
+int cd_cycle_translate_ctrl(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
+                            const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
+                            float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
+                            const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
+                            uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
+                            int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
+                            const float* mapper, const float* alpha, const float* weight, int B_ctrl, int n_ctrl,
+                            float* z_out, float* x_out);
+
 /* Stochastic refinement (ddpm_ddim_wrapper.py:431-453): x_t = sa*x + s1a*n (row R of coef_host),
  * then R random-noise steps rows R-1..0. noise [R+1,B,C,H,W] or NULL. In/out x [B,C,H,W]. */
 int cd_pix_refine(cd_handle h, int net, int sched_kind, float* x, int B, int R,
@@ -300,6 +322,13 @@ int cd_op_layernorm(cd_handle h, const float* x, int rows, int C, const float* g
    path: fused q|k|v projection, LDS transpose reads), 1 = V pre-transposed to [B,H,D,Tk_pad] first */
 int cd_op_attention(cd_handle h, const float* q, const float* k, const float* v, int B, int H, int Tq,
                     int Tk, int D, float scale, int use_transpose_kernel, float* o);
+/* one launch of the controlled cross-attention (k_cross_attention_ctrl) on caller tensors, fp32 device: q_own [B,Tq,H*D],
+   q_src [B_src,Tq,H*D], k_own [B,L_buf,H*D], k_src [B_src,L_buf,H*D] (rows L..L_buf-1 of each sample are never used),
+   v_own [B,L,H*D], mapper [B_ctrl,L,L], alpha / weight [B_ctrl,L] -> o [B,Tq,H*D]; row b uses source b % B_src and control
+   b % B_ctrl. L <= 96, D in {32, 40, 64, 80, 160}. */
+int cd_op_cross_attention_ctrl(cd_handle h, const float* q_own, const float* q_src, const float* k_own, const float* k_src,
+                               const float* v_own, const float* mapper, const float* alpha, const float* weight, int B,
+                               int B_src, int B_ctrl, int H, int Tq, int L, int L_buf, int D, float scale, float* o);
 int cd_op_softmax_rows(cd_handle h, const float* s, int64_t rows, int cols, float* p);
 int cd_op_timestep_embedding(cd_handle h, const float* t, int B, int dim, int mode, float* out);
 /* one scheduler step on explicit tensors (bit-exact checks): mode 0 init_xt, 1 encode, 2 decode */
