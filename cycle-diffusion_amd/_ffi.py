@@ -90,6 +90,7 @@ SIGNATURES = {
     "cd_op_last_gemm_config": [_VP] + [C.POINTER(_I)] * 5,
     "cd_op_up_phase_reorder": [_VP, _VP, _I, _I, _I, _I, _VP],
     "cd_op_groupnorm": [_VP, _VP, _I, _I, _I, _I, _I, _F, _VP, _VP, _VP, _I, _VP],
+    "cd_op_groupnorm_ex": [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, _F, _VP, _VP, _VP, _I, _I, _VP, _VP, _I, _VP],
     "cd_op_layernorm": [_VP, _VP, _I, _I, _VP, _VP, _F, _VP],
     "cd_op_attention": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _I, _VP],
     "cd_op_cross_attention_ctrl": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _VP],

@@ -1128,6 +1128,56 @@ int cd_op_groupnorm(cd_handle h, const float* x, int B, int C, int H, int W, int
   CD_API_END
 }
 
+// GroupNorm as the networks call it (groupnorm_fwd on the precision they run): one source or a channel concat of two, each
+// with its own row stride C + pad (pad columns hold NaN: a read past C shows in the result), the producing convs' block
+// statistics handed in by the caller (Act::stats), a FiLM row per image or one shared row (film_ld = 0)
+int cd_op_groupnorm_ex(cd_handle h, const float* x0, int C0, int pad0, const float* x1, int C1, int pad1, int B, int H,
+                       int W, float eps, const float* gamma, const float* beta, const float* film, int film_ld, int silu,
+                       const float* stats0, const float* stats1, int precision, void* y) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x0 && gamma && beta && y && B > 0 && H > 0 && W > 0 && C0 > 0 && pad0 >= 0 && pad1 >= 0, "bad argument");
+  CD_CHECK(x1 ? C1 > 0 : (C1 == 0 && !stats1), "bad argument (second source)");
+  CD_CHECK(precision >= 0 && precision <= 2 && film_ld >= 0, "bad argument (precision 0 = 16-bit, 1 = fp32, 2 = fp32 split)");
+  const int align = precision ? 4 : 8;  // the kernels' vector width in elements
+  CD_CHECK((C0 + pad0) % align == 0 && (C1 + pad1) % align == 0, "row strides must be multiples of %d elements", align);
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  c.f32 = precision != 0; c.x3 = precision == 2;
+  const int HW = H * W, C = C0 + C1;
+  auto upload = [&](const float* x, int Cs, int pad, const float* stats) {
+    Act a; a.B = B; a.H = H; a.W = W; a.C = Cs; a.ld = Cs + pad; a.f32 = c.f32;
+    a.p = (bf16_t*)h->arena.alloc((size_t)B * HW * a.ld * (c.f32 ? sizeof(float) : sizeof(bf16_t)));
+    const float* src = x;
+    if (pad) {  // NCHW staging copy with `pad` more channels of NaN per image
+      const size_t n = (size_t)B * a.ld * HW;
+      float* t = (float*)h->arena.alloc(n * sizeof(float));
+      launch_fill_f32(h->st, t, __builtin_nanf(""), (int64_t)n);
+      HIP_CHECK(hipMemcpy2DAsync(t, (size_t)a.ld * HW * 4, x, (size_t)Cs * HW * 4, (size_t)Cs * HW * 4, B,
+                                 hipMemcpyDeviceToDevice, h->st));
+      src = t;
+    }
+    if (c.f32) launch_nchw_to_nhwc_f32(h->st, src, a.pf(), B, a.ld, HW, a.ld, 1.f, 0.f);
+    else launch_nchw_to_nhwc(h->st, src, a.p, B, a.ld, HW, a.ld, 1.f, 0.f, 0);
+    a.stats = const_cast<float*>(stats);
+    return a;
+  };
+  Act a0 = upload(x0, C0, pad0, stats0);
+  Act a1;
+  if (x1) a1 = upload(x1, C1, pad1, stats1);
+  GNW w; w.g = const_cast<float*>(gamma); w.b = const_cast<float*>(beta); w.C = C; w.eps = eps;
+  Act o = groupnorm_fwd(c, w, a0, x1 ? &a1 : nullptr, silu != 0, film, film_ld);
+  if (precision == 2) {  // the raw [rows][hi(C) | lo(C)] fp16 pairs, and the range guard of the split representation
+    CD_CHECK(o.split && o.ld == 2 * C, "groupnorm: split output expected");
+    HIP_CHECK(hipMemcpyAsync(y, o.p, (size_t)B * HW * 2 * C * sizeof(bf16_t), hipMemcpyDeviceToDevice, h->st));
+    HIP_CHECK(hipStreamSynchronize(h->st));
+    h->check_overflow();
+  } else {
+    launch_nhwc_to_nchw(h->st, o.p, c.f32 ? 1 : 0, o.ld, (float*)y, B, C, HW, 1.f, 0.f);
+  }
+  CD_API_END
+}
+
 int cd_op_layernorm(cd_handle h, const float* x, int rows, int C, const float* gamma, const float* beta,
                     float eps, float* y) {
   CD_API_BEGIN

@@ -316,6 +316,17 @@ int cd_op_last_gemm_config(cd_handle h, int* tile_id, int* bk, int* splitk, int*
 int cd_op_up_phase_reorder(cd_handle h, const float* x, int B, int C, int H, int W, float* y);
 int cd_op_groupnorm(cd_handle h, const float* x, int B, int C, int H, int W, int G, float eps,
                     const float* gamma, const float* beta, const float* film, int silu, float* y);
+/* GroupNorm(32) the way the networks call it. x0 fp32 NCHW [B,C0,H,W] and, if x1 is given, x1 [B,C1,H,W]: the channel
+ * concat [x0 | x1] is normalised. Each source is stored NHWC with row stride C + pad; the pad columns hold NaN. film: fp32
+ * [B][film_ld] rows of scale(C) | shift(C), film_ld = 0: one row shared by the batch. stats0 / stats1 (either may be NULL):
+ * the block statistics a producing convolution's epilogue writes, fp32 [B*H*W / 32][2][C0] and [..][2][C1] (see
+ * cd_op_conv2d_16); they are used only where the networks would use them (both sources carry them, pad = 0, H*W % 32 == 0),
+ * otherwise the tensor is read. precision: 0 = the 16-bit path (y fp32 NCHW [B,C0+C1,H,W]), 1 = the fp32 path (the same),
+ * 2 = its split mode: y receives the raw fp16 pairs [B*H*W][hi(C) | lo(C)], value = (hi + lo) / 16, and the call fails
+ * with the range-guard error when an output left the representable range (|y| >= 4094). */
+int cd_op_groupnorm_ex(cd_handle h, const float* x0, int C0, int pad0, const float* x1, int C1, int pad1, int B, int H,
+                       int W, float eps, const float* gamma, const float* beta, const float* film, int film_ld, int silu,
+                       const float* stats0, const float* stats1, int precision, void* y);
 int cd_op_layernorm(cd_handle h, const float* x, int rows, int C, const float* gamma, const float* beta,
                     float eps, float* y);
 /* q [B,Tq,H*D], k,v [B,Tk,H*D] fp32 -> o [B,Tq,H*D]; use_transpose_kernel: 0 = V consumed token-major (the U-Net

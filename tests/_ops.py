@@ -134,6 +134,49 @@ def groupnorm(eng, x, gamma, beta, eps, silu=False, film=None):
     return y.cpu()
 
 
+X3_ACT_SCALE = 16.0  # csrc/kernels.h kX3ActScale
+
+
+def groupnorm_ex(eng, x0, gamma, beta, eps, x1=None, pad0=0, pad1=0, silu=False, film=None, film_shared=False,
+                 film_ld=None, stats0=None, stats1=None, precision=0):
+    """cd_op_groupnorm_ex: groupnorm_fwd as the networks call it. film [B, 2C] (or [2C] with film_shared: film_ld = 0);
+    film_ld > 2C pads every FiLM row with NaN. precision 2 decodes the fp16 pairs of the split output."""
+    B, C0, H, W = x0.shape
+    C1 = x1.shape[1] if x1 is not None else 0
+    Cc = C0 + C1
+    f, ld = None, 0
+    if film is not None:
+        if film_shared:
+            assert film.shape == (2 * Cc,)
+            f = dev(film)
+        else:
+            ld = film_ld or 2 * Cc
+            rows = torch.full((B, ld), float("nan"))
+            rows[:, :2 * Cc] = film
+            f = dev(rows)
+    xs0, xs1 = dev(x0), dev(x1) if x1 is not None else None
+    g, b = dev(gamma), dev(beta)
+
+    def guarded(st):  # one more block of NaN behind the statistics: an index past the end stays in the tensor and shows
+        if st is None:
+            return None
+        return dev(torch.cat([st.float(), torch.full((1,) + tuple(st.shape[1:]), float("nan"))], 0))
+
+    s0, s1 = guarded(stats0), guarded(stats1)
+    if precision == 2:
+        y = torch.empty((B * H * W, 2 * Cc), device="cuda", dtype=torch.float16)
+    else:
+        y = torch.empty((B, Cc, H, W), device="cuda", dtype=torch.float32)
+    check(eng.lib.cd_op_groupnorm_ex(eng.h, ptr(xs0), C0, pad0, ptr(xs1), C1, pad1, B, H, W, C.c_float(eps), ptr(g), ptr(b),
+                                     ptr(f), ld, int(silu), ptr(s0), ptr(s1), precision, ptr(y)))
+    torch.cuda.synchronize()
+    if precision == 2:  # (hi + lo) / kX3ActScale: exact in float64
+        y = y.cpu().double()
+        y = (y[:, :Cc] + y[:, Cc:]) / X3_ACT_SCALE
+        return y.reshape(B, H, W, Cc).permute(0, 3, 1, 2).contiguous()
+    return y.cpu()
+
+
 def layernorm(eng, x, gamma, beta, eps=1e-5):
     rows, Cc = x.shape
     y = torch.empty_like(x, device="cuda")
