@@ -81,6 +81,7 @@ SIGNATURES = {
                                   _VP, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP],
     "cd_cycle_translate_ctrl": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I,
                                 _VP, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP, _VP, _I, _I, _VP, _VP],
+    "cd_ilvr_decode": [_VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _U64, _VP, _I, _I, _I, _VP, _VP, _U64, _VP],
     "cd_pix_refine": [_VP, _I, _I, _VP, _I, _I, _VP, _VP, _U64],
     "cd_op_pack_conv_weight": [_VP, _VP, _I, _I, _I, _I, _I, C.POINTER(_VP), C.POINTER(_I), C.POINTER(_I)],
     "cd_op_free": [_VP, _VP],
@@ -94,6 +95,7 @@ SIGNATURES = {
     "cd_op_layernorm": [_VP, _VP, _I, _I, _VP, _VP, _F, _VP],
     "cd_op_attention": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _I, _VP],
     "cd_op_cross_attention_ctrl": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _VP],
+    "cd_op_lowpass": [_VP, _VP, _I, _I, _I, _I, _VP],
     "cd_op_softmax_rows": [_VP, _VP, _I64, _I, _VP],
     "cd_op_timestep_embedding": [_VP, _VP, _I, _I, _I, _VP],
     "cd_op_sched_step": [_VP, _I, _I, _VP, _VP, _VP, _VP, _I, _F, _VP, _VP, _I, _I, _I, _I, _VP],

@@ -994,6 +994,93 @@ int cd_pix_refine(cd_handle h, int net, int sched_kind, float* x, int B, int R, 
   CD_API_END
 }
 
+}  // extern "C"
+
+// ---- ILVR (csrc/ilvr.hip)
+namespace {
+LowpassTaps upload_taps(cd_engine* h, int n_in, int n_out) {
+  std::vector<float> w;
+  std::vector<int> first;
+  LowpassTaps t;
+  t.n_in = n_in; t.n_out = n_out;
+  build_lowpass_taps(n_in, n_out, w, first, t.P);
+  t.w = (const float*)upload_table(h, w.data(), w.size() * sizeof(float));
+  t.first = (const int*)upload_table(h, first.data(), first.size() * sizeof(int));
+  return t;
+}
+
+void check_lowpass_geometry(int R, int down_n) {
+  CD_CHECK(down_n >= 1, "ILVR: down_n must be >= 1, got %d", down_n);
+  CD_CHECK(R % down_n == 0, "ILVR: down_n = %d does not divide the resolution %d", down_n, R);
+  CD_CHECK(R / down_n >= 4, "ILVR: R / down_n = %d / %d leaves fewer than 4 pixels (the cubic window then reflects twice)", R, down_n);
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+}  // namespace
+
+extern "C" {
+
+// ILVR: cd_ddim_decode's loop without contexts; after the decode step of row k > range_t the running image is pulled to
+// the reference's low-pass band, x <- x' + phi_N((qa_k y + qb_k n_k) - x'). Rows k <= range_t run the decode step alone.
+int cd_ilvr_decode(cd_handle h, int net, int sched_kind, const float* z, int z_slots, int n_eps, int B, int K,
+                   const cd_step_coef* coef_host, const float* noise_tail, uint64_t seed, const float* ref, int B_ref,
+                   int down_n, int range_t, const float* qsample_coef_host, const float* ref_noise, uint64_t ref_seed,
+                   float* x_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && z && coef_host && x_out && ref && B > 0 && K > 0 && n_eps <= z_slots - 1, "bad argument");
+  UNet* u = get_unet(h, net);
+  CD_CHECK(!(u->desc.use_spatial_transformer && u->desc.context_dim > 0),
+           "ILVR runs on an unconditional pixel DDPM: this network takes a text context");
+  const int R = u->image_size;
+  check_lowpass_geometry(R, down_n);
+  CD_CHECK(range_t >= 0, "ILVR: range_t must be >= 0, got %d", range_t);
+  CD_CHECK(B_ref > 0 && B % B_ref == 0, "ILVR: %d reference images for a batch of %d", B_ref, B);
+  CD_CHECK(qsample_coef_host, "ILVR: the q-sample coefficient table is NULL");
+  ArenaScope arena_scope(h->arena);
+  SamplerState s = setup_sampler(h, net, nullptr, nullptr, 0, 1.f, B);
+  StepArgs& a = s.args;
+  a.geom.tab = upload_coef(h, coef_host, K);
+  const int64_t chw = (int64_t)s.C * s.HW, n = (int64_t)B * chw;
+  const int64_t zbs = (int64_t)z_slots * chw;
+  a.eps.bstride = zbs; a.gauss.seed = seed;
+  IlvrArgs iv;
+  if (range_t < K - 1) {  // some row is conditioned
+    const int r = R / down_n;
+    iv.xp = iv.out = s.xt;
+    iv.y = ref; iv.y_bmod = B_ref;
+    iv.qtab = (const float2*)upload_table(h, qsample_coef_host, (size_t)K * 2 * sizeof(float));
+    iv.gauss.seed = ref_seed;
+    iv.B = B; iv.C = s.C; iv.R = R;
+    iv.D = upload_taps(h, R, r);
+    iv.U = upload_taps(h, r, R);
+    iv.T = (float*)h->arena.alloc((size_t)B * s.C * r * r * sizeof(float));
+    iv.xin = a.xin;
+    iv.vec4 = (R % 4 == 0 && aligned16(ref) && aligned16(ref_noise)) ? 1 : 0;
+  }
+  HIP_CHECK(hipMemcpy2DAsync(s.xt, chw * 4, z, zbs * 4, chw * 4, B, hipMemcpyDeviceToDevice, h->st));
+  if (!s.f32) launch_nchw_to_nhwc(h->st, s.xt, s.xin, B, s.C, s.HW, s.cpad, 1.f, 0.f, 0);
+  for (int i = 0; i < K; ++i) {
+    const int k = K - 1 - i;
+    run_unet(h, s, k);
+    const float* eps = (i < n_eps) ? z + (int64_t)(1 + i) * chw : nullptr;
+    const float* nz = (!eps && noise_tail) ? noise_tail + (int64_t)(i - n_eps) * n : nullptr;
+    a.geom.step = k; a.eps.p = eps;
+    a.gauss.noise = nz; a.gauss.stream = (uint32_t)(0x1000 + i);
+    launch_decode_step(h->st, sched_kind, a);
+    if (k > range_t) {
+      iv.qrow = k;
+      iv.gauss.noise = ref_noise ? ref_noise + (int64_t)i * n : nullptr;
+      iv.gauss.stream = (uint32_t)(0x5000 + i);  // its own stream: the step's draws are 0x1000 + i
+      launch_ilvr_down(h->st, iv);
+      launch_ilvr_up_add(h->st, iv);
+    }
+    h->pacer.tick(h->st);
+  }
+  HIP_CHECK(hipMemcpyAsync(x_out, s.xt, (size_t)n * 4, hipMemcpyDeviceToDevice, h->st));
+  CD_API_END
+}
+
 // ------------------------------------------------------------------ single-kernel entry points
 int cd_op_pack_conv_weight(cd_handle h, const float* w_host, int N, int Cin, int KH, int KW, int geglu,
                            void** packed_dev, int* Npad, int* Cpad) {
@@ -1251,6 +1338,27 @@ int cd_op_cross_attention_ctrl(cd_handle h, const float* q_own, const float* q_s
   p.scale = scale;
   launch_cross_attention_ctrl(h->st, p);
   launch_nhwc_to_nchw(h->st, ob, 0, C, o, B * Tq, C, 1, 1.f, 0.f);
+  CD_API_END
+}
+
+// y = phi_N(x) through the two ILVR kernels (x' = 0, qa = 1, qb = 0)
+int cd_op_lowpass(cd_handle h, const float* x, int B, int C, int R, int down_n, float* y) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && y && B > 0 && C > 0 && R > 0, "bad argument");
+  check_lowpass_geometry(R, down_n);
+  ArenaScope arena_scope(h->arena);
+  const int r = R / down_n;
+  IlvrArgs iv;
+  iv.out = y; iv.y = x; iv.y_bmod = B;
+  iv.B = B; iv.C = C; iv.R = R;
+  iv.D = upload_taps(h, R, r);
+  iv.U = upload_taps(h, r, R);
+  iv.T = (float*)h->arena.alloc((size_t)B * C * r * r * sizeof(float));
+  iv.vec4 = (R % 4 == 0 && aligned16(x) && aligned16(y)) ? 1 : 0;
+  launch_ilvr_down(h->st, iv);
+  launch_ilvr_up_add(h->st, iv);
+  HIP_CHECK(hipStreamSynchronize(h->st));
   CD_API_END
 }
 

@@ -83,6 +83,39 @@ void launch_decode_step(hipStream_t st, int kind, const StepArgs& a, const MaskB
 // a.xt <- blend(a.xt) ahead of the first forward; uses a.geom and a.xin beside it
 void launch_mask_blend_init(hipStream_t st, const StepArgs& a, const MaskBlend& mk);
 
+// ---------------------------------------------------------------- ILVR low-pass conditioning (ilvr.hip)
+// A resize matrix M [n_out, n_in] as its nonzero taps: row i is w[t * n_out + i] at column first[i] + t, t = 0 .. P-1
+// (tap-major, so that neighbouring lanes read neighbouring rows). The host has folded the mirrored border taps into the
+// interior and clamped first[i] to [0, n_in - P]: a kernel never tests a boundary.
+struct LowpassTaps {
+  const float* w = nullptr;
+  const int* first = nullptr;
+  int n_out = 0, n_in = 0, P = 0;
+};
+// x <- x' + phi_N(y' - x'), phi_N(X) = U D X D^T U^T per channel image, y' = qa * y + qb * n; two launches:
+//   launch_ilvr_down    T[b, c] = D (y' - x') D^T   [B, C, r, r], r = R / N
+//   launch_ilvr_up_add  out = x' + U T U^T          (and the next forward's 16-bit input, if xin is set)
+// Fixed summation order: taps ascending (compensated), the row index of the image first, then the column index.
+struct IlvrArgs {
+  const float* xp = nullptr;     // x' [B, C, R, R]; null = 0 (cd_op_lowpass)
+  float* out = nullptr;          // [B, C, R, R]; may be xp
+  const float* y = nullptr;      // the reference image [y_bmod, C, R, R]: sample b reads row b % y_bmod
+  int y_bmod = 1;
+  const float2* qtab = nullptr;  // (qa, qb) by row; null = (1, 0)
+  int qrow = 0;
+  GaussSrc gauss;                // n; not drawn when qb == 0
+  float* T = nullptr;
+  int B = 0, C = 0, R = 0;
+  LowpassTaps D, U;              // D [r, R], U [R, r]
+  XinOut xin;
+  int vec4 = 0;                  // 1: R % 4 == 0 and every tensor is 16-byte aligned
+};
+constexpr int kIlvrMaxR = 1024;
+// resize_matrix(n_in, n_out) of utils/lowpass.py as taps, in float64 on the host, rounded once: w [P][n_out], first [n_out]
+void build_lowpass_taps(int n_in, int n_out, std::vector<float>& w, std::vector<int>& first, int& P);
+void launch_ilvr_down(hipStream_t st, const IlvrArgs& a);
+void launch_ilvr_up_add(hipStream_t st, const IlvrArgs& a);
+
 // ---------------------------------------------------------------- implicit-GEMM conv / GEMM (conv_gemm.hip)
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_GEGLU = 3, ACT_QGELU = 4, ACT_RELU = 5 };  // QGELU: x*sigmoid(1.702x) (CLIP)
 // RELU: max(x, 0) (the BasicConv2d units of the FID Inception-v3, inception.hip)

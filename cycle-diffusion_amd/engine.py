@@ -615,6 +615,42 @@ class Engine:
         self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise, ctl)  # the launches read them asynchronously
         return z, x
 
+    def ilvr_decode(self, net, kind, z, coef, ref, down_n, qcoef, range_t=0, n_eps=0, noise_tail=None, seed=0, ref_noise=None,
+                    ref_seed=0):
+        """cd_ilvr_decode: ddim_decode on an unconditional pixel DDPM with ILVR's low-pass conditioning on the reference image
+        `ref` [B_ref, C, R, R] (B_ref dividing B) after the step of every row k > range_t. qcoef = PixelSchedule.coef_ilvr()
+        [K, 2]; ref_noise [K, B, C, R, R] (slot i = the draw of loop iteration i) or None (Philox(ref_seed))."""
+        z = self._f32(z)
+        B, T, Cc, H, W = z.shape
+        K = len(coef)
+        ref = self._f32(ref)
+        if ref.dim() != 4 or tuple(ref.shape[1:]) != (Cc, H, W):
+            raise ValueError("the reference image must be [B_ref, %d, %d, %d], got %s" % (Cc, H, W, tuple(ref.shape)))
+        qcoef = np.ascontiguousarray(qcoef, dtype=np.float32)
+        if qcoef.shape != (K, 2):
+            raise ValueError("q-sample table must be [%d, 2] (PixelSchedule.coef_ilvr), got %s" % (K, qcoef.shape))
+        nt = self._f32(noise_tail) if noise_tail is not None else None
+        if ref_noise is not None:
+            ref_noise = self._f32(ref_noise)
+            if tuple(ref_noise.shape) != (K, B, Cc, H, W):
+                raise ValueError("ref_noise must be %s, got %s" % ((K, B, Cc, H, W), tuple(ref_noise.shape)))
+        x = torch.empty((B, Cc, H, W), device=z.device, dtype=torch.float32)
+        coef = np.ascontiguousarray(coef)
+        check(self.lib.cd_ilvr_decode(self.h, net, kind, ptr(z), T, n_eps, B, K, C.c_void_p(coef.ctypes.data), ptr(nt),
+                                      C.c_uint64(seed), ptr(ref), ref.shape[0], int(down_n), int(range_t),
+                                      C.c_void_p(qcoef.ctypes.data), ptr(ref_noise), C.c_uint64(ref_seed), ptr(x)))
+        self._keep = (z, nt, ref, ref_noise)  # the launches read them asynchronously
+        return x
+
+    def op_lowpass(self, x, down_n):
+        """cd_op_lowpass: phi_N of fp32 [B, C, R, R] through the two ILVR kernels"""
+        x = self._f32(x)
+        B, Cc, R, W = x.shape
+        assert R == W, x.shape
+        y = torch.empty_like(x)
+        check(self.lib.cd_op_lowpass(self.h, ptr(x), B, Cc, R, int(down_n), ptr(y)))
+        return y
+
     def pix_refine(self, net, kind, x, coef, noise=None, seed=0):
         x = self._f32(x).clone()
         R = len(coef) - 1

@@ -1,6 +1,6 @@
-"""The two baselines the paper compares CycleDiffusion with (README "CycleDiffusion (ours) vs DDIB vs SDEdit"; the unpaired
-Cat -> Dog / Wild -> Dog tables), as gan_types beside the wrappers they mirror - same text encoders, first stage, ranker,
-precision and noise hooks:
+"""The baselines the paper compares CycleDiffusion with (README "CycleDiffusion (ours) vs DDIB vs SDEdit"; the unpaired
+Cat -> Dog / Wild -> Dog tables, which also list ILVR), as gan_types beside the wrappers they mirror - same text encoders,
+first stage, ranker, precision and noise hooks:
 
   DDIB   deterministic DDIM inversion under the source (model / text), then a deterministic DDIM decode under the target.
          Inversion: include/cyclediff.h cd_ddim_invert on DDIMSchedule.coef_invert / PixelSchedule.coef_invert rows
@@ -10,6 +10,9 @@ precision and noise hooks:
          stochastic_encode + decode (ddim.py:648-681) for the latent models, sample_xt + generate()'s chain for the pixel
          DDPMs (ddpm_ddim_wrapper.py:310-314, 392-430). The q-sample is cd_dpm_encode with K = 0, the decode is the
          existing decode-with-eps path (cd_ddim_decode(_v) with the per-step noise injected as eps).
+  ILVR   (pixel DDPMs only) the target's ordinary stochastic chain from pure noise; after every step above `ilvr_range_t` the
+         running image takes the low-pass band of the freshly noised source image, x <- x' + phi_N(y' - x') (Choi et al.,
+         ICCV 2021, Algorithm 1; cd_ilvr_decode). No source model is evaluated.
 
 None of these classes has a translate(): Model.forward runs encode() then forward(), as the reference composes them.
 """
@@ -255,6 +258,50 @@ class DDPMSDEditWrapper(_NoCoupledLoop, DDPMDDIMWrapper):
         return x
 
 
+class DDPMILVRWrapper(_NoCoupledLoop, DDPMDDIMWrapper):
+    """gan_type = DDPM_ILVR, keys `ilvr_down_n` (N of the low-pass filter phi_N; divides the resolution, R / N >= 4) and
+    `ilvr_range_t` (default 0: the steps of decode rows k > ilvr_range_t are conditioned, so only the last one is free).
+    Source side: encode(image) = the image itself in [-1, 1] as [B, C*R*R] - no network. Target side: forward(z) = generate()'s
+    chain from x_T ~ N(0, I) with fresh noise per step (the configured sample_type / eta) and the conditioning after each step,
+    then refinement and post-process."""
+
+    def __init__(self, source_model_type, sample_type, custom_steps, es_steps, ilvr_down_n, ilvr_range_t=0,
+                 sdedit_strengths=None, skip_steps=None, white_box_steps=None, **kw):
+        from ..utils import lowpass
+        from .ddpm_ddim_wrapper import MODEL_TYPES, _desc
+        _reject("ILVR", sdedit_strengths=sdedit_strengths, skip_steps=skip_steps, white_box_steps=white_box_steps)
+        for name, v, lo in (("ilvr_down_n", ilvr_down_n, 1), ("ilvr_range_t", ilvr_range_t, 0)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+                raise ValueError("%s must be an integer >= %d, got %r" % (name, lo, v))
+        if source_model_type not in MODEL_TYPES:
+            raise NotImplementedError(source_model_type)
+        net_desc = kw.get("net_desc")
+        res = (net_desc if net_desc is not None else _desc(MODEL_TYPES[source_model_type][0])).image_size
+        lowpass.check_geometry(res, ilvr_down_n)  # before the engine and the weights exist
+        super().__init__(source_model_type, sample_type, custom_steps, es_steps, **kw)
+        self.ilvr_down_n, self.ilvr_range_t = ilvr_down_n, ilvr_range_t
+        self.latent_dim = self.resolution ** 2 * self.channels
+
+    def encode(self, image, class_label=None):
+        assert image.shape[2] == image.shape[3] == self.resolution
+        return ((image - 0.5) * 2.0).to(self.device, torch.float32).reshape(image.shape[0], -1)
+
+    def generate(self, z, class_label):
+        bsz, K = z.shape[0], self.es_steps
+        y = z.view(bsz, self.channels, self.resolution, self.resolution).contiguous()
+        xT = self._randn(1, tuple(y.shape))
+        # per step: denoising_step's randn_like, then the draw that noises the reference (Algorithm 1's order)
+        nz = self._randn(2 * K, tuple(y.shape))
+        x = self.engine.ilvr_decode(self.net, self.sched.kind, xT.transpose(0, 1).contiguous(), self.sched.coef_decode(), y,
+                                    self.ilvr_down_n, self.sched.coef_ilvr(), range_t=self.ilvr_range_t, n_eps=0,
+                                    noise_tail=nz[0::2].contiguous(), ref_noise=nz[1::2].contiguous())
+        x = self._refine(x)
+        self._range_guard()
+        return x
+
+
 GAN_TYPES = {"SDDDIBText": SDDDIBTextWrapper, "LatentDiffDDIBText": LatentDiffDDIBTextWrapper,
              "SDSDEditText": SDSDEditTextWrapper, "LatentDiffSDEditText": LatentDiffSDEditTextWrapper,
              "DDPM_DDIB": DDPMDDIBWrapper, "DDPM_SDEdit": DDPMSDEditWrapper}
+# the samplers that take the source IMAGE rather than a latent of a source model; get_gan_wrapper looks here after GAN_TYPES
+SAMPLER_TYPES = {"DDPM_ILVR": DDPMILVRWrapper}

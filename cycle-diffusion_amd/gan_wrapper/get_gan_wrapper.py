@@ -25,7 +25,9 @@ def get_gan_wrapper(args, target=False):
     if args.gan_type == "LatentDiffStochastic":
         from .latent_wrapper import LatentDiffStochasticWrapper
         return LatentDiffStochasticWrapper(**kwargs)
-    from .baselines import GAN_TYPES  # the DDIB / SDEdit baselines (gan_wrapper/baselines.py)
+    from .baselines import GAN_TYPES, SAMPLER_TYPES  # the DDIB / SDEdit / ILVR baselines (gan_wrapper/baselines.py)
     if args.gan_type in GAN_TYPES:
         return GAN_TYPES[args.gan_type](**kwargs)
+    if args.gan_type in SAMPLER_TYPES:
+        return SAMPLER_TYPES[args.gan_type](**kwargs)
     raise ValueError(args.gan_type)

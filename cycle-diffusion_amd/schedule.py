@@ -208,6 +208,13 @@ class PixelSchedule:
             rows[K - 1 - it] = self._row(i, j, self.eta)
         return _pack(rows)
 
+    def coef_ilvr(self):
+        """ILVR's q-sample of the reference image (cd_ilvr_decode): [K, 2] fp32, row k = (sqrt(abar), sqrt(1 - abar)) of the
+        level seq_next[k] that coef_decode()'s row k ARRIVES at (Algorithm 1 of the paper noises y to t - 1), from the fp32
+        alpha-bar; the last row arrives at the clean image, abar := 1 (it is never conditioned)."""
+        ab = np.asarray([ONE if j == -1 else self.acp[j] for j in self.seq_next], dtype=f32)
+        return np.ascontiguousarray(np.stack([np.sqrt(ab), np.sqrt(ONE - ab)], axis=1).astype(f32))
+
     def _row_eta0(self, i, j):
         """denoising_step(..., eta=0, 'ddim') (diffusion_utils.py:114-117): no sigma term, sqrt(1 - at_next) direction."""
         at = self.acp[i]

@@ -282,6 +282,25 @@ int cd_cycle_translate_ctrl(cd_handle h, int net, int sched_kind, const float* x
                             const float* mapper, const float* alpha, const float* weight, int B_ctrl, int n_ctrl,
                             float* z_out, float* x_out);
 
+/* ILVR (Choi et al., ICCV 2021: Iterative Latent Variable Refinement), the reference-image-conditioned sampler of the
+ * paper's unpaired table; no counterpart in the reference tree. cd_ddim_decode's loop on an unconditional
+ * pixel DDPM, with the running image pulled to the low-pass band of a reference image after the step of every row k > range_t:
+ *     x' = the decode step of row k (sched_kind, bit for bit cd_ddim_decode's)
+ *     y' = qa_k * ref + qb_k * n_k,  x = x' + phi_N(y' - x'),  phi_N(X) = U D X D^T U^T per channel image,
+ * D the antialiased cubic down-by-down_n [R / down_n, R] and U the cubic up-by-down_n (cycle-diffusion_amd/utils/lowpass.py;
+ * fp32, taps ascending, rows then columns). Row 0 is never conditioned; range_t >= K - 1 conditions nothing and is
+ * cd_ddim_decode bit for bit.
+ *   Arguments up to `seed` as cd_ddim_decode's, without contexts and guidance. ref [B_ref,C,R,R] in [-1, 1], B a multiple of
+ *   B_ref: sample b uses row b % B_ref. qsample_coef_host: K rows of (qa, qb) = (sqrt(abar), sqrt(1 - abar)) of the level the
+ *   step of row k ARRIVES at, row index = k (PixelSchedule.coef_ilvr). n_k = ref_noise[K-1-k] of ref_noise [K,B,C,R,R] (slot i =
+ *   the draw of loop iteration i) or Philox(ref_seed) when ref_noise is NULL.
+ * Refused (error text, nothing launched): networks with a text context, down_n < 1, R % down_n != 0, R / down_n < 4,
+ * range_t < 0, B % B_ref != 0, qsample_coef_host == NULL, R > 1024. down_n = 1 is the identity filter: x = x' + (y' - x'). */
+int cd_ilvr_decode(cd_handle h, int net, int sched_kind, const float* z, int z_slots, int n_eps, int B, int K,
+                   const cd_step_coef* coef_host, const float* noise_tail, uint64_t seed, const float* ref, int B_ref,
+                   int down_n, int range_t, const float* qsample_coef_host, const float* ref_noise, uint64_t ref_seed,
+                   float* x_out);
+
 /* Stochastic refinement (ddpm_ddim_wrapper.py:431-453): x_t = sa*x + s1a*n (row R of coef_host),
  * then R random-noise steps rows R-1..0. noise [R+1,B,C,H,W] or NULL. In/out x [B,C,H,W]. */
 int cd_pix_refine(cd_handle h, int net, int sched_kind, float* x, int B, int R,
@@ -340,6 +359,9 @@ int cd_op_attention(cd_handle h, const float* q, const float* k, const float* v,
 int cd_op_cross_attention_ctrl(cd_handle h, const float* q_own, const float* q_src, const float* k_own, const float* k_src,
                                const float* v_own, const float* mapper, const float* alpha, const float* weight, int B,
                                int B_src, int B_ctrl, int H, int Tq, int L, int L_buf, int D, float scale, float* o);
+/* y = phi_N(x) on caller tensors, fp32 NCHW [B,C,R,R], through the two kernels of cd_ilvr_decode (x' = 0, qa = 1, qb = 0);
+ * refused as cd_ilvr_decode refuses its geometry. */
+int cd_op_lowpass(cd_handle h, const float* x, int B, int C, int R, int down_n, float* y);
 int cd_op_softmax_rows(cd_handle h, const float* s, int64_t rows, int cols, float* p);
 int cd_op_timestep_embedding(cd_handle h, const float* t, int B, int dim, int mode, float* out);
 /* one scheduler step on explicit tensors (bit-exact checks): mode 0 init_xt, 1 encode, 2 decode */
