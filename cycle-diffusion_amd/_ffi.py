@@ -92,6 +92,12 @@ SIGNATURES = {
     "cd_op_up_phase_reorder": [_VP, _VP, _I, _I, _I, _I, _VP],
     "cd_op_groupnorm": [_VP, _VP, _I, _I, _I, _I, _I, _F, _VP, _VP, _VP, _I, _VP],
     "cd_op_groupnorm_ex": [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, _F, _VP, _VP, _VP, _I, _I, _VP, _VP, _I, _VP],
+    "cd_op_pack_conv_weight_prec": [_VP, _VP, _I, _I, _I, _I, _I, C.POINTER(_VP)],
+    "cd_op_conv2d_prec": [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, _VP, _I, _I, _I, _I, _I, _I, _I, _VP, _VP, _I, _VP, _I, _I,
+                          _I, _I, _I, _I, _F, _VP, _VP],
+    "cd_op_attention_prec": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _VP, _I, _I, _VP],
+    "cd_op_rows_prec": [_VP, _I, _VP, _I64, _I, _I, _VP, _I, _I, _VP, _VP, _I, _VP],
+    "cd_op_resample_prec": [_VP, _I, _VP, _I, _I, _I, _I, _I, _VP],
     "cd_op_layernorm": [_VP, _VP, _I, _I, _VP, _VP, _F, _VP],
     "cd_op_attention": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _I, _VP],
     "cd_op_cross_attention_ctrl": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _VP],

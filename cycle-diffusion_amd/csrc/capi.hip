@@ -79,6 +79,7 @@ struct cd_engine {
   std::vector<std::unique_ptr<Net>> nets;
   std::vector<ParamStore*> op_stores;  // storage behind cd_op_pack_conv
   ParamStore op_params;
+  ParamStore op_params_f32;  // fp32 rows (+ the three-term fp16 splits on the fp16 build) behind cd_op_pack_conv_weight_prec
   std::unique_ptr<KernelProfiler> prof;
   SplitKWorkspace splitk;  // split-K partial tiles + arrival counters of THIS engine's stream (conv_gemm.hip)
   // CD_PREC_F32X3 range guard: one word of mapped host memory the split kernels set when a scaled activation / weight
@@ -190,6 +191,7 @@ int cd_engine_create(void* hip_stream, size_t workspace_bytes, cd_handle* out) {
   HIP_CHECK(hipHostMalloc((void**)&h->overflow_host, 64, hipHostMallocMapped));
   *h->overflow_host = 0;
   HIP_CHECK(hipHostGetDevicePointer((void**)&h->overflow_dev, h->overflow_host, 0));
+  h->op_params_f32.f32 = true; h->op_params_f32.x3 = CD_ACT_FP16 != 0; h->op_params_f32.overflow = h->overflow_dev;
   *out = h.release();
   CD_API_END
 }
@@ -1622,3 +1624,230 @@ extern "C" int cd_op_probe(cd_handle h, int which, const void* in, void* out, si
   }
   CD_API_END
 }
+
+// ------------------------------------------------------------------ single-kernel entry points of the fp32 path
+// The engine's building blocks as the networks call them under a Ctx with f32 (precision 1) or f32 + x3 (precision 2, the
+// split-fp16 mode) set. Operands are stored with row stride C + pad; the pad columns hold NaN, so a read past C shows.
+namespace {
+
+float* op_nan_buffer(cd_engine* h, size_t n) {
+  float* t = (float*)h->arena.alloc(n * sizeof(float));
+  launch_fill_f32(h->st, t, __builtin_nanf(""), (int64_t)n);
+  return t;
+}
+// columns [col0, col0 + C) of dst [rows][ld] <- src [rows][C]
+void op_put_cols(cd_engine* h, float* dst, int ld, int col0, const float* src, int64_t rows, int C) {
+  HIP_CHECK(hipMemcpy2DAsync(dst + col0, (size_t)ld * 4, src, (size_t)C * 4, (size_t)C * 4, (size_t)rows,
+                             hipMemcpyDeviceToDevice, h->st));
+}
+Act op_rows_act(float* p, int64_t rows, int C, int ld) {
+  Act a; a.p = (bf16_t*)p; a.B = (int)rows; a.H = 1; a.W = 1; a.C = C; a.ld = ld; a.f32 = true;
+  return a;
+}
+// fp32 [rows][C] -> [rows][C + pad], NaN in the pad columns
+Act op_upload_rows(cd_engine* h, const float* x, int64_t rows, int C, int pad) {
+  const int ld = C + pad;
+  float* t = op_nan_buffer(h, (size_t)rows * ld);
+  op_put_cols(h, t, ld, 0, x, rows, C);
+  return op_rows_act(t, rows, C, ld);
+}
+// fp32 NCHW [B][C][HW] -> fp32 NHWC with row stride ld: channels [C, Czero) hold 0 (the weights' channel padding), [Czero, ld) NaN
+Act op_upload_nhwc(cd_engine* h, const float* x, int B, int C, int Czero, int ld, int H, int W) {
+  const int HW = H * W;
+  Act a; a.B = B; a.H = H; a.W = W; a.C = Czero; a.ld = ld; a.f32 = true;
+  a.p = (bf16_t*)h->arena.alloc((size_t)B * HW * ld * sizeof(float));
+  const float* src = x;
+  if (ld != C) {  // NCHW staging copy with ld channels per image
+    float* t = op_nan_buffer(h, (size_t)B * ld * HW);
+    if (Czero > C)
+      HIP_CHECK(hipMemset2DAsync(t + (size_t)C * HW, (size_t)ld * HW * 4, 0, (size_t)(Czero - C) * HW * 4, B, h->st));
+    HIP_CHECK(hipMemcpy2DAsync(t, (size_t)ld * HW * 4, x, (size_t)C * HW * 4, (size_t)C * HW * 4, B, hipMemcpyDeviceToDevice,
+                               h->st));
+    src = t;
+  }
+  launch_nchw_to_nhwc_f32(h->st, src, a.pf(), B, ld, HW, ld, 1.f, 0.f);
+  return a;
+}
+// the split form straight from NCHW (k_nchw_to_nhwc_split, as the U-Net input is uploaded): [pixel][hi(Cpad) | lo(Cpad)]
+Act op_upload_nhwc_split(cd_engine* h, const float* x, int B, int C, int Cpad, int H, int W) {
+  Act a; a.B = B; a.H = H; a.W = W; a.C = Cpad; a.ld = 2 * Cpad; a.f32 = true; a.split = true;
+  a.p = (bf16_t*)h->arena.alloc((size_t)B * H * W * 2 * Cpad * sizeof(bf16_t));
+  launch_nchw_to_nhwc_f32(h->st, x, a.pf(), B, C, H * W, Cpad, 1.f, 0.f, 1, h->overflow_dev);
+  return a;
+}
+// a result of `floats` 4-byte words (fp32 rows, or the fp16 pairs of the split mode: the same bytes) -> y; the range guard
+void op_download(cd_engine* h, const Act& o, size_t floats, void* y) {
+  HIP_CHECK(hipMemcpyAsync(y, o.p, floats * 4, hipMemcpyDeviceToDevice, h->st));
+  HIP_CHECK(hipStreamSynchronize(h->st));
+  h->check_overflow();
+}
+
+}  // namespace
+
+extern "C" {
+
+int cd_op_pack_conv_weight_prec(cd_handle h, const float* w_host, int N, int Cin, int KH, int KW, int geglu,
+                                void** packed_dev) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && w_host && packed_dev, "bad argument");
+  static int counter = 0;
+  ConvW* c = h->op_params_f32.new_conv(N, Cin, KH, KW, false, geglu != 0);
+  const std::string name = "op32." + std::to_string(counter++);
+  h->op_params_f32.conv_weight(name, c);
+  int64_t shape[4] = {N, Cin, KH, KW};
+  h->op_params_f32.load(h->st, name, w_host, 4, shape);  // synchronises: a weight outside the split range raises here
+  h->check_overflow();
+  *packed_dev = c;
+  CD_API_END
+}
+
+int cd_op_conv2d_prec(cd_handle h, const float* x0, int C0, int pad0, const float* x1, int C1, int pad1, int B, int H, int W,
+                      const void* packed_w, int N, int KH, int KW, int stride, int pad, int asym_pad, int up,
+                      const float* bias, const float* rowvec, int rowvec_shared, const float* resid, int resid_pad, int act,
+                      int raw_geglu, int tile, int precision, int via_split_rows, float alpha, float* y, float* stats) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x0 && packed_w && y && B > 0 && H > 0 && W > 0 && C0 > 0 && pad0 >= 0 && pad1 >= 0 && resid_pad >= 0,
+           "bad argument");
+  CD_CHECK(precision == 1 || precision == 2, "bad argument (precision 1 = fp32, 2 = fp32 split)");
+  CD_CHECK(x1 ? C1 > 0 : C1 == 0, "bad argument (second source)");
+  CD_CHECK(pad0 % 4 == 0 && pad1 % 4 == 0, "row padding must be a multiple of 4 elements");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  c.f32 = true; c.x3 = precision == 2;
+  ConvW w = *(const ConvW*)packed_w;
+  CD_CHECK(w.f32 && w.N == N && w.KH == KH && w.KW == KW, "packed weight does not match the call");
+  w.b = const_cast<float*>(bias);
+  const int c0p = x1 ? C0 : round_up(C0, 32);
+  Act a0, a1;
+  const Act* second = nullptr;
+  if (precision == 2 && !x1 && !via_split_rows) {
+    CD_CHECK(pad0 == 0, "the split form has no row padding");
+    a0 = op_upload_nhwc_split(h, x0, B, C0, c0p, H, W);
+  } else {
+    a0 = op_upload_nhwc(h, x0, B, C0, c0p, c0p + pad0, H, W);
+    if (x1) a1 = op_upload_nhwc(h, x1, B, C1, C1, C1 + pad1, H, W);
+    if (precision == 2) a0 = split_rows_f32_fwd(c, a0, x1 ? &a1 : nullptr);  // as unet_openai.hip feeds its skip projections
+    else second = x1 ? &a1 : nullptr;
+  }
+  ConvOpts o; o.stride = stride; o.pad = pad; o.asym = asym_pad != 0; o.up = up != 0; o.tile = tile;
+  o.act = act; o.alpha = alpha; o.raw_geglu = raw_geglu != 0; o.want_stats = stats != nullptr;
+  const int Hin = up ? 2 * H : H, Win = up ? 2 * W : W;
+  const int Ho = asym_pad ? (Hin + 1 - KH) / stride + 1 : (Hin + 2 * pad - KH) / stride + 1;
+  const int Wo = asym_pad ? (Win + 1 - KW) / stride + 1 : (Win + 2 * pad - KW) / stride + 1;
+  if (rowvec) { o.rowvec = rowvec; o.rowvec_ld = N; o.rows_per_vec = rowvec_shared ? B * Ho * Wo : Ho * Wo; }
+  Act r;
+  if (resid) {
+    r = op_upload_nhwc(h, resid, B, N, N, N + resid_pad, Ho, Wo);
+    r.C = N;
+    o.resid = &r;
+  }
+  Act out = conv_fwd(c, w, a0, second, o);
+  CD_CHECK(out.f32 && !out.split && out.C == N, "conv: fp32 output expected");
+  launch_nhwc_to_nchw(h->st, out.p, 1, out.ld, y, B, N, Ho * Wo, 1.f, 0.f);
+  if (stats) {
+    CD_CHECK(out.stats, "this convolution produces no GroupNorm statistics (fp32 without the split mode, or rows %% 32 != 0)");
+    HIP_CHECK(hipMemcpyAsync(stats, out.stats, (size_t)(out.rows() / 32) * 2 * N * sizeof(float), hipMemcpyDeviceToDevice,
+                             h->st));
+  }
+  HIP_CHECK(hipStreamSynchronize(h->st));
+  h->check_overflow();
+  CD_API_END
+}
+
+int cd_op_attention_prec(cd_handle h, const float* q, const float* k, const float* v, int B, int H, int Tq, int Tk, int D,
+                         int padq, int padk, int padv, float scale, int q_log2, const float* obias, int mode, int precision,
+                         void* o) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && q && k && v && o && B > 0 && H > 0 && Tq > 0 && Tk > 0 && D > 0 && padq >= 0 && padk >= 0 && padv >= 0,
+           "bad argument");
+  CD_CHECK(mode >= 0 && mode <= 2 && (precision == 1 || (precision == 2 && mode == 2)),
+           "bad argument (mode 0 = attention_f32_fwd, 1 = one wave per query, 2 = flash; the split output is mode 2's)");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  c.f32 = true; c.x3 = precision == 2;
+  const int C = H * D;
+  Act out;
+  if (mode == 2) {
+    CD_CHECK(!obias, "attention_flash_f32_fwd takes no output bias");
+    Act qa = op_upload_rows(h, q, (int64_t)B * Tq, C, padq);
+    Act ka = op_upload_rows(h, k, (int64_t)B * Tk, C, padk);
+    Act va = op_upload_rows(h, v, (int64_t)B * Tk, C, padv);
+    out = attention_flash_f32_fwd(c, qa.pf(), qa.ld, ka.pf(), ka.ld, (int64_t)Tk * ka.ld, va.pf(), va.ld, (int64_t)Tk * va.ld, B,
+                                  H, Tq, Tk, D, scale, Tq, 1, q_log2 != 0);
+  } else {
+    CD_CHECK(Tq == Tk && !q_log2 && padk == 0, "modes 0 and 1 take one fused q | k tensor (Tq = Tk, its padding in padq)");
+    const int T = Tq, ld = 2 * C + padq;
+    float* qk = op_nan_buffer(h, (size_t)B * T * ld);
+    op_put_cols(h, qk, ld, 0, q, (int64_t)B * T, C);
+    op_put_cols(h, qk, ld, C, k, (int64_t)B * T, C);
+    Act va = op_upload_rows(h, v, (int64_t)B * T, C, padv);
+    if (mode == 0) {
+      Act qka; qka.p = (bf16_t*)qk; qka.B = B; qka.H = T; qka.W = 1; qka.C = 2 * C; qka.ld = ld; qka.f32 = true;
+      va.B = B; va.H = T;
+      out = attention_f32_fwd(c, qka, va, H, D, scale, obias);
+    } else {
+      out = alloc_act(c, B, T, 1, C);
+      launch_attention_f32(h->st, qk, ld, qk + C, ld, va.pf(), va.ld, out.pf(), out.ld, B, H, T, D, scale, obias);
+    }
+  }
+  CD_CHECK(out.split == (precision == 2), "attention: output form");
+  op_download(h, out, (size_t)B * Tq * C, o);
+  CD_API_END
+}
+
+int cd_op_rows_prec(cd_handle h, int op, const float* x0, int64_t rows, int C0, int pad0, const float* x1, int C1, int pad1,
+                    const float* gamma, const float* beta, int precision, void* y) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x0 && y && rows > 0 && C0 > 0 && pad0 >= 0 && pad1 >= 0, "bad argument");
+  CD_CHECK(precision == 1 || precision == 2, "bad argument (precision 1 = fp32, 2 = fp32 split)");
+  CD_CHECK(x1 ? (C1 > 0 && op == 2) : C1 == 0, "bad argument (second source: split_rows only)");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  c.f32 = true; c.x3 = precision == 2;
+  Act a0 = op_upload_rows(h, x0, rows, C0, pad0);
+  Act out;
+  if (op == 0) {
+    CD_CHECK(gamma && beta, "layernorm: gain and bias");
+    LNW w; w.g = const_cast<float*>(gamma); w.b = const_cast<float*>(beta); w.C = C0;
+    out = layernorm_fwd(c, w, a0);
+  } else if (op == 1) {
+    out = geglu_f32_fwd(c, a0);
+  } else if (op == 2) {
+    Act a1;
+    if (x1) a1 = op_upload_rows(h, x1, rows, C1, pad1);
+    out = split_rows_f32_fwd(c, a0, x1 ? &a1 : nullptr);
+  } else {
+    CD_CHECK(false, "bad argument (op 0 = LayerNorm, 1 = GEGLU, 2 = split_rows)");
+  }
+  CD_CHECK(out.split == (precision == 2), "rows: output form");
+  op_download(h, out, (size_t)rows * out.C, y);
+  CD_API_END
+}
+
+int cd_op_resample_prec(cd_handle h, int op, const float* x, int B, int C, int H, int W, int precision, void* y) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && y && B > 0 && C > 0 && C % 4 == 0 && H > 0 && W > 0, "bad argument");
+  CD_CHECK((op == 0 && (precision == 1 || precision == 2) && H % 2 == 0 && W % 2 == 0) || (op == 1 && precision == 1),
+           "bad argument (op 0 = 2x2 average pool, fp32 or split; 1 = nearest x2 upsample, fp32)");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  c.f32 = true; c.x3 = precision == 2;
+  if (precision == 2) {
+    Act a = op_upload_nhwc_split(h, x, B, C, C, H, W);
+    Act out = avgpool2_fwd(c, a);
+    CD_CHECK(out.split, "avgpool: split output expected");
+    op_download(h, out, (size_t)out.rows() * C, y);
+  } else {
+    Act a = op_upload_nhwc(h, x, B, C, C, C, H, W);
+    Act out = op == 0 ? avgpool2_fwd(c, a) : upsample2_fwd(c, a);
+    launch_nhwc_to_nchw(h->st, out.p, 1, out.ld, (float*)y, B, C, out.H * out.W, 1.f, 0.f);
+  }
+  CD_API_END
+}
+
+}  // extern "C"

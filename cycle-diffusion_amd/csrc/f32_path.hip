@@ -9,7 +9,9 @@
 // (DESIGN.md §5). These networks are small (1-94 M parameters), so the 157 TFLOP/s fp32 MFMA rate is ample.
 //
 // One tile shape per problem size and a fixed k-ascending accumulation order: results are bit-reproducible across
-// processes (no autotuner, no split-K on this path).
+// processes (no autotuner, no split-K in k_conv_f32). The split mode's three-term GEMMs run on launch_conv_gemm: the tuner
+// picks their tile, which does not change the bits; a split-K factor would (it sums its K ranges in range order) and
+// comes only from the shipped table, fixed per shape.
 #include <stdio.h>
 
 #include "common.h"
@@ -403,7 +405,8 @@ __global__ void k_pack_w3(const float* __restrict__ w, _Float16* __restrict__ w3
 }
 
 // ---------------------------------------------------------------------------------------- attention
-// softmax(scale * q k^T) v for the pixel U-Nets' AttentionBlock / AttnBlock (<= 1024 tokens per image):
+// softmax(scale * q k^T) v for the pixel U-Nets' AttentionBlock / AttnBlock (launch_attention_f32: (D + T) * 4 <= 64 KiB of
+// LDS, e.g. 15872 tokens at D = 512; the networks use it at <= 1024 tokens per image):
 // one wave per (image, head, query); scores in LDS; fp32 throughout (QKVAttentionLegacy upcasts its softmax to
 // fp32 as well, improved_ddpm/unet.py:357).
 __global__ __launch_bounds__(64) void k_attention_f32(const float* __restrict__ q, const float* __restrict__ k,

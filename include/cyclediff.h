@@ -346,6 +346,38 @@ int cd_op_groupnorm(cd_handle h, const float* x, int B, int C, int H, int W, int
 int cd_op_groupnorm_ex(cd_handle h, const float* x0, int C0, int pad0, const float* x1, int C1, int pad1, int B, int H,
                        int W, float eps, const float* gamma, const float* beta, const float* film, int film_ld, int silu,
                        const float* stats0, const float* stats1, int precision, void* y);
+/* ---- single-kernel entry points of the fp32 execution path (CD_PREC_F32 = precision 1, CD_PREC_F32X3 = precision 2) ----
+ * The engine's building blocks as the networks call them. Activations are stored with row stride C + pad (pad % 4 == 0 where a
+ * kernel reads vectors); the pad columns hold NaN. Precision 2 results that are split activations arrive as the raw fp16 pairs
+ * [rows][hi(C) | lo(C)], value = (hi + lo) / 16; every call synchronises and fails with the range-guard error ("fp16 range") when
+ * a scaled value left the fp16 range. */
+/* weights for cd_op_conv2d_prec: fp32 rows and (fp16 build) their three-term split [wh | wh | wl]; |w| >= 255 raises here */
+int cd_op_pack_conv_weight_prec(cd_handle h, const float* w_host, int N, int Cin, int KH, int KW, int geglu,
+                                void** packed_dev);
+/* precision 1: conv_fwd -> k_conv_f32 (the channel concat [x0 | x1] inside the kernel). precision 2: the input in split form
+ * (one source, via_split_rows = 0: straight from NCHW as the U-Net input is uploaded; otherwise split_rows_f32_fwd(x0, x1) on the
+ * padded fp32 rows) -> the three-term GEMM with its fp32 residual and, if `stats` is given, the GroupNorm block statistics
+ * of the output (fp32 [B*Ho*Wo / 32][2][N]; an error where the convolution writes none). rowvec: fp32 [B][N], or one [N] row
+ * with rowvec_shared; resid: fp32 NCHW [B,N,Ho,Wo], stored with row stride N + resid_pad (any resid_pad >= 0); raw_geglu:
+ * weights packed with geglu = 1 leave their [32 value | 32 gate] column blocks as they are; y = fp32 NCHW [B,N,Ho,Wo]. */
+int cd_op_conv2d_prec(cd_handle h, const float* x0, int C0, int pad0, const float* x1, int C1, int pad1, int B, int H, int W,
+                      const void* packed_w, int N, int KH, int KW, int stride, int pad, int asym_pad, int up,
+                      const float* bias, const float* rowvec, int rowvec_shared, const float* resid, int resid_pad, int act,
+                      int raw_geglu, int tile, int precision, int via_split_rows, float alpha, float* y, float* stats);
+/* q [B,Tq,H*D], k, v [B,Tk,H*D] fp32 -> o [B,Tq,H*D]. mode 0 = attention_f32_fwd on a fused q | k tensor (row stride
+ * 2 H D + padq; flash for D <= 160, else one wave per query), 1 = the wave-per-query kernel forced, both with Tq = Tk and an
+ * optional output bias [H*D]; 2 = attention_flash_f32_fwd with separate q / k / v row strides H D + pad, Tq != Tk, q_log2
+ * (q already carries scale * log2 e) and, at precision 2, the split output. */
+int cd_op_attention_prec(cd_handle h, const float* q, const float* k, const float* v, int B, int H, int Tq, int Tk, int D,
+                         int padq, int padk, int padv, float scale, int q_log2, const float* obias, int mode, int precision,
+                         void* o);
+/* row-wise pieces on fp32 rows x0 [rows][C0] (stride C0 + pad0): op 0 = layernorm_fwd (eps 1e-5), 1 = geglu_f32_fwd
+ * (C0 = 2 Nout in the packed [32 value | 32 gate] order -> [rows][Nout]), 2 = split_rows_f32_fwd(x0, x1) (precision 2 only) */
+int cd_op_rows_prec(cd_handle h, int op, const float* x0, int64_t rows, int C0, int pad0, const float* x1, int C1, int pad1,
+                    const float* gamma, const float* beta, int precision, void* y);
+/* x fp32 NCHW [B,C,H,W]: op 0 = avgpool2_fwd (precision 1 -> y fp32 NCHW [B,C,H/2,W/2]; precision 2: split input and
+ * output, y = the raw pairs [B*H/2*W/2][2C]), op 1 = upsample2_fwd (precision 1, y fp32 NCHW [B,C,2H,2W]) */
+int cd_op_resample_prec(cd_handle h, int op, const float* x, int B, int C, int H, int W, int precision, void* y);
 int cd_op_layernorm(cd_handle h, const float* x, int rows, int C, const float* gamma, const float* beta,
                     float eps, float* y);
 /* q [B,Tq,H*D], k,v [B,Tk,H*D] fp32 -> o [B,Tq,H*D]; use_transpose_kernel: 0 = V consumed token-major (the U-Net

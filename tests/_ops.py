@@ -177,6 +177,98 @@ def groupnorm_ex(eng, x0, gamma, beta, eps, x1=None, pad0=0, pad1=0, silu=False,
     return y.cpu()
 
 
+# ---------------------------------------------------------------------------------------------- fp32 path (precision 1 / 2)
+def decode_pairs(y, Cc):
+    """raw fp16 pairs [rows][hi(C) | lo(C)] -> float64 [rows][C] = (hi + lo) / kX3ActScale (exact)"""
+    y = y.cpu().double()
+    return (y[:, :Cc] + y[:, Cc:]) / X3_ACT_SCALE
+
+
+def pack_conv_prec(eng, w, geglu=False):
+    """cd_op_pack_conv_weight_prec: fp32 rows + their three-term fp16 split; raises the range error for |w| >= 255"""
+    w = w.detach().float().cpu().contiguous()
+    if w.dim() == 2:
+        w = w[:, :, None, None].contiguous()
+    N, Cin, KH, KW = w.shape
+    out = C.c_void_p()
+    check(eng.lib.cd_op_pack_conv_weight_prec(eng.h, C.c_void_p(w.data_ptr()), N, Cin, KH, KW, int(geglu), C.byref(out)))
+    return out, (N, Cin, KH, KW)
+
+
+def conv_out_hw(H, W, k, stride, pad, asym, up):
+    Hin, Win = (2 * H, 2 * W) if up else (H, W)
+    if asym:
+        return (Hin + 1 - k) // stride + 1, (Win + 1 - k) // stride + 1
+    return (Hin + 2 * pad - k) // stride + 1, (Win + 2 * pad - k) // stride + 1
+
+
+def conv2d_prec(eng, x0, w, precision, x1=None, pad0=0, pad1=0, stride=1, pad=1, asym=False, up=False, bias=None, rowvec=None,
+                resid=None, resid_pad=0, act=0, alpha=1.0, tile=0, geglu=False, via_split_rows=False, want_stats=False):
+    """cd_op_conv2d_prec: conv_fwd on the fp32 path (precision 1: k_conv_f32; 2: the three-term split GEMM). rowvec [B, N] or
+    a shared [N] row; geglu: weights packed with geglu = 1, columns returned raw in the packed order. -> y or (y, stats)"""
+    handle, (N, Cin, KH, KW) = pack_conv_prec(eng, w, geglu)
+    B, C0, H, W = x0.shape
+    C1 = x1.shape[1] if x1 is not None else 0
+    Ho, Wo = conv_out_hw(H, W, KH, stride, pad, asym, up)
+    y = torch.empty((B, N, Ho, Wo), device="cuda", dtype=torch.float32)
+    st = torch.zeros((B * Ho * Wo // 32, 2, N), device="cuda", dtype=torch.float32) if want_stats else None
+    b = None
+    if bias is not None:
+        b = dev(geglu_pack_vec(bias) if geglu else bias)
+    xs0, xs1 = dev(x0), dev(x1) if x1 is not None else None
+    rv, rs = dev(rowvec) if rowvec is not None else None, dev(resid) if resid is not None else None
+    shared = rowvec is not None and rowvec.dim() == 1
+    check(eng.lib.cd_op_conv2d_prec(eng.h, ptr(xs0), C0, pad0, ptr(xs1), C1, pad1, B, H, W, handle, N, KH, KW, stride, pad,
+                                    int(asym), int(up), ptr(b), ptr(rv), int(shared), ptr(rs), resid_pad, act, int(geglu), tile,
+                                    precision, int(via_split_rows), C.c_float(alpha), ptr(y), ptr(st)))
+    torch.cuda.synchronize()
+    return (y.cpu(), st.cpu()) if want_stats else y.cpu()
+
+
+def attention_prec(eng, q, k, v, heads, scale, mode, precision=1, padq=0, padk=0, padv=0, q_log2=False, obias=None):
+    """cd_op_attention_prec: q [B, Tq, H D], k / v [B, Tk, H D] -> [B, Tq, H D] (float64 of the decoded pairs at precision 2)"""
+    B, Tq, Cc = q.shape
+    Tk = k.shape[1]
+    o = torch.empty((B * Tq, 2 * Cc), device="cuda", dtype=torch.float16) if precision == 2 else \
+        torch.empty((B * Tq, Cc), device="cuda", dtype=torch.float32)
+    qs, ks, vs = dev(q), dev(k), dev(v)
+    ob = dev(obias) if obias is not None else None
+    check(eng.lib.cd_op_attention_prec(eng.h, ptr(qs), ptr(ks), ptr(vs), B, heads, Tq, Tk, Cc // heads, padq, padk, padv,
+                                       C.c_float(scale), int(q_log2), ptr(ob), mode, precision, ptr(o)))
+    torch.cuda.synchronize()
+    o = decode_pairs(o, Cc) if precision == 2 else o.cpu()
+    return o.reshape(B, Tq, Cc)
+
+
+def rows_prec(eng, op, x0, precision, x1=None, pad0=0, pad1=0, gamma=None, beta=None):
+    """cd_op_rows_prec: op "layernorm" | "geglu" | "split_rows" on fp32 rows [rows, C]"""
+    code = {"layernorm": 0, "geglu": 1, "split_rows": 2}[op]
+    rows, C0 = x0.shape
+    C1 = x1.shape[1] if x1 is not None else 0
+    Cout = C0 // 2 if code == 1 else C0 + C1
+    y = torch.empty((rows, 2 * Cout), device="cuda", dtype=torch.float16) if precision == 2 else \
+        torch.empty((rows, Cout), device="cuda", dtype=torch.float32)
+    xs0, xs1 = dev(x0), dev(x1) if x1 is not None else None
+    g, b = dev(gamma) if gamma is not None else None, dev(beta) if beta is not None else None
+    check(eng.lib.cd_op_rows_prec(eng.h, code, ptr(xs0), rows, C0, pad0, ptr(xs1), C1, pad1, ptr(g), ptr(b), precision, ptr(y)))
+    torch.cuda.synchronize()
+    return decode_pairs(y, Cout) if precision == 2 else y.cpu()
+
+
+def resample_prec(eng, op, x, precision):
+    """cd_op_resample_prec: op "avgpool" (precision 1, or 2 = split in and out, decoded) | "upsample" (precision 1); NCHW"""
+    B, Cc, H, W = x.shape
+    Ho, Wo = (H // 2, W // 2) if op == "avgpool" else (2 * H, 2 * W)
+    y = torch.empty((B * Ho * Wo, 2 * Cc), device="cuda", dtype=torch.float16) if precision == 2 else \
+        torch.empty((B, Cc, Ho, Wo), device="cuda", dtype=torch.float32)
+    xs = dev(x)
+    check(eng.lib.cd_op_resample_prec(eng.h, 0 if op == "avgpool" else 1, ptr(xs), B, Cc, H, W, precision, ptr(y)))
+    torch.cuda.synchronize()
+    if precision == 2:
+        return decode_pairs(y, Cc).reshape(B, Ho, Wo, Cc).permute(0, 3, 1, 2).contiguous()
+    return y.cpu()
+
+
 def layernorm(eng, x, gamma, beta, eps=1e-5):
     rows, Cc = x.shape
     y = torch.empty_like(x, device="cuda")
