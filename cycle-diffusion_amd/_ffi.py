@@ -99,6 +99,8 @@ SIGNATURES = {
     "cd_op_rows_prec": [_VP, _I, _VP, _I64, _I, _I, _VP, _I, _I, _VP, _VP, _I, _VP],
     "cd_op_resample_prec": [_VP, _I, _VP, _I, _I, _I, _I, _I, _VP],
     "cd_op_layernorm": [_VP, _VP, _I, _I, _VP, _VP, _F, _VP],
+    "cd_op_st_entry": [_VP, _VP, _I, _I, _I, _VP, _VP, _F, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP,
+                       C.POINTER(_I)],
     "cd_op_attention": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _I, _VP],
     "cd_op_cross_attention_ctrl": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _VP],
     "cd_op_lowpass": [_VP, _VP, _I, _I, _I, _I, _VP],

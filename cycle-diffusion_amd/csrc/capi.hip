@@ -5,6 +5,8 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <map>
+#include <utility>
 
 #include "engine.h"
 
@@ -79,6 +81,8 @@ struct cd_engine {
   std::vector<std::unique_ptr<Net>> nets;
   std::vector<ParamStore*> op_stores;  // storage behind cd_op_pack_conv
   ParamStore op_params;
+  // cd_op_st_entry: the derived q | k | v weights (plain, LayerNorm-folded) in op_params, one pair per (w_qk, w_v)
+  std::map<std::pair<const void*, const void*>, std::pair<ConvW*, ConvW*>> op_st_entry;
   ParamStore op_params_f32;  // fp32 rows (+ the three-term fp16 splits on the fp16 build) behind cd_op_pack_conv_weight_prec
   std::unique_ptr<KernelProfiler> prof;
   SplitKWorkspace splitk;  // split-K partial tiles + arrival counters of THIS engine's stream (conv_gemm.hip)
@@ -1278,6 +1282,48 @@ int cd_op_layernorm(cd_handle h, const float* x, int rows, int C, const float* g
   launch_nchw_to_nhwc(h->st, x, a, rows, C, 1, C, 1.f, 0.f, 0);
   launch_layernorm(h->st, a, C, o, C, rows, C, gamma, beta, eps);
   launch_nhwc_to_nchw(h->st, o, 0, C, y, rows, C, 1, 1.f, 0.f);
+  CD_API_END
+}
+
+int cd_op_st_entry(cd_handle h, const float* x, int B, int H, int W, const float* gn_gamma, const float* gn_beta,
+                   float gn_eps, const void* w_in, const float* b_in, const float* ln_gamma, const float* ln_beta,
+                   const void* w_qk, const void* w_v, const float* v_bias, int stages, float* h_out, float* qk_out,
+                   float* vt_out, int* stages_run) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && gn_gamma && gn_beta && w_in && ln_gamma && ln_beta && w_qk && w_v && h_out && qk_out && vt_out &&
+               B > 0 && H > 0 && W > 0, "bad argument");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  const int C = 320, T = H * W;
+  ConvW win = *(const ConvW*)w_in;
+  win.b = const_cast<float*>(b_in);
+  StEntryW w;
+  w.norm.g = const_cast<float*>(gn_gamma); w.norm.b = const_cast<float*>(gn_beta); w.norm.C = C; w.norm.eps = gn_eps;
+  w.ln1.g = const_cast<float*>(ln_gamma); w.ln1.b = const_cast<float*>(ln_beta); w.ln1.C = C;
+  w.proj_in = &win; w.qk1 = (const ConvW*)w_qk; w.v1 = (const ConvW*)w_v;
+  CD_CHECK(win.N == C && win.Cpad == C && w.qk1->N == 2 * C && w.qk1->Cpad == C && w.v1->N == C && w.v1->Cpad == C,
+           "transformer entry: 320-channel weights expected");
+  w.vbias = v_bias;
+  {  // storage of the derived weights: one pair per (w_qk, w_v) of this engine, refilled by every call (op weights live
+     // until the engine is destroyed, and the norm / bias vectors behind the same handles may differ from call to call)
+    const auto key = std::make_pair(w_qk, w_v);
+    auto it = h->op_st_entry.find(key);
+    if (it == h->op_st_entry.end()) {
+      st_entry_alloc(h->op_params, w);
+      it = h->op_st_entry.emplace(key, std::make_pair(w.qkv, w.qkv_ln)).first;
+    }
+    w.qkv = it->second.first; w.qkv_ln = it->second.second;
+  }
+  st_entry_refresh(h->st, w);
+  Act a = alloc_act(c, B, H, W, C);
+  launch_nchw_to_nhwc(h->st, x, a.p, B, C, T, C, 1.f, 0.f, 0);
+  if (stages < 0) stages = st_entry_stages();
+  const StEntryOut r = st_entry_fwd(c, w, a, stages);
+  if (stages_run) *stages_run = r.stages;
+  launch_nhwc_to_nchw(h->st, r.h.p, 0, r.h.ld, h_out, B, C, T, 1.f, 0.f);
+  launch_nhwc_to_nchw(h->st, r.qk.p, 0, r.qk.ld, qk_out, B, 2 * C, T, 1.f, 0.f);
+  launch_nhwc_to_nchw(h->st, r.vt, 0, r.Tpad, vt_out, B * C, r.Tpad, 1, 1.f, 0.f);  // [B][C][Tpad] as it is
   CD_API_END
 }
 

@@ -182,6 +182,44 @@ Act groupnorm_fwd(Ctx& c, const GNW& w, const Act& x, const Act* x2, bool silu, 
                   int film_ld = 0);
 struct LNW { float* g = nullptr; float* b = nullptr; int C = 0; };
 Act layernorm_fwd(Ctx& c, const LNW& w, const Act& x);
+// 16-bit path, single source, no SiLU / FiLM: the statistics passes of groupnorm_fwd without the apply pass. Returns the
+// per-image multiply-add coefficients [B][2][C] (al | be), valid until the next GroupNorm of this engine is launched
+const float* groupnorm_coef_fwd(Ctx& c, const GNW& w, const Act& x);
+
+// Entry of a SpatialTransformer block of the 320-channel level with d_head = 40 (16-bit path): GroupNorm -> proj_in ->
+// LayerNorm1 -> to_q | to_k -> V^T. On whole images of a multiple of 256 tokens and enough rows for the streaming kernel
+// (st_entry_available) the three norm / transpose launches run inside the two k_lin_stream launches:
+enum {
+  ST_ENTRY_QKV = 1,  // one q | k | v launch whose last 320 columns leave as V^T (no V^T GEMM); same bits
+  ST_ENTRY_LN1 = 2,  // ... with LayerNorm1 in its registers and its gain / bias in its weights (needs ST_ENTRY_QKV)
+  ST_ENTRY_GN = 4,   // GroupNorm's multiply-add applied in proj_in's registers (no apply pass); same bits
+};
+int st_entry_stages();  // CYCLEDIFF_ST_ENTRY (a bit per stage, default all), read once: A/B runs
+// where the launches are valid and sensible at all (whole images per strip, >= 32 768 rows); the norm1 fold is gated by
+// conv_ln_fold_available on top
+bool st_entry_available(const Ctx& c, int64_t rows, int hw);
+// where the U-Net takes them: the row counts at which the shipped tile table already runs proj_in and q | k on the streaming
+// kernel (tune_gfx950.txt: tile 30 for N = 320 and N = 640 from 61 440 rows of 64 x 64 tokens). Smaller forwards - the coupled
+// single batch's 49 152 rows among them - keep their tiles and their separate norm launches.
+constexpr int64_t kStEntryNetMinRows = 61440;
+struct StEntryW {
+  GNW norm; LNW ln1;
+  const ConvW *proj_in = nullptr, *qk1 = nullptr, *v1 = nullptr;
+  // derived, not declared as parameters (st_entry_refresh): [Wq*; Wk; Wv] fragment-major with a zero bias (or vbias for
+  // the value rows), and the same with LayerNorm1 folded in (W diag(gamma) rounded once, bias W beta)
+  ConvW *qkv = nullptr, *qkv_ln = nullptr;
+  const float* vbias = nullptr;  // tests only: to_v has no bias in the reference
+};
+void st_entry_alloc(ParamStore& ps, StEntryW& w);
+void st_entry_refresh(hipStream_t st, StEntryW& w);
+struct StEntryOut { Act h, qk; bf16_t* vt = nullptr; int Tpad = 0; int stages = 0; };  // stages: the bits that ran
+// V^T[b] = Wv . X[b]^T on the implicit-GEMM family: weights as the A operand, tokens as the B operand -> [B][C][Tpad]
+void vt_gemm_fwd(Ctx& c, const ConvW& wv, const bf16_t* x, int ldx, int B, int T, int Tpad, bf16_t* vt);
+// h = proj_in(GroupNorm(x)) [B*T][C]; then qk = [q (log2 units) | k] of LayerNorm1(h) [B*T][2C], vt [B][C][Tpad]
+// (arena-allocated: the caller brackets the second call with the mark its attention releases); st_entry_fwd = both
+Act st_entry_proj_in(Ctx& c, const StEntryW& w, const Act& x, int stages);
+StEntryOut st_entry_qkv(Ctx& c, const StEntryW& w, const Act& h, int stages);
+StEntryOut st_entry_fwd(Ctx& c, const StEntryW& w, const Act& x, int stages);
 
 // 2x2 average pool / nearest x2 upsample of a dense activation (resblock_updown, improved_ddpm/unet.py:104-135)
 Act avgpool2_fwd(Ctx& c, const Act& x);

@@ -436,6 +436,130 @@ Act groupnorm_fwd(Ctx& c, const GNW& w, const Act& x, const Act* x2, bool silu, 
   return y;
 }
 
+const float* groupnorm_coef_fwd(Ctx& c, const GNW& w, const Act& x) {
+  CD_CHECK(!c.f32 && !x.f32 && !x.split && x.C == w.C, "groupnorm coefficients: 16-bit single source of %d channels", w.C);
+  GroupNormParams p;
+  p.x = x.p; p.C0 = x.C; p.ld0 = x.ld;
+  p.B = x.B; p.HW = x.H * x.W; p.G = 32; p.eps = w.eps; p.gamma = w.g; p.beta = w.b;
+  p.no_apply = 1;
+  p.S = groupnorm_slabs(p.B, p.HW, x.C);
+  const size_t part_floats = round_up((size_t)p.B * p.S * p.G * 2, (size_t)64);
+  CD_CHECK(part_floats + (size_t)p.B * 2 * x.C <= c.gn_partial_floats, "groupnorm: workspace too small");
+  p.partial = c.gn_partial;
+  p.coef = c.gn_partial + part_floats;
+  if (x.stats && x.ld == x.C) p.pre0 = x.stats;
+  launch_groupnorm(c.st, p);
+  return p.coef;
+}
+
+// ------------------------------------------------------------------ entry of the 64 x 64 transformer blocks
+int st_entry_stages() {
+  static const int v = [] {
+    const char* e = getenv("CYCLEDIFF_ST_ENTRY");
+    int s = e && e[0] ? atoi(e) : (ST_ENTRY_QKV | ST_ENTRY_LN1 | ST_ENTRY_GN);
+    if (!(s & ST_ENTRY_QKV)) s &= ~ST_ENTRY_LN1;
+    return s;
+  }();
+  return v;
+}
+
+bool st_entry_available(const Ctx& c, int64_t rows, int hw) {
+  // whole images per 256-row strip, and at least half a round of the chip's CUs in strips: below that the persistent
+  // workgroups of the streaming kernel leave most of the chip idle. (Where the U-Net takes the launches is its own,
+  // narrower choice: kStEntryNetMinRows.)
+  return !c.f32 && rows >= 32768 && lin_stream_entry_supports(rows, hw, 320);
+}
+
+void st_entry_alloc(ParamStore& ps, StEntryW& w) {
+  if (!w.qk1 || !w.v1 || !w.qk1->wfrag || !w.v1->wfrag || w.qk1->Cpad != 320 || w.qk1->N != 640 || w.v1->N != 320) return;
+  w.qkv = ps.new_conv(960, 320, 1, 1, true);
+  w.qkv_ln = ps.new_conv(960, 320, 1, 1, true);
+}
+
+void st_entry_refresh(hipStream_t st, StEntryW& w) {
+  if (!w.qkv) return;
+  const size_t row = (size_t)320 * sizeof(bf16_t);
+  HIP_CHECK(hipMemcpyAsync(w.qkv->w, w.qk1->w, 640 * row, hipMemcpyDeviceToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(w.qkv->w + (size_t)640 * 320, w.v1->w, 320 * row, hipMemcpyDeviceToDevice, st));
+  HIP_CHECK(hipMemsetAsync(w.qkv->b, 0, 960 * sizeof(float), st));
+  if (w.vbias) HIP_CHECK(hipMemcpyAsync(w.qkv->b + 640, w.vbias, 320 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  launch_pack_wfrag(st, w.qkv->w, 320, w.qkv->wfrag, 960);
+  if (w.ln1.g && w.qkv_ln) {
+    launch_fold_ln(st, w.qkv->w, 320, w.ln1.g, w.ln1.b, w.qkv->b, w.qkv_ln->w, w.qkv_ln->b, 960, 320);
+    launch_pack_wfrag(st, w.qkv_ln->w, 320, w.qkv_ln->wfrag, 960);
+  }
+}
+
+// V^T[b] = Wv . X[b]^T : weights as the A operand, tokens as the B operand -> [B][C][Tpad]
+void vt_gemm_fwd(Ctx& c, const ConvW& wv, const bf16_t* x, int ldx, int B, int T, int Tpad, bf16_t* vt) {
+  ConvGemmParams p;
+  p.src0 = wv.w; p.C0 = wv.Cpad; p.ld0 = wv.Cpad;
+  p.B = 1; p.Hs = wv.N; p.Ws = 1; p.Hin = wv.N; p.Win = 1; p.Hout = wv.N; p.Wout = 1;
+  p.M = wv.N;
+  p.wgt = x; p.Ktot = wv.Cpad; p.N = T;
+  CD_CHECK(ldx == wv.Cpad, "vt_gemm: token row stride %d must equal K %d", ldx, wv.Cpad);
+  p.nbatch = B; p.a_bs = 0; p.w_bs = (int64_t)T * ldx; p.o_bs = (int64_t)wv.N * Tpad;
+  p.out = vt; p.out_ld = Tpad; p.zeros = c.zeros;
+  launch_conv_gemm(c.st, p);
+}
+
+int st_entry_effective(const Ctx& c, const StEntryW& w, const Act& x, int stages) {
+  const bool fused_ok = w.qkv && w.norm.C == 320 && x.C == 320 && x.ld == 320 && st_entry_available(c, x.rows(), x.H * x.W);
+  if (!fused_ok) stages = 0;
+  // norm1 folds where norm2 / norm3 do (CYCLEDIFF_LN_FOLD, its row threshold), and only into the q | k | v launch
+  if (!(stages & ST_ENTRY_QKV) || !w.qkv_ln || !conv_ln_fold_available(c, *w.qkv_ln, x.rows())) stages &= ~ST_ENTRY_LN1;
+  return stages;
+}
+
+Act st_entry_proj_in(Ctx& c, const StEntryW& w, const Act& x, int stages) {
+  const int B = x.B, T = x.H * x.W, C = w.norm.C;
+  ConvOpts p0; p0.pad = 0;
+  stages = st_entry_effective(c, w, x, stages);
+  Act h;
+  if (stages & ST_ENTRY_GN) {  // GroupNorm's statistics fold only; proj_in applies the coefficients to its A fragments
+    const float* coef = groupnorm_coef_fwd(c, w.norm, x);
+    h = alloc_act(c, B, x.H, x.W, C);
+    launch_lin_stream_gn(c.st, x.p, x.ld, (int)x.rows(), T, coef, w.proj_in->wfrag, w.proj_in->b, h.p, h.ld);
+  } else {
+    Act n = groupnorm_fwd(c, w.norm, x, nullptr, false);
+    h = conv_fwd(c, *w.proj_in, n, nullptr, p0);  // tokens [B*T][C]
+  }
+  return h;
+}
+
+StEntryOut st_entry_qkv(Ctx& c, const StEntryW& w, const Act& h, int stages) {
+  const int B = h.B, T = h.H * h.W, C = w.norm.C;
+  ConvOpts p0; p0.pad = 0;
+  stages = st_entry_effective(c, w, h, stages);
+  CD_CHECK(!w.vbias || (stages & ST_ENTRY_QKV), "transformer entry: a value bias needs the q | k | v launch");
+  StEntryOut r;
+  r.h = h;
+  r.stages = stages & ~ST_ENTRY_GN;
+  r.Tpad = round_up(T, 64);
+  if (stages & ST_ENTRY_QKV) {
+    r.qk = alloc_act(c, B, h.H, h.W, 2 * C);
+    r.vt = (bf16_t*)c.arena->alloc((size_t)B * C * r.Tpad * 2);  // T % 256 == 0: no padding columns to clear
+    const bool ln = (stages & ST_ENTRY_LN1) != 0;
+    Act a = ln ? r.h : layernorm_fwd(c, w.ln1, r.h);
+    const ConvW& wq = ln ? *w.qkv_ln : *w.qkv;
+    launch_lin_stream_qkv(c.st, a.p, a.ld, (int)a.rows(), T, wq.wfrag, wq.b, r.qk.p, r.vt, r.Tpad, ln, 1e-5f);
+    return r;
+  }
+  Act n1 = layernorm_fwd(c, w.ln1, r.h);
+  r.qk = conv_fwd(c, *w.qk1, n1, nullptr, p0);  // [B*T][2C]
+  r.vt = (bf16_t*)c.arena->alloc((size_t)B * C * r.Tpad * 2);
+  if (r.Tpad != T) HIP_CHECK(hipMemsetAsync(r.vt, 0, (size_t)B * C * r.Tpad * 2, c.st));
+  vt_gemm_fwd(c, *w.v1, n1.p, n1.ld, B, T, r.Tpad, r.vt);
+  return r;
+}
+
+StEntryOut st_entry_fwd(Ctx& c, const StEntryW& w, const Act& x, int stages) {
+  const int gn = st_entry_effective(c, w, x, stages) & ST_ENTRY_GN;
+  StEntryOut r = st_entry_qkv(c, w, st_entry_proj_in(c, w, x, stages), stages);
+  r.stages |= gn;  // (st_entry_qkv sees h, which has x's shape: the same gate)
+  return r;
+}
+
 Act avgpool2_fwd(Ctx& c, const Act& x) {
   if (x.split) {
     Act y = alloc_act(c, x.B, x.H / 2, x.W / 2, x.C);

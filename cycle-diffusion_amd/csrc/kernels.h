@@ -236,10 +236,27 @@ struct LinStreamParams {
   int M = 0, N = 0;
   float ln_eps = 1e-5f;  // LayerNorm-folded variants
   int geglu_direct = 0;  // GEGLU epilogue straight from the accumulators (no LDS transpose), lin_stream.hip
+  // V^T variants (the q | k | v projection of the 64 x 64 transformer blocks): packed columns [nsplit, N) leave
+  // untransposed into vt[row / hw][column - nsplit][vt_ld], token row % hw; nsplit % 64 == 0, hw % 256 == 0
+  int nsplit = 0, hw = 0;
+  bf16_t* vt = nullptr; int vt_ld = 0;
+  int64_t vt_bytes = 0;
+  // GroupNorm-applying variant (proj_in): a = pack(a * coef[row / hw][0][k] + coef[row / hw][1][k]) ahead of the product
+  const float* gn_coef = nullptr;
 };
 constexpr int kLinStreamTile = 30;
 bool lin_stream_supports(const ConvGemmParams& p);
 void launch_lin_stream(hipStream_t st, const ConvGemmParams& p);
+// The entry of a 64 x 64 transformer block on the streaming kernel. Both need whole images in every 256-row strip
+// (hw % 256 == 0) and 32-bit byte offsets: lin_stream_entry_supports().
+bool lin_stream_entry_supports(int64_t M, int hw, int lda);
+// qk[M][640] = a . W[0:640]^T + bias, vt[M / hw][320][vt_ld] = (a . W[640:960]^T + bias)^T per image; wfrag = the 960 rows
+// fragment-major, bias = 960 floats or null. ln_fold: the rows of a are LayerNorm-ed in registers (statistics only)
+void launch_lin_stream_qkv(hipStream_t st, const bf16_t* a, int lda, int M, int hw, const bf16_t* wfrag, const float* bias,
+                           bf16_t* qk, bf16_t* vt, int vt_ld, bool ln_fold, float ln_eps);
+// out[M][320] = pack(a * al + be) . W^T + bias with the per-image GroupNorm coefficients gn_coef[M / hw][2][320]
+void launch_lin_stream_gn(hipStream_t st, const bf16_t* a, int lda, int M, int hw, const float* gn_coef, const bf16_t* wfrag,
+                          const float* bias, bf16_t* out, int ldo);
 // w_out = w . diag(gamma) (16-bit), bias_out = bias + w . beta (fp32): the weights of a LayerNorm-folded layer
 void launch_fold_ln(hipStream_t st, const bf16_t* w, int ldw, const float* gamma, const float* beta, const float* bias,
                     bf16_t* w_out, float* bias_out, int N, int Kc);
@@ -301,6 +318,7 @@ struct GroupNormParams {
   // [B*HW/32][2][C]): when set, the stats pass is replaced by a small per-(image, group) fold
   const float* pre0 = nullptr;
   const float* pre1 = nullptr;
+  int no_apply = 0;  // 1: stop after the coefficients (the consumer applies them itself: lin_stream.hip's proj_in variant)
 };
 int groupnorm_slabs(int B, int HW, int C);
 void launch_groupnorm(hipStream_t st, const GroupNormParams& p);

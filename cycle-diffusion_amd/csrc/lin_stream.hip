@@ -104,11 +104,21 @@ __device__ __forceinline__ void touch4(u32x4& a, u32x4& b, u32x4& c, u32x4& d) {
 // LNF: LayerNorm folded in. The rows of A are normalised in registers when a strip's fragments become current - a lane
 // holds half of its row (160 values), the other half sits in lane ^ 32 - and the layer runs on weights that carry the
 // LayerNorm's gain and bias (k_fold_ln): y = ((x - mean) rstd) . (W gamma)^T + (b + W beta), attention.py:211-215.
-template <int ACT, bool RESID, bool STATS, bool LNF = false>
+//
+// VT: the column tiles at or above LinStreamParams::nsplit leave UNtransposed - the accumulators hold D^T, which is the
+// [channel][token] layout k_attention's d = 40 path reads its values in - into vt[image][channel][vt_ld]: the fused
+// q | k | v projection of the 64 x 64 transformer blocks (to_v has no V^T GEMM of its own). A strip lies inside one image
+// (hw % 256 == 0).
+// GNA: the GroupNorm apply ahead of proj_in. When a strip's fragments become current every value becomes
+// pack(x al[c] + be[c]) with the coefficients k_gn_fold left for the strip's image: k_gn_apply's expression on the
+// registers this kernel holds anyway. The coefficients are wave-uniform per (image, channel) and come through the scalar
+// cache, so they never enter the wave's in-order vector-memory count.
+template <int ACT, bool RESID, bool STATS, bool LNF = false, bool VT = false, bool GNA = false>
 __global__ __launch_bounds__(512, 2) void k_lin_stream(LinStreamParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr bool GEGLU = (ACT == ACT_GEGLU);
   static_assert(!(GEGLU && (RESID || STATS)), "GEGLU has neither residual nor statistics");
+  static_assert(!(VT && (GEGLU || RESID || STATS)) && !(GNA && (LNF || VT)), "entry variants are plain projections");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* wring = smem;
   char* aring = smem + OFF_A;
@@ -135,6 +145,8 @@ __global__ __launch_bounds__(512, 2) void k_lin_stream(LinStreamParams p) {
       __builtin_amdgcn_make_buffer_rsrc((void*)p.wfrag, 0, (unsigned)((size_t)p.N * K * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(
       (void*)p.out, 0, (unsigned)((size_t)p.M * p.ldo * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(VT ? p.vt : p.out), 0, VT ? (unsigned)p.vt_bytes : 0u, 0x00020000);
   u32x4 rs_r = {0u, 0u, 0u, 0x00020000u};
   if (RESID) {
     const uint64_t ra = (uint64_t)p.resid;
@@ -203,6 +215,37 @@ __global__ __launch_bounds__(512, 2) void k_lin_stream(LinStreamParams p) {
       for (int e = 0; e < 8; ++e) f[e] = __builtin_fmaf(f[e], rstd, nmr);
       af[ks] = __builtin_bit_cast(bf16x8, pack8_sat(f));
       __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // GroupNorm apply of the wave's 32 rows in place: lane = row, fragment ks holds channels 16 ks + 8 half .. + 8
+  auto gn_apply_rows = [&](int row0) __attribute__((always_inline)) {
+    typedef __attribute__((ext_vector_type(8))) float f32x8s;
+    const float* cf = p.gn_coef + (int64_t)(row0 / p.hw) * (2 * K);
+    const bool hi = (lane >> 5) != 0;
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks) {
+      float f[8], cc[2][8];
+#pragma unroll
+      for (int ab = 0; ab < 2; ++ab) {  // the multipliers, then the addends: 16 scalar registers at a time
+        f32x8s c0, c1;
+        if (ab == 0)
+          asm volatile("s_load_dwordx8 %0, %2, %3\n\ts_load_dwordx8 %1, %2, %4\n\ts_waitcnt lgkmcnt(0)"
+                       : "=&s"(c0), "=&s"(c1) : "s"(cf), "n"(ks * 64), "n"(ks * 64 + 32) : "memory");
+        else
+          asm volatile("s_load_dwordx8 %0, %2, %3\n\ts_load_dwordx8 %1, %2, %4\n\ts_waitcnt lgkmcnt(0)"
+                       : "=&s"(c0), "=&s"(c1) : "s"(cf), "n"(K * 4 + ks * 64), "n"(K * 4 + ks * 64 + 32) : "memory");
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          cc[ab][e] = hi ? c1[e] : c0[e];
+          asm volatile("" : "+v"(cc[ab][e]));  // selected here: the scalar registers are free for the next load
+        }
+      }
+      unpack8(__builtin_bit_cast(uint4, af[ks]), f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] = f[e] * cc[0][e] + cc[1][e];
+      af[ks] = __builtin_bit_cast(bf16x8, pack8(f));
+      asm volatile("" : "+v"(af[ks]));    // finished here, not sunk towards its first use behind the later loads
+      __builtin_amdgcn_sched_barrier(0);  // one fragment at a time, as in normalise_rows
     }
   };
   // copy one landed A piece into the NEXT-strip registers (only the 4 waves whose rows it holds)
@@ -293,6 +336,7 @@ __global__ __launch_bounds__(512, 2) void k_lin_stream(LinStreamParams p) {
   }
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) af[ks] = afn[ks];
+  if (GNA) gn_apply_rows((int)blockIdx.x * 256);
   if (LNF) normalise_rows();
 
   f32x16 acc[2];
@@ -324,6 +368,12 @@ __global__ __launch_bounds__(512, 2) void k_lin_stream(LinStreamParams p) {
     const int row0 = ((int)blockIdx.x + ord * G) * 256;
     const bool has_next = ord + 1 < my_count;
     const bool rows_ok = row0 + wave * 32 < p.M;
+    // VT: the strip's image and the wave's first token in it, as an element offset into vt
+    int vt_base = 0;
+    if (VT) {
+      const int img = row0 / p.hw;
+      vt_base = img * (p.N - p.nsplit) * p.vt_ld + (row0 - img * p.hw) + wave * 32;
+    }
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) { acc[0][r] = 0.f; acc[1][r] = 0.f; }
@@ -415,6 +465,36 @@ __global__ __launch_bounds__(512, 2) void k_lin_stream(LinStreamParams p) {
           }
           __builtin_amdgcn_sched_barrier(0);  // one register quad at a time
         }
+      } else if (VT && t * 64 >= p.nsplit) {
+        // V^T exit: the wave's 32 channels x 32 tokens go to its LDS stage CHANNEL-major (bias added on the way: a lane
+        // knows its 16 channels), and leave as 16-byte vectors of 8 consecutive tokens - pass ps covers channels
+        // (lane >> 2) + 16 ps, tokens 8 (lane & 3) .. + 8. The channel part of the address travels in the scalar offset.
+        const unsigned v_lane = (unsigned)((prow * p.vt_ld + pcol) * 2);
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+          __builtin_amdgcn_wave_barrier();
+          const int ncol0 = t * 64 + nb * 32;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const f32x4 bv = *(const f32x4*)(bias_s + ncol0 + 8 * q + 4 * half2);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) stage[(8 * q + 4 * half2 + j) * ST_LD + mi2] = acc[nb][4 * q + j] + bv[j];
+          }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_wave_barrier();
+#pragma unroll
+          for (int ps = 0; ps < 2; ++ps) {
+            const float* srow = stage + (prow + 16 * ps) * ST_LD + pcol;
+            const f32x4 lo = *(const f32x4*)srow, hi = *(const f32x4*)(srow + 4);
+            const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            if (rows_ok) {
+              const uint4 o = pack8_sat(v);
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs_v, v_lane,
+                                                     (vt_base + (ncol0 - p.nsplit + 16 * ps) * p.vt_ld) * 2, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
       } else {
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
@@ -503,6 +583,7 @@ __global__ __launch_bounds__(512, 2) void k_lin_stream(LinStreamParams p) {
     if (has_next) {
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) af[ks] = afn[ks];
+      if (GNA) gn_apply_rows(row0 + G * 256);
       if (LNF) normalise_rows();
     }
   }
@@ -539,10 +620,10 @@ __global__ void k_fold_ln(const bf16_t* __restrict__ w, int ldw, const float* __
   if (lane == 0) bias_out[n] = (bias ? bias[n] : 0.f) + acc;
 }
 
-template <int ACT, bool RESID, bool STATS, bool LNF = false>
+template <int ACT, bool RESID, bool STATS, bool LNF = false, bool VT = false, bool GNA = false>
 void launch_variant(hipStream_t st, const LinStreamParams& p, int grid) {
   static PerDeviceOnce attr_once;
-  auto kern = k_lin_stream<ACT, RESID, STATS, LNF>;
+  auto kern = k_lin_stream<ACT, RESID, STATS, LNF, VT, GNA>;
   attr_once([&]() {
     HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
   });
@@ -568,13 +649,7 @@ bool lin_stream_supports(const ConvGemmParams& p) {
   return true;
 }
 
-void launch_lin_stream(hipStream_t st, const ConvGemmParams& c) {
-  using namespace lin_detail;
-  CD_CHECK(lin_stream_supports(c), "lin_stream: unsupported problem (M %d N %d K %d)", c.M, c.N, c.Ktot);
-  LinStreamParams p;
-  p.a = c.src0; p.lda = c.ld0; p.wfrag = c.wgt_frag; p.bias = c.bias;
-  p.resid = c.resid; p.ldr = c.resid_ld; p.out = (bf16_t*)c.out; p.ldo = c.out_ld;
-  p.stats = c.stats; p.M = c.M; p.N = c.N;
+static int lin_stream_grid(int M) {
   static std::atomic<int> ncu_of[64];  // CU count per device (one persistent workgroup per CU)
   int dev = 0;
   HIP_CHECK(hipGetDevice(&dev));
@@ -585,8 +660,69 @@ void launch_lin_stream(hipStream_t st, const ConvGemmParams& c) {
     ncu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     ncu_of[dev & 63].store(ncu, std::memory_order_relaxed);
   }
-  const int nstrips = (p.M + 255) / 256;
-  const int grid = nstrips < ncu ? nstrips : ncu;
+  const int nstrips = (M + 255) / 256;
+  return nstrips < ncu ? nstrips : ncu;
+}
+
+namespace {
+// the per-launch timing launch_conv_gemm gives the launches that go through it (bench.py's roofline leg)
+struct ProfScope {
+  hipEvent_t e1 = nullptr; hipStream_t st;
+  ProfScope(hipStream_t s, int M, int N, const char* name) : st(s) {
+    KernelProfiler* prof = g_conv_prof;
+    if (!prof || !prof->enabled) return;
+    hipEvent_t e0 = nullptr;
+    char what[112] = "";
+    if (prof->verbose) snprintf(what, sizeof(what), "M%d N%d K320 k1 s1 z1 act0 | %s x1", M, N, name);
+    prof->next_pair(&e0, &e1, 2.0 * (double)M * (double)N * 320.0, what);
+    (void)hipEventRecord(e0, st);
+  }
+  ~ProfScope() { if (e1) (void)hipEventRecord(e1, st); }
+};
+}  // namespace
+
+bool lin_stream_entry_supports(int64_t M, int hw, int lda) {
+  return M > 0 && hw > 0 && hw % 256 == 0 && M % hw == 0 && lda % 8 == 0 && M * lda * 2 < (1ll << 31) &&
+         M * 640 * 2 < (1ll << 31);
+}
+
+void launch_lin_stream_qkv(hipStream_t st, const bf16_t* a, int lda, int M, int hw, const bf16_t* wfrag, const float* bias,
+                           bf16_t* qk, bf16_t* vt, int vt_ld, bool ln_fold, float ln_eps) {
+  using namespace lin_detail;
+  CD_CHECK(lin_stream_entry_supports(M, hw, lda) && vt_ld >= hw && vt_ld % 8 == 0 && a && wfrag && qk && vt,
+           "lin_stream: q | k | v^T projection on %d rows, %d tokens per image", M, hw);
+  LinStreamParams p;
+  p.a = a; p.lda = lda; p.wfrag = wfrag; p.bias = bias; p.out = qk; p.ldo = 2 * K;
+  p.M = M; p.N = 3 * K; p.nsplit = 2 * K; p.hw = hw;
+  p.vt = vt; p.vt_ld = vt_ld; p.vt_bytes = (int64_t)(M / hw) * K * vt_ld * 2;
+  CD_CHECK(p.vt_bytes < (1ll << 31), "lin_stream: V^T of %lld bytes", (long long)p.vt_bytes);
+  p.ln_eps = ln_eps;
+  const int grid = lin_stream_grid(M);
+  ProfScope prof(st, M, 3 * K, ln_fold ? "lin_stream q|k|v^T, LayerNorm folded" : "lin_stream q|k|v^T");
+  if (ln_fold) launch_variant<ACT_NONE, false, false, true, true>(st, p, grid);
+  else launch_variant<ACT_NONE, false, false, false, true>(st, p, grid);
+}
+
+void launch_lin_stream_gn(hipStream_t st, const bf16_t* a, int lda, int M, int hw, const float* gn_coef, const bf16_t* wfrag,
+                          const float* bias, bf16_t* out, int ldo) {
+  using namespace lin_detail;
+  CD_CHECK(lin_stream_entry_supports(M, hw, lda) && ldo % 8 == 0 && (int64_t)M * ldo * 2 < (1ll << 31) && a && wfrag &&
+               gn_coef && out, "lin_stream: GroupNorm-applying projection on %d rows, %d pixels per image", M, hw);
+  LinStreamParams p;
+  p.a = a; p.lda = lda; p.wfrag = wfrag; p.bias = bias; p.out = out; p.ldo = ldo;
+  p.M = M; p.N = K; p.hw = hw; p.gn_coef = gn_coef;
+  ProfScope prof(st, M, K, "lin_stream, GroupNorm applied");
+  launch_variant<ACT_NONE, false, false, false, false, true>(st, p, lin_stream_grid(M));
+}
+
+void launch_lin_stream(hipStream_t st, const ConvGemmParams& c) {
+  using namespace lin_detail;
+  CD_CHECK(lin_stream_supports(c), "lin_stream: unsupported problem (M %d N %d K %d)", c.M, c.N, c.Ktot);
+  LinStreamParams p;
+  p.a = c.src0; p.lda = c.ld0; p.wfrag = c.wgt_frag; p.bias = c.bias;
+  p.resid = c.resid; p.ldr = c.resid_ld; p.out = (bf16_t*)c.out; p.ldo = c.out_ld;
+  p.stats = c.stats; p.M = c.M; p.N = c.N;
+  const int grid = lin_stream_grid(p.M);
   // CYCLEDIFF_GEGLU_DIRECT=0 / 1 (A/B runs): the staged / the straight-from-the-accumulators GEGLU epilogue
   static const int geglu_direct = [] { const char* e = getenv("CYCLEDIFF_GEGLU_DIRECT"); return e && e[0] ? atoi(e) : kGegluDirectDefault; }();
   p.geglu_direct = geglu_direct;

@@ -360,6 +360,7 @@ void launch_groupnorm(hipStream_t st, const GroupNormParams& p) {
     hipLaunchKernelGGL(k_gn_stats, dim3(p.S, p.B), dim3(256), lds, st, p, rows_per_slab);
     hipLaunchKernelGGL(k_gn_coef, dim3(p.B), dim3(256), 0, st, p);
   }
+  if (p.no_apply) return;
   // ~2048 blocks per launch where the tensor allows it; at least one unrolled batch of rows per thread
   int rows_per_block = (int)(((int64_t)p.HW * p.B + 2047) / 2048);
   const int unit = 4 * rif;

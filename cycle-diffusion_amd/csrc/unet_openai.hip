@@ -36,6 +36,9 @@ struct STW {  // SpatialTransformer with one BasicTransformerBlock
   // LayerNorm-folded copies (320-channel level only): norm2 -> to_q of the cross-attention, norm3 -> the GEGLU
   // projection. Rebuilt from the loaded tensors whenever the parameter store changes (UNetOpenAI::refresh_ln_folds)
   ConvW *q2_ln = nullptr, *ff1_ln = nullptr;
+  // d_head = 40: the block's entry (norm -> proj_in -> norm1 -> q | k -> V^T) with its derived q | k | v weights, rebuilt
+  // with the LayerNorm folds (engine.h st_entry_fwd)
+  StEntryW entry;
   // context cache (step invariant)
   bf16_t* k2c = nullptr;  // [B*L][C]
   bf16_t* v2c = nullptr;  // [B*L][C] (token-major: k_attention transposes V tiles with LDS transpose reads)
@@ -157,6 +160,9 @@ int UNetOpenAI::add_st(const std::string& pfx, int C, int heads, int dh) {
     params.conv_rows(tb + ".attn1.to_q.weight", {C, C}, s.qk1, 0, C, 0, C, 0, qscale);
     params.conv_rows(tb + ".attn1.to_k.weight", {C, C}, s.qk1, C, C, 0, C, 0);
     s.v1 = make_conv(params, tb + ".attn1.to_v", C, C, 1, false, false, 2);
+    s.entry.norm = s.norm; s.entry.ln1 = s.ln1;
+    s.entry.proj_in = s.proj_in; s.entry.qk1 = s.qk1; s.entry.v1 = s.v1;
+    st_entry_alloc(params, s.entry);
   } else {
     s.qkv1 = params.new_conv(3 * C, C, 1, 1, false);
     params.conv_rows(tb + ".attn1.to_q.weight", {C, C}, s.qkv1, 0, C, 0, C, 0, qscale);
@@ -365,19 +371,6 @@ Act UNetOpenAI::res_fwd(Ctx& c, const ResW& r, const Act& x, const Act* x2, cons
   return out;
 }
 
-// V^T[b] = Wv . X[b]^T : weights as the A operand, tokens as the B operand -> [B][C][Tpad]
-static void vt_gemm(Ctx& c, const ConvW& wv, const bf16_t* x, int ldx, int B, int T, int Tpad, bf16_t* vt) {
-  ConvGemmParams p;
-  p.src0 = wv.w; p.C0 = wv.Cpad; p.ld0 = wv.Cpad;
-  p.B = 1; p.Hs = wv.N; p.Ws = 1; p.Hin = wv.N; p.Win = 1; p.Hout = wv.N; p.Wout = 1;
-  p.M = wv.N;
-  p.wgt = x; p.Ktot = wv.Cpad; p.N = T;
-  CD_CHECK(ldx == wv.Cpad, "vt_gemm: token row stride %d must equal K %d", ldx, wv.Cpad);
-  p.nbatch = B; p.a_bs = 0; p.w_bs = (int64_t)T * ldx; p.o_bs = (int64_t)wv.N * Tpad;
-  p.out = vt; p.out_ld = Tpad; p.zeros = c.zeros;
-  launch_conv_gemm(c.st, p);
-}
-
 void UNetOpenAI::set_context(Ctx& c, const bf16_t* ctx, int B, int L) {
   if (st_.empty()) return;
   if (B != ctx_B_ || L != ctx_L_) {
@@ -554,23 +547,26 @@ void UNetOpenAI::st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x, Act& o
   const float scale = 1.0f / sqrtf((float)s.dh);
   const bf16_t* k2c = s.k2c + (int64_t)b0 * ctx_L_ * C;
   const bf16_t* v2c = s.v2c + (int64_t)b0 * ctx_L_ * C;
-  Act n = groupnorm_fwd(c, s.norm, x_in, nullptr, false);
-  Act h = conv_fwd(c, *s.proj_in, n, nullptr, p0);  // tokens [B*T][C]
+  const int entry_stages = x_in.rows() >= kStEntryNetMinRows ? st_entry_stages() : 0;
+  Act h;
+  if (s.qkv1) {
+    Act n = groupnorm_fwd(c, s.norm, x_in, nullptr, false);
+    h = conv_fwd(c, *s.proj_in, n, nullptr, p0);  // tokens [B*T][C]
+  } else {  // d_head = 40: through V^T in two streaming launches where the shape allows it
+    h = st_entry_proj_in(c, s.entry, x_in, entry_stages);
+  }
   {  // self-attention
     const size_t m2 = c.arena->mark();
-    Act n1 = layernorm_fwd(c, s.ln1, h);
     Act a;
     if (s.qkv1) {
+      Act n1 = layernorm_fwd(c, s.ln1, h);
       Act qkv = conv_fwd(c, *s.qkv1, n1, nullptr, p0);  // [B*T][3C] = q (log2 units) | k | v
       a = attention_fwd(c, qkv.p, qkv.ld, qkv.p + C, qkv.ld, qkv.p + 2 * C, qkv.ld, B, s.heads, T, T, s.dh, scale,
                         x.H, x.W, /*q_log2=*/true);
     } else {
-      Act qk = conv_fwd(c, *s.qk1, n1, nullptr, p0);  // [B*T][2C]
-      const int Tpad = round_up(T, 64);
-      bf16_t* vt = (bf16_t*)c.arena->alloc((size_t)B * C * Tpad * 2);
-      if (Tpad != T) HIP_CHECK(hipMemsetAsync(vt, 0, (size_t)B * C * Tpad * 2, c.st));
-      vt_gemm(c, *s.v1, n1.p, n1.ld, B, T, Tpad, vt);
-      a = attention_vt_fwd(c, qk.p, qk.ld, qk.p + C, qk.ld, vt, B, s.heads, T, T, Tpad, s.dh, scale, x.H, x.W,
+      const StEntryOut ent = st_entry_qkv(c, s.entry, h, entry_stages);
+      const Act& qk = ent.qk;  // [B*T][2C]
+      a = attention_vt_fwd(c, qk.p, qk.ld, qk.p + C, qk.ld, ent.vt, B, s.heads, T, T, ent.Tpad, s.dh, scale, x.H, x.W,
                            /*q_log2=*/true);
     }
     ConvOpts o; o.pad = 0; o.resid = &h; o.out = h.p; o.out_ld = h.ld;  // in-place residual update:
@@ -662,7 +658,7 @@ Act UNetOpenAI::ab_fwd(Ctx& c, const ABW& a, const Act& x) {
   const int Tpad = round_up(T, 64);
   bf16_t* vt = (bf16_t*)c.arena->alloc((size_t)B * C * Tpad * 2);
   if (Tpad != T) HIP_CHECK(hipMemsetAsync(vt, 0, (size_t)B * C * Tpad * 2, c.st));
-  vt_gemm(c, *a.v, n.p, n.ld, B, T, Tpad, vt);
+  vt_gemm_fwd(c, *a.v, n.p, n.ld, B, T, Tpad, vt);
   Act o = alloc_act(c, B, x.H, x.W, C);
   AttnParams p;
   p.q = qk.p; p.k = qk.p + C; p.vt = vt; p.o = o.p;
@@ -705,6 +701,7 @@ void UNetOpenAI::refresh_ln_folds(Ctx& c) {
     for (const Layer& l : b.layers)
       if (l.kind == Layer::UP_CONV) params.refresh_up_phase(c.st, l.conv);
   for (STW& s : st_) {
+    st_entry_refresh(c.st, s.entry);
     if (!s.q2_ln) continue;
     struct { const ConvW* src; ConvW* dst; const LNW* ln; } jobs[2] = {{s.q2, s.q2_ln, &s.ln2}, {s.ff1, s.ff1_ln, &s.ln3}};
     for (auto& j : jobs) {

@@ -380,6 +380,21 @@ int cd_op_rows_prec(cd_handle h, int op, const float* x0, int64_t rows, int C0, 
 int cd_op_resample_prec(cd_handle h, int op, const float* x, int B, int C, int H, int W, int precision, void* y);
 int cd_op_layernorm(cd_handle h, const float* x, int rows, int C, const float* gamma, const float* beta,
                     float eps, float* y);
+/* the entry of a 320-channel SpatialTransformer block with 40-wide heads on the 16-bit path, as the U-Net runs it:
+ * x fp32 NCHW [B,320,H,W] -> h = proj_in(GroupNorm32(x)) (h_out, NCHW [B,320,H,W]), [q | k] = [to_q | to_k](LayerNorm(h))
+ * (qk_out, NCHW [B,640,H,W]) and V^T = to_v(LayerNorm(h))^T per image (vt_out, [B][320][round_up(H*W, 64)]). w_in, w_qk
+ * ([to_q rows; to_k rows], 640 x 320) and w_v are handles of cd_op_pack_conv_weight; every other pointer is fp32 device
+ * memory (b_in, v_bias may be NULL). stages: bit 0 = one q | k | v launch of the streaming kernel with a V^T exit, bit 1 =
+ * LayerNorm folded into it (needs bit 0), bit 2 = the GroupNorm apply inside proj_in's launch; -1 = what CYCLEDIFF_ST_ENTRY
+ * says (default 7). Shapes the fused launches do not take (H*W % 256 != 0, fewer rows than the streaming kernel's
+ * threshold of 32 768; bit 1 also where CYCLEDIFF_LN_FOLD / CYCLEDIFF_LN_FOLD_MIN_ROWS keep the other LayerNorm folds off)
+ * run the separate launches whatever `stages` says; *stages_run (may be NULL) receives the bits whose launches ran.
+ * v_bias needs bit 0 in effect. The two derived 960 x 320 weights are allocated once per (engine, w_qk, w_v) and live, like
+ * every op weight, until the engine is destroyed; each call refills them. */
+int cd_op_st_entry(cd_handle h, const float* x, int B, int H, int W, const float* gn_gamma, const float* gn_beta,
+                   float gn_eps, const void* w_in, const float* b_in, const float* ln_gamma, const float* ln_beta,
+                   const void* w_qk, const void* w_v, const float* v_bias, int stages, float* h_out, float* qk_out,
+                   float* vt_out, int* stages_run);
 /* q [B,Tq,H*D], k,v [B,Tk,H*D] fp32 -> o [B,Tq,H*D]; use_transpose_kernel: 0 = V consumed token-major (the U-Net
    path: fused q|k|v projection, LDS transpose reads), 1 = V pre-transposed to [B,H,D,Tk_pad] first */
 int cd_op_attention(cd_handle h, const float* q, const float* k, const float* v, int B, int H, int Tq,
