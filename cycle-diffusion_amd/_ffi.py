@@ -107,6 +107,7 @@ SIGNATURES = {
     "cd_op_softmax_rows": [_VP, _VP, _I64, _I, _VP],
     "cd_op_timestep_embedding": [_VP, _VP, _I, _I, _I, _VP],
     "cd_op_sched_step": [_VP, _I, _I, _VP, _VP, _VP, _VP, _I, _F, _VP, _VP, _I, _I, _I, _I, _VP],
+    "cd_op_gauss": [_VP, _U64, C.c_uint32, _I64, _I64, _VP],
     "cd_op_sched_step_masked": [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, _VP, _VP, _I, _I, _F, _F, _VP, _I, _I, _I, _I, _VP, _I],
     "cd_op_bench_conv": [_VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float)],
     "cd_op_bench_mfma_sustained": [_VP, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)],

@@ -391,6 +391,17 @@ struct MaskArgs {
   uint64_t seed = 0;
 };
 
+// The generator's streams are banded by loop, 4096 streams to a band (tests/_philox_ref.py STREAMS):
+// 0 x_T and 1 + i the encoder, 0x1000 + i the decode, 0x2000 / 0x2001 + i the refinement, 0x3000 + j the inversion,
+// 0x4000 + slot the keep-mask's q-sample, 0x5000 + i ILVR's reference, 0x7a65 the VAE posterior. A loop that draws from the
+// generator (`noise` is NULL) may not walk into the next loop's numbers; a noise tensor has no such limit.
+constexpr int kStreamBandSteps = 0xFFF;
+void check_stream_band(const void* noise, int steps, const char* what) {
+  CD_CHECK(noise || steps <= kStreamBandSteps,
+           "%s = NULL draws from the counter-based generator, whose stream band holds at most %d steps of one loop (got %d): "
+           "pass the noise tensor", what, kStreamBandSteps, steps);
+}
+
 void check_mask_args(const MaskArgs& m, UNet* u, int sched_kind, int B, bool coupled) {
   CD_CHECK(sched_kind == CD_SCHED_DDIM, "a keep-mask is only defined for sched_kind = CD_SCHED_DDIM (the reference has no mask "
                                         "hook on DDPMDDIMWrapper)");
@@ -623,6 +634,7 @@ int cd_dpm_encode(cd_handle h, int net, int sched_kind, const float* x0, const f
   enter_engine(h);
   // K = 0: only x_T is drawn (white_box_steps = -1 of the text wrappers: every decode step then draws fresh noise)
   CD_CHECK(h && x0 && coef_host && z_out && B > 0 && K >= 0, "bad argument");
+  check_stream_band(noise, K, "cd_dpm_encode: noise");
   ArenaScope arena_scope(h->arena);
   SamplerState s = setup_sampler(h, net, ctx_c, ctx_uc, ctx_len, guidance, B);
   // the 'ddpm' posterior kernels carry no classifier-free-guidance combine (the pixel DDPMs that use them are unconditional,
@@ -653,6 +665,8 @@ static void ddim_decode_impl(cd_handle h, int net, int sched_kind, const float* 
                              int B, int K, const cd_step_coef* coef_host, const float* noise_tail, uint64_t seed,
                              float* x_out, const MaskArgs* mk = nullptr) {
   CD_CHECK(h && z && coef_host && x_out && B > 0 && K > 0 && n_eps <= z_slots - 1, "bad argument");
+  check_stream_band(noise_tail, K, "decode: noise_tail");
+  if (mk && mk->source == CD_MASK_QSAMPLE) check_stream_band(mk->noise, K, "keep-mask: mask_noise");
   if (mk) check_mask_args(*mk, get_unet(h, net), sched_kind, B, /*coupled=*/false);
   ArenaScope arena_scope(h->arena);
   SamplerState s = setup_sampler(h, net, ctx_c, ctx_uc, ctx_len, guidance, B);
@@ -779,6 +793,8 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
                        uint64_t seed, int last_uses_x0, float* z_out, float* x_out, const MaskArgs* mk,
                        const CtrlArgs* ck = nullptr) {
   CD_CHECK(h && x0 && coef_enc_host && coef_dec_host && z_out && x_out && B > 0 && n_dec > 0 && K > 0, "bad argument");
+  check_stream_band(noise, K, "cd_cycle_translate: noise");
+  if (mk && mk->source == CD_MASK_QSAMPLE) check_stream_band(mk->noise, K, "keep-mask: mask_noise");
   ArenaScope arena_scope(h->arena);
   UNet* u = get_unet(h, net);
   const int Bd = B * n_dec;
@@ -980,6 +996,7 @@ int cd_pix_refine(cd_handle h, int net, int sched_kind, float* x, int B, int R, 
   CD_API_BEGIN
   enter_engine(h);
   CD_CHECK(h && x && coef_host && B > 0 && R > 0, "bad argument");
+  check_stream_band(noise, R, "cd_pix_refine: noise");
   ArenaScope arena_scope(h->arena);
   SamplerState s = setup_sampler(h, net, nullptr, nullptr, 0, 1.f, B);
   StepArgs& a = s.args;
@@ -1035,6 +1052,8 @@ int cd_ilvr_decode(cd_handle h, int net, int sched_kind, const float* z, int z_s
   CD_API_BEGIN
   enter_engine(h);
   CD_CHECK(h && z && coef_host && x_out && ref && B > 0 && K > 0 && n_eps <= z_slots - 1, "bad argument");
+  check_stream_band(noise_tail, K, "cd_ilvr_decode: noise_tail");
+  check_stream_band(ref_noise, K, "cd_ilvr_decode: ref_noise");
   UNet* u = get_unet(h, net);
   CD_CHECK(!(u->desc.use_spatial_transformer && u->desc.context_dim > 0),
            "ILVR runs on an unconditional pixel DDPM: this network takes a text context");
@@ -1448,6 +1467,18 @@ int cd_op_sched_step(cd_handle h, int mode, int sched_kind, const cd_step_coef* 
   if (mode == 0) launch_init_xt(h->st, a);
   else if (mode == 1) launch_encode_step(h->st, sched_kind, a);
   else launch_decode_step(h->st, sched_kind, a);
+  HIP_CHECK(hipStreamSynchronize(h->st));
+  CD_API_END
+}
+
+// n draws of the counter-based generator, elements first .. first + n - 1 of (seed, stream), as the kernels take them
+int cd_op_gauss(cd_handle h, uint64_t seed, uint32_t stream, int64_t first, int64_t n, float* out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && out && first >= 0 && n >= 0 && first <= INT64_MAX - n, "bad argument");
+  GaussSrc g;
+  g.seed = seed; g.stream = stream;
+  if (n > 0) launch_gauss_fill(h->st, g, first, out, n);
   HIP_CHECK(hipStreamSynchronize(h->st));
   CD_API_END
 }

@@ -3,30 +3,12 @@
 #include "common.h"
 #include <mutex>
 
+#include "gauss.h"
 #include "kernels.h"
 
 namespace cd {
 
 namespace {
-
-__device__ inline void philox_round2(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
-  uint32_t hi0 = __umulhi(M0, c[0]), lo0 = M0 * c[0];
-  uint32_t hi1 = __umulhi(M1, c[2]), lo1 = M1 * c[2];
-  uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-  c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-}
-__device__ inline float philox_normal2(uint64_t seed, uint32_t stream, uint64_t idx) {
-  uint32_t c[4] = {(uint32_t)(idx >> 1), (uint32_t)(idx >> 33), stream, 0x9E3779B9u};
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int i = 0; i < 10; ++i) { philox_round2(c, k0, k1); k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-  float u1 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  float u2 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  float rad = sqrtf(-2.0f * __logf(u1));
-  float ang = 6.28318530717958647692f * u2;
-  return (idx & 1) ? rad * __sinf(ang) : rad * __cosf(ang);
-}
 
 __global__ void k_nchw_to_nhwc(const float* __restrict__ x, bf16_t* __restrict__ y, int B, int C,
                                int HW, int Cpad, float scale, float shift, int dup) {
@@ -264,7 +246,7 @@ __global__ void k_posterior_sample(const float* __restrict__ mom, int ld, const 
       float lv = m[zc + c];
       lv = fminf(fmaxf(lv, -30.0f), 20.0f);       // distributions.py:30
       const float sd = expf(0.5f * lv);           // distributions.py:33
-      const float nz = noise ? noise[i] : philox_normal2(seed, 0x7a65u, (uint64_t)i);
+      const float nz = noise ? noise[i] : philox_normal(seed, 0x7a65u, (uint64_t)i);
       v = mean + sd * nz;                         // distributions.py:36
     }
     z[i] = scale * v;                             // ddpm.py:543 scale_factor * z

@@ -1,12 +1,14 @@
-// Standard-normal draws of the scheduler kernels: the tensor the caller passed, or a counter-based generator.
-// Included by the kernels that draw (sched.hip, ilvr.hip); fp contraction is off from here to the end of the including file.
+// Standard-normal draws of the kernels that take noise: the tensor the caller passed, or a counter-based generator.
+// Included by every kernel that draws (sched.hip, ilvr.hip, elementwise.hip): ONE definition, so that a draw is the same
+// number whichever kernel makes it. philox_normal switches fp contraction off for its own body only, and takes its logarithm
+// from the builtin at that place: the compiler expands it into log2(x) times ln 2 in two parts, and under contraction - which
+// the header's __logf wrapper inherits from the including file - it fuses the last add of that expansion and gives another last
+// bit (the copy elementwise.hip once had did). The including file's own arithmetic keeps its setting.
 #pragma once
 #include "common.h"
 #include "kernels.h"
 
 namespace cd {
-
-#pragma clang fp contract(off)
 
 // ---------------- counter-based RNG (Philox4x32-10 + Box-Muller) for throughput runs ----------
 __device__ inline void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
@@ -17,6 +19,7 @@ __device__ inline void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) 
   c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
 }
 __device__ inline float philox_normal(uint64_t seed, uint32_t stream, uint64_t idx) {
+#pragma clang fp contract(off)
   // one normal per (stream, idx): counter = (idx/2, stream), Box-Muller pair selected by idx&1
   uint32_t c[4] = {(uint32_t)(idx >> 1), (uint32_t)(idx >> 33), stream, 0x9E3779B9u};
   uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
@@ -27,7 +30,7 @@ __device__ inline float philox_normal(uint64_t seed, uint32_t stream, uint64_t i
   }
   float u1 = ((float)(c[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
   float u2 = ((float)(c[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-  float rad = sqrtf(-2.0f * __logf(u1));
+  float rad = sqrtf(-2.0f * __builtin_logf(u1));  // what __logf returns, with this body's contraction setting
   float ang = 6.28318530717958647692f * u2;
   return (idx & 1) ? rad * __sinf(ang) : rad * __cosf(ang);
 }

@@ -82,6 +82,8 @@ void launch_encode_step(hipStream_t st, int kind, const StepArgs& a);
 void launch_decode_step(hipStream_t st, int kind, const StepArgs& a, const MaskBlend* mk = nullptr, bool blend = false);
 // a.xt <- blend(a.xt) ahead of the first forward; uses a.geom and a.xin beside it
 void launch_mask_blend_init(hipStream_t st, const StepArgs& a, const MaskBlend& mk);
+// out[i] = the draw of element first + i from g, i < n (cd_op_gauss: the generator as the tests see it)
+void launch_gauss_fill(hipStream_t st, GaussSrc g, int64_t first, float* out, int64_t n);
 
 // ---------------------------------------------------------------- ILVR low-pass conditioning (ilvr.hip)
 // A resize matrix M [n_out, n_in] as its nonzero taps: row i is w[t * n_out + i] at column first[i] + t, t = 0 .. P-1

@@ -243,4 +243,17 @@ void launch_mask_blend_init(hipStream_t st, const StepArgs& a, const MaskBlend& 
   hipLaunchKernelGGL(k_mask_blend_init, ew_grid(a.geom), dim3(256), 0, st, a.xt, mk, a.geom, a.xin);
 }
 
+// out[i] = draw(g, first + i): the draws of gauss.h as every kernel above takes them, laid bare for the tests (cd_op_gauss)
+__global__ void k_gauss_fill(GaussSrc g, int64_t first, float* out, int64_t n) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    out[i] = draw(g, first + i);
+  }
+}
+
+void launch_gauss_fill(hipStream_t st, GaussSrc g, int64_t first, float* out, int64_t n) {
+  const int64_t nb = (n + 255) / 256;
+  hipLaunchKernelGGL(k_gauss_fill, dim3((unsigned)(nb > 2048 ? 2048 : (nb < 1 ? 1 : nb))), dim3(256), 0, st, g, first, out, n);
+}
+
 }  // namespace cd

@@ -651,6 +651,12 @@ class Engine:
         check(self.lib.cd_op_lowpass(self.h, ptr(x), B, Cc, R, int(down_n), ptr(y)))
         return y
 
+    def gauss(self, seed, stream, n, first=0):
+        """cd_op_gauss: the n draws first .. first + n - 1 of Philox(seed, stream), as every noise=None path takes them"""
+        out = torch.empty((int(n),), device=self.device, dtype=torch.float32)
+        check(self.lib.cd_op_gauss(self.h, C.c_uint64(seed), C.c_uint32(stream), int(first), int(n), ptr(out)))
+        return out
+
     def pix_refine(self, net, kind, x, coef, noise=None, seed=0):
         x = self._f32(x).clone()
         R = len(coef) - 1

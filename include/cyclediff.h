@@ -415,6 +415,11 @@ int cd_op_timestep_embedding(cd_handle h, const float* t, int B, int dim, int mo
 int cd_op_sched_step(cd_handle h, int mode, int sched_kind, const cd_step_coef* coef_host, const float* x0,
                      float* xt, const float* eps_hat, int cfg, float guidance, const float* noise,
                      const float* eps_in, int is_last, int B, int C, int HW, float* z_slot);
+/* n raw draws of the counter-based Gaussian generator every sampler falls back to when its noise pointer is NULL
+ * (Philox4x32-10 + Box-Muller, csrc/gauss.h): out[i] = the draw of element first + i of (seed, stream), fp32 device, i < n.
+ * The stream of every loop is tabulated in DESIGN.md section 3; a loop that draws refuses more than 4095 steps, the width
+ * of its band. `first` reaches the element indices around 2^32 and 2^33 with a handful of elements. */
+int cd_op_gauss(cd_handle h, uint64_t seed, uint32_t stream, int64_t first, int64_t n, float* out);
 /* the masked step kernels on explicit tensors (bit-exact checks). mode 0: x <- blend(x) (the blend ahead of the first forward);
  * mode 2: the CD_SCHED_DDIM decode step of cd_op_sched_step followed, when blend != 0, by the blend. src [B_mask,C,HW] is x0
  * (CD_MASK_QSAMPLE: src_k = qa*x0 + qb*mask_noise, mask_noise [B,C,HW] required) or the source latent itself (CD_MASK_ENCODER);
