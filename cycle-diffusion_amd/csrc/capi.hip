@@ -393,7 +393,8 @@ struct MaskArgs {
 
 // The generator's streams are banded by loop, 4096 streams to a band (tests/_philox_ref.py STREAMS):
 // 0 x_T and 1 + i the encoder, 0x1000 + i the decode, 0x2000 / 0x2001 + i the refinement, 0x3000 + j the inversion,
-// 0x4000 + slot the keep-mask's q-sample, 0x5000 + i ILVR's reference, 0x7a65 the VAE posterior. A loop that draws from the
+// 0x4000 + slot the keep-mask's q-sample, 0x5000 + i ILVR's reference, 0x6000 + i the keep-mask estimate's draws, 0x7a65 the
+// VAE posterior. A loop that draws from the
 // generator (`noise` is NULL) may not walk into the next loop's numbers; a noise tensor has no such limit.
 constexpr int kStreamBandSteps = 0xFFF;
 void check_stream_band(const void* noise, int steps, const char* what) {
@@ -1106,6 +1107,99 @@ int cd_ilvr_decode(cd_handle h, int net, int sched_kind, const float* z, int z_s
   CD_API_END
 }
 
+}  // extern "C"
+
+// ---- keep-mask estimation (csrc/automask.hip)
+namespace {
+// the parameters cd_automask and cd_op_automask_reduce share, each refused by name
+void check_automask_params(int n_draws, float ratio, float thr, int dilate) {
+  CD_CHECK(n_draws >= 1 && n_draws <= kStreamBandSteps, "keep-mask estimate: n_draws must lie in [1, %d] (the width of its stream "
+                                                        "band), got %d", kStreamBandSteps, n_draws);
+  CD_CHECK(ratio > 0.f, "keep-mask estimate: ratio must be > 0, got %g", (double)ratio);
+  CD_CHECK(thr >= 0.f && thr < 1.f, "keep-mask estimate: thr must lie in [0, 1), got %g", (double)thr);
+  CD_CHECK(dilate >= 0 && dilate <= kAutoMaskMaxDilate, "keep-mask estimate: dilate must lie in [0, %d], got %d",
+           kAutoMaskMaxDilate, dilate);
+}
+}  // namespace
+
+extern "C" {
+
+// The keep-mask of DiffEdit's first step: n_draws noised copies of x0 at one level, the network under the source and under the
+// target context on each (one x_t per pair: the second half of the input is the copy of the first), and the reduction of
+// automask.hip over |e_tgt - e_src|. The forward is cd_unet_forward's call on those rows; draws that do not fit max_rows rows
+// run in further forwards and keep adding into the same per-pixel sums in draw order.
+int cd_automask(cd_handle h, int net, const float* x0, const float* ctx_src, const float* ctx_tgt, int ctx_len, int B,
+                int n_draws, int t, float qa, float qb, const float* noise, uint64_t seed, int max_rows, float ratio, float thr,
+                int dilate, float* map_out, float* keep_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x0 && ctx_src && ctx_tgt && keep_out && B > 0 && ctx_len > 0, "bad argument");
+  UNet* u = get_unet(h, net);
+  CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer && u->desc.context_dim > 0,
+           "cd_automask: the estimate compares two text contexts; this network has no text context (a pixel network)");
+  check_automask_params(n_draws, ratio, thr, dilate);
+  CD_CHECK(max_rows >= 2 * B, "cd_automask: max_rows = %d holds no draw of a batch of %d (2 * B rows each)", max_rows, B);
+  const int C = u->desc.in_channels, R = u->image_size, HW = R * R, Co = u->out_channels, Dc = u->desc.context_dim;
+  CD_CHECK(Co == C, "cd_automask: the network predicts %d channels for %d input channels", Co, C);
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  AutoMaskArgs m;
+  m.B = B; m.C = C; m.H = R; m.W = R;
+  m.sb = (int64_t)HW * Co; m.sc = 1; m.sp = Co;  // the network's NHWC output
+  m.n_total = n_draws; m.ratio = ratio; m.thr = thr; m.dilate = dilate;
+  m.nblk = automask_sum_blocks(HW);
+  m.acc = (float*)h->arena.alloc((size_t)B * HW * 4);
+  m.partial = (float*)h->arena.alloc((size_t)B * m.nblk * 4);
+  m.map_out = map_out; m.keep_out = keep_out;
+  const size_t buffers = h->arena.mark();
+  const int per_fwd = std::min(n_draws, std::max(1, max_rows / (2 * B)));
+  const int64_t per_draw = (int64_t)B * C * HW;
+  const size_t esz = u->f32 ? 4 : 2;
+  AutoMaskNoised q;
+  q.x0 = x0; q.qa = qa; q.qb = qb; q.seed = seed; q.B = B; q.C = C; q.HW = HW;
+  bf16_t* xin = nullptr;
+  float *eh = nullptr, *tvec = nullptr;
+  int cur = 0;  // draws the buffers and the network's context are laid out for
+  for (int i0 = 0; i0 < n_draws; i0 += per_fwd) {
+    const int nc = std::min(per_fwd, n_draws - i0), rows = 2 * nc * B;
+    if (nc != cur) {  // the first forward, and a shorter last one
+      h->arena.release(buffers);
+      const size_t half = (size_t)B * ctx_len * Dc;
+      bf16_t* cx = (bf16_t*)h->arena.alloc((size_t)rows * ctx_len * Dc * esz);
+      for (int j = 0; j < 2 * nc; ++j) {  // [c_src x nc | c_tgt x nc], converted as make_ctx converts them
+        const float* from = j < nc ? ctx_src : ctx_tgt;
+        if (u->f32) HIP_CHECK(hipMemcpyAsync((float*)cx + j * half, from, half * 4, hipMemcpyDeviceToDevice, h->st));
+        else launch_nchw_to_nhwc(h->st, from, cx + j * half, B * ctx_len, Dc, 1, Dc, 1.f, 0.f, 0);
+      }
+      u->set_context(c, cx, rows, ctx_len);
+      xin = (bf16_t*)h->arena.alloc((size_t)rows * HW * u->in_cpad * esz);
+      if (!u->f32) HIP_CHECK(hipMemsetAsync(xin, 0, (size_t)rows * HW * u->in_cpad * esz, h->st));  // the pad channels
+      eh = (float*)h->arena.alloc((size_t)rows * HW * Co * 4);
+      tvec = (float*)h->arena.alloc((size_t)rows * 4);
+      launch_fill_f32(h->st, tvec, (float)t, rows);
+      q.xq = u->f32 ? (float*)h->arena.alloc((size_t)nc * per_draw * 4) : nullptr;
+      q.xin.xin = u->f32 ? nullptr : xin; q.xin.cpad = u->in_cpad; q.xin.dup = 1;
+      cur = nc;
+    }
+    q.n_draws = nc;
+    q.noise = noise ? noise + (int64_t)i0 * per_draw : nullptr;
+    q.stream0 = (uint32_t)(0x6000 + i0);
+    launch_automask_qsample(h->st, q);
+    if (u->f32)  // the fp32 networks' layout pass, once per half
+      for (int half = 0; half < 2; ++half)
+        launch_nchw_to_nhwc_f32(h->st, q.xq, (float*)xin + (size_t)half * nc * B * HW * u->in_cpad, nc * B, C, HW, u->in_cpad,
+                                1.f, 0.f, u->x3 ? 1 : 0, h->overflow_dev);
+    UNetIO io; io.xin = xin; io.B = rows; io.t_explicit = tvec; io.t_shared = false; io.out = eh; io.out_ld = Co;
+    u->forward(c, io);
+    m.e_src = eh; m.e_tgt = eh + (int64_t)nc * B * m.sb;
+    m.n_chunk = nc; m.first = i0 == 0 ? 1 : 0;
+    launch_automask_accum(h->st, m);
+    h->pacer.tick(h->st);
+  }
+  launch_automask_finish(h->st, m);
+  CD_API_END
+}
+
 // ------------------------------------------------------------------ single-kernel entry points
 int cd_op_pack_conv_weight(cd_handle h, const float* w_host, int N, int Cin, int KH, int KW, int geglu,
                            void** packed_dev, int* Npad, int* Cpad) {
@@ -1479,6 +1573,31 @@ int cd_op_gauss(cd_handle h, uint64_t seed, uint32_t stream, int64_t first, int6
   GaussSrc g;
   g.seed = seed; g.stream = stream;
   if (n > 0) launch_gauss_fill(h->st, g, first, out, n);
+  HIP_CHECK(hipStreamSynchronize(h->st));
+  CD_API_END
+}
+
+// the reduction of cd_automask on caller-built predictions, fp32 [n, B, C, H, W] each
+int cd_op_automask_reduce(cd_handle h, const float* eps_src, const float* eps_tgt, int n, int B, int C, int H, int W,
+                          float ratio, float thr, int dilate, float* map_out, float* mean_out, float* keep_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && eps_src && eps_tgt && keep_out && B > 0 && C > 0 && H > 0 && W > 0, "bad argument");
+  check_automask_params(n, ratio, thr, dilate);
+  ArenaScope arena_scope(h->arena);
+  const int HW = H * W;
+  AutoMaskArgs m;
+  m.B = B; m.C = C; m.H = H; m.W = W;
+  m.e_src = eps_src; m.e_tgt = eps_tgt;
+  m.sb = (int64_t)C * HW; m.sc = HW; m.sp = 1;  // NCHW view
+  m.n_chunk = m.n_total = n; m.first = 1;
+  m.ratio = ratio; m.thr = thr; m.dilate = dilate;
+  m.nblk = automask_sum_blocks(HW);
+  m.acc = (float*)h->arena.alloc((size_t)B * HW * 4);
+  m.partial = (float*)h->arena.alloc((size_t)B * m.nblk * 4);
+  m.map_out = map_out; m.mean_out = mean_out; m.keep_out = keep_out;
+  launch_automask_accum(h->st, m);
+  launch_automask_finish(h->st, m);
   HIP_CHECK(hipStreamSynchronize(h->st));
   CD_API_END
 }

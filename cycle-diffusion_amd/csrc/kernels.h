@@ -118,6 +118,43 @@ void build_lowpass_taps(int n_in, int n_out, std::vector<float>& w, std::vector<
 void launch_ilvr_down(hipStream_t st, const IlvrArgs& a);
 void launch_ilvr_up_add(hipStream_t st, const IlvrArgs& a);
 
+// ---------------------------------------------------------------- keep-mask estimation (automask.hip)
+// x_i = qa*x0 + qb*n_i for n_draws draws of one forward: rows (i, b) of its input, i-major
+struct AutoMaskNoised {
+  const float* x0 = nullptr;     // [B, C, HW]
+  float qa = 1.f, qb = 0.f;
+  const float* noise = nullptr;  // [n_draws, B, C, HW], or null -> Philox(seed, stream0 + i), element = the flat index in [B, C, HW]
+  uint64_t seed = 0;
+  uint32_t stream0 = 0;
+  int n_draws = 0, B = 0, C = 0, HW = 0;
+  XinOut xin;                    // 16-bit NHWC [n_draws * B (twice with dup), HW, cpad], or null
+  float* xq = nullptr;           // fp32 NCHW [n_draws * B, C, HW], or null
+};
+constexpr int kAutoMaskMaxDilate = 8;
+struct AutoMaskArgs {
+  // accumulate: element (i, b, c, p) of either prediction at [(i * B + b) * sb + c * sc + p * sp]
+  const float* e_src = nullptr;
+  const float* e_tgt = nullptr;
+  int64_t sb = 0, sc = 0, sp = 0;
+  int n_chunk = 0;         // draws in this launch
+  int first = 0;           // 1: acc starts from 0, else from what lies there
+  float* acc = nullptr;    // [B, HW]: sum over draws and channels of |e_tgt - e_src|
+  int B = 0, C = 0, H = 0, W = 0;
+  // finish: map = acc / float(n_total * C)
+  int n_total = 0;
+  float ratio = 3.f, thr = 0.5f;
+  int dilate = 0;
+  float* partial = nullptr;   // [B, nblk] block sums of map, nblk = automask_sum_blocks(H * W)
+  int nblk = 0;
+  float* map_out = nullptr;   // [B, HW] or null
+  float* mean_out = nullptr;  // [B] or null
+  float* keep_out = nullptr;  // [B, HW], exact 0 / 1 (1 = keep the source)
+};
+int automask_sum_blocks(int HW);
+void launch_automask_qsample(hipStream_t st, const AutoMaskNoised& a);
+void launch_automask_accum(hipStream_t st, const AutoMaskArgs& a);
+void launch_automask_finish(hipStream_t st, const AutoMaskArgs& a);  // the per-image sum, then threshold / dilation / output
+
 // ---------------------------------------------------------------- implicit-GEMM conv / GEMM (conv_gemm.hip)
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_GEGLU = 3, ACT_QGELU = 4, ACT_RELU = 5 };  // QGELU: x*sigmoid(1.702x) (CLIP)
 // RELU: max(x, 0) (the BasicConv2d units of the FID Inception-v3, inception.hip)

@@ -657,6 +657,44 @@ class Engine:
         check(self.lib.cd_op_gauss(self.h, C.c_uint64(seed), C.c_uint32(stream), int(first), int(n), ptr(out)))
         return out
 
+    def automask(self, net, x0, ctx_src, ctx_tgt, t, qa, qb, n_draws=10, noise=None, seed=0, max_rows=None, ratio=3.0,
+                 thr=0.5, dilate=0, want_map=True):
+        """cd_automask: the keep-mask of DiffEdit's first step. x0 [B, C, H, W] noised n_draws times to the level (t, qa, qb),
+        the network under ctx_src and under ctx_tgt [B, L, Dc] on each, map = mean |e_tgt - e_src| over draws and channels,
+        clipped at ratio x the image's own mean, thresholded and dilated -> (keep [B, 1, H, W] of 0 / 1 with 1 = keep the
+        source, map [B, 1, H, W] or None). noise [n_draws, B, C, H, W] or None (Philox(seed), stream 0x6000 + i); max_rows:
+        rows of one forward (default: all 2 * n_draws * B)."""
+        x0 = self._f32(x0)
+        B, Cc, H, W = x0.shape
+        cs, ct = self._f32(ctx_src), self._f32(ctx_tgt)
+        if cs.dim() != 3 or cs.shape[0] != B or tuple(ct.shape) != tuple(cs.shape):
+            raise ValueError("contexts must both be [%d, L, Dc], got %s and %s" % (B, tuple(cs.shape), tuple(ct.shape)))
+        if noise is not None:
+            noise = self._f32(noise)
+            if tuple(noise.shape) != (int(n_draws), B, Cc, H, W):
+                raise ValueError("noise must be %s, got %s" % ((int(n_draws), B, Cc, H, W), tuple(noise.shape)))
+        keep = torch.empty((B, 1, H, W), device=x0.device, dtype=torch.float32)
+        mp = torch.empty_like(keep) if want_map else None
+        max_rows = 2 * int(n_draws) * B if max_rows is None else int(max_rows)
+        check(self.lib.cd_automask(self.h, net, ptr(x0), ptr(cs), ptr(ct), cs.shape[1], B, int(n_draws), int(t), C.c_float(qa),
+                                   C.c_float(qb), ptr(noise), C.c_uint64(seed), max_rows, C.c_float(ratio), C.c_float(thr),
+                                   int(dilate), ptr(mp), ptr(keep)))
+        self._keep = (x0, cs, ct, noise)  # the launches read them asynchronously
+        return keep, mp
+
+    def op_automask_reduce(self, eps_src, eps_tgt, ratio=3.0, thr=0.5, dilate=0):
+        """cd_op_automask_reduce: the reduction of automask() on fp32 [n, B, C, H, W] predictions -> (keep, map [B, 1, H, W],
+        mean [B])"""
+        es, et = self._f32(eps_src), self._f32(eps_tgt)
+        if es.dim() != 5 or tuple(es.shape) != tuple(et.shape):
+            raise ValueError("predictions must both be [n, B, C, H, W], got %s and %s" % (tuple(es.shape), tuple(et.shape)))
+        n, B, Cc, H, W = es.shape
+        keep = torch.empty((B, 1, H, W), device=es.device, dtype=torch.float32)
+        mp, mean = torch.empty_like(keep), torch.empty((B,), device=es.device, dtype=torch.float32)
+        check(self.lib.cd_op_automask_reduce(self.h, ptr(es), ptr(et), n, B, Cc, H, W, C.c_float(ratio), C.c_float(thr),
+                                             int(dilate), ptr(mp), ptr(mean), ptr(keep)))
+        return keep, mp, mean
+
     def pix_refine(self, net, kind, x, coef, noise=None, seed=0):
         x = self._f32(x).clone()
         R = len(coef) - 1

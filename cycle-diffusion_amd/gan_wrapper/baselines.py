@@ -18,7 +18,7 @@ None of these classes has a translate(): Model.forward runs encode() then forwar
 """
 import torch
 
-from .. import _ffi, schedule
+from .. import _ffi, auto_mask, schedule
 from .ddpm_ddim_wrapper import DDPMDDIMWrapper
 from .latent_text_wrapper import LatentDiffStochasticTextWrapper, SDStochasticTextWrapper
 
@@ -86,6 +86,7 @@ class _LatentDDIBText(_LatentBaseline):
             raise ValueError("DDIB is deterministic: n_trials must be 1, got %r" % (n_trials,))
         # the inversion is the whole chain (skip_steps shortens it); cross-attention control needs the coupled loop's source rows
         _reject("DDIB", white_box_steps=white_box_steps, cac_steps=kw.pop("cac_steps", None), cac_mode=kw.pop("cac_mode", None))
+        auto_mask.refuse(kw, "DDIB")
         kw.setdefault("encoder_unconditional_guidance_scales", [1.0])
         kw.setdefault("decoder_unconditional_guidance_scales", [1.0])
         super().__init__(source_model_type, custom_steps, 0.0, -1, list(skip_steps), n_trials=1, couple=False, **kw)
@@ -135,6 +136,7 @@ class _LatentSDEditText(_LatentBaseline):
         _reject("SDEdit", skip_steps=skip_steps, white_box_steps=white_box_steps,
                 encoder_unconditional_guidance_scales=encoder_unconditional_guidance_scales,
                 cac_steps=kw.pop("cac_steps", None), cac_mode=kw.pop("cac_mode", None))
+        auto_mask.refuse(kw, "SDEdit")
         kw.setdefault("decoder_unconditional_guidance_scales", [1.0])
         super().__init__(source_model_type, custom_steps, eta, -1, [0], encoder_unconditional_guidance_scales=[1.0],
                          n_trials=n_trials or 1, couple=False, **kw)
@@ -270,6 +272,7 @@ class DDPMILVRWrapper(_NoCoupledLoop, DDPMDDIMWrapper):
         from ..utils import lowpass
         from .ddpm_ddim_wrapper import MODEL_TYPES, _desc
         _reject("ILVR", sdedit_strengths=sdedit_strengths, skip_steps=skip_steps, white_box_steps=white_box_steps)
+        auto_mask.refuse(kw, "ILVR")
         for name, v, lo in (("ilvr_down_n", ilvr_down_n, 1), ("ilvr_range_t", ilvr_range_t, 0)):
             if isinstance(v, bool) or not isinstance(v, int) or v < lo:
                 raise ValueError("%s must be an integer >= %d, got %r" % (name, lo, v))

@@ -17,7 +17,7 @@ import os
 
 import torch
 
-from .. import _ffi, schedule
+from .. import _ffi, auto_mask, schedule
 from ..engine import afhq_iddpm_desc, ho_ddpm_desc
 from ..runtime import get_engine, load_or_init_weights
 
@@ -53,8 +53,11 @@ class DDPMDDIMWrapper(torch.nn.Module):
 
     def __init__(self, source_model_type, sample_type, custom_steps, es_steps, source_model_path=None,
                  refine_steps=0, refine_iterations=1, eta=None, t_0=None, enforce_class_input=None, device=None,
-                 noise_on_cpu=False, precision="fp32", net_desc=None, allow_lossy_ddim=False):
+                 noise_on_cpu=False, precision="fp32", net_desc=None, allow_lossy_ddim=False, **auto_mask_keys):
         super().__init__()
+        auto_mask.refuse(auto_mask_keys, "%s (gan_type DDPM_DDIM and the pixel baselines)" % type(self).__name__)
+        if auto_mask_keys:
+            raise TypeError("unexpected [gan] keys %s" % sorted(auto_mask_keys))
         if str(precision) not in PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(PRECISIONS))
         self.precision = str(precision)

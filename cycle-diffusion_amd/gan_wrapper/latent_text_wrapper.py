@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import _ffi, attn_control, schedule
+from .. import auto_mask as am
 from ..engine import kl_f8_vae_desc, ldm_text_unet_desc, sd_v1_unet_desc
 from ..runtime import get_engine, load_or_init_weights, read_checkpoint, synthetic_allowed
 
@@ -44,6 +45,16 @@ class StandInTextEmbedder:
             out.append(torch.randn(self.length, self.context_dim, generator=g))
         return torch.stack(out, 0)
 
+
+class LatentMask:
+    """A keep-mask that is latent already, [B, 1, h, w] in [0, 1]: `mask=LatentMask(m)` passes it to forward() / translate()
+    without the block mean a pixel-space mask goes through."""
+
+    def __init__(self, m):
+        self.m = torch.as_tensor(m)
+
+
+AUTO_MASK = object()  # in the place of a mask inside the wrappers: estimate it from the two prompts (`[gan] auto_mask`)
 
 TEXT_PRECISIONS = {"fp16": _ffi.CD_PREC_16, "16": _ffi.CD_PREC_16, "fp32": _ffi.CD_PREC_F32, "fp32x3": _ffi.CD_PREC_F32X3}
 
@@ -67,8 +78,14 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                  encoder_unconditional_guidance_scales=None, decoder_unconditional_guidance_scales=None,
                  n_trials=None, cond_stage=None, ranker=None, device=None, text_encoder=None,
                  noise_on_cpu=False, fold_ensemble=True, ranker_path=None, precision="fp16", couple=True,
-                 mask_source="q_sample", cac_steps=0.0, cac_mode="refine"):
+                 mask_source="q_sample", cac_steps=0.0, cac_mode="refine", auto_mask=None, auto_mask_draws=10,
+                 auto_mask_strength=0.5, auto_mask_ratio=3.0, auto_mask_threshold=0.5, auto_mask_dilate=0, auto_mask_seed=0):
         super().__init__()
+        # `[gan] auto_mask = diffedit` (default none): translate() / forward() without a `mask=` estimate the keep-mask from the
+        # two prompts (the keys: auto_mask.py) and take the masked path with it; an explicit `mask=` wins
+        self.auto_mask_opts = am.AutoMaskOptions(auto_mask, auto_mask_draws, auto_mask_strength, auto_mask_ratio,
+                                                 auto_mask_threshold, auto_mask_dilate, auto_mask_seed)
+        self.last_auto_mask = self.last_auto_map = None
         # `[gan] cac_steps` (0 = off, the default): cross-attention control (prompt-to-prompt on the coupled loop)
         # on the first int(cac_steps * K) of the K decode steps a member runs; `cac_mode = refine | replace`: how the target
         # prompt's tokens are matched to the source's (attn_control.build_control)
@@ -296,13 +313,56 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
     # ---- keep-mask (sample_with_eps(mask=, x0=), ddim.py:427-430)
     def _latent_mask(self, mask, bsz):
         """pixel-space [B, 1, R, R] in [0, 1] (1 = keep the source) -> latent [B, 1, R/f, R/f]: the f x f block mean, f the
-        first stage's down-sampling factor; not thresholded - the blend is linear in m, a feathered mask stays feathered"""
+        first stage's down-sampling factor; not thresholded - the blend is linear in m, a feathered mask stays feathered.
+        A LatentMask is latent already and passes as it is."""
+        if isinstance(mask, LatentMask):
+            if tuple(mask.m.shape) != (bsz, 1, self.image_size, self.image_size):
+                raise ValueError("latent mask must be [%d, 1, %d, %d], got %s" % (bsz, self.image_size, self.image_size,
+                                                                                  tuple(mask.m.shape)))
+            return mask.m.to(self.device, torch.float32).contiguous()
         mask = torch.as_tensor(mask).to(self.device, torch.float32)
         if mask.dim() != 4 or tuple(mask.shape) != (bsz, 1, self.resolution, self.resolution):
             raise ValueError("mask must be [%d, 1, %d, %d], got %s" % (bsz, self.resolution, self.resolution, tuple(mask.shape)))
         if bool((mask < 0).any()) or bool((mask > 1).any()):
             raise ValueError("mask values must lie in [0, 1] (1 = keep the source)")
         return torch.nn.functional.avg_pool2d(mask, self.vae_factor).contiguous()
+
+    # ---- keep-mask estimated from the two prompts (DESIGN.md 16)
+    def _auto_mask_on(self):
+        o = getattr(self, "auto_mask_opts", None)
+        return o is not None and o.on
+
+    def auto_mask_level(self):
+        """(t, qa, qb) of the estimate's level: row k = am.level_index(strength, S) of this wrapper's own schedule"""
+        sch = self._schedule()
+        k = am.level_index(self.auto_mask_opts.strength, len(sch))
+        qa, qb = sch.coef_qsample(0)[k]
+        return int(sch.coef_decode(0)["t"][k]), float(qa), float(qb)
+
+    def auto_mask(self, x0, encode_text, decode_text):
+        """keep [B, 1, h, w] (exact 0 / 1, 1 = keep the source) and map [B, 1, h, w] of the latent x0 [B, C, h, w] under the
+        two prompts, by the `auto_mask_*` keys whatever `auto_mask` itself says. The draws come from the counter-based
+        generator (auto_mask_seed), never from torch's: nothing else draws differently for it."""
+        bsz = x0.shape[0]
+        c_src, _ = self.get_condition(encode_text, bsz)
+        c_tgt, _ = self.get_condition(decode_text, bsz)
+        return self._auto_mask_ctx(x0, c_src, c_tgt)
+
+    def _auto_mask_ctx(self, x0, c_src, c_tgt):
+        o = self.auto_mask_opts
+        t, qa, qb = self.auto_mask_level()
+        # rows of one forward as the other calls bound them: MAX_FOLD samples of a guided call, COUPLE_MAX_TOKENS tokens
+        max_rows = max(2, min(2 * self.MAX_FOLD, self.couple_max_tokens // self.image_size ** 2))
+        per = max(1, max_rows // 2)  # samples per call (a sample's draw index is its place in its call)
+        keeps, maps = [], []
+        for i in range(0, x0.shape[0], per):
+            k, m = self.engine.automask(self.unet, x0[i:i + per].contiguous(), c_src[i:i + per].contiguous(),
+                                        c_tgt[i:i + per].contiguous(), t, qa, qb, n_draws=o.draws, seed=o.seed,
+                                        max_rows=max_rows, ratio=o.ratio, thr=o.threshold, dilate=o.dilate)
+            keeps.append(k)
+            maps.append(m)
+        self.last_auto_mask, self.last_auto_map = torch.cat(keeps, 0), torch.cat(maps, 0)
+        return self.last_auto_mask, self.last_auto_map
 
     def _mask_draws(self, K, bsz, n_eps=None):
         """the K q_sample draws of ONE sample_with_eps(mask=) call in its own order (randn_like(x0) at the top of every step,
@@ -414,7 +474,11 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         `mask` (pixel-space [B, 1, R, R] in [0, 1], 1 = keep the source): the region-keeping edit, see _translate_masked;
         without one every call below is the unmasked path's.
         `attn_ctrl` (a prebuilt (M, alpha, w) of attn_control.build_control) or `[gan] cac_steps > 0`: cross-attention control,
-        see _translate_ctrl; with cac_steps = 0 and no attn_ctrl nothing below changes."""
+        see _translate_ctrl; with cac_steps = 0 and no attn_ctrl nothing below changes.
+        `[gan] auto_mask = diffedit` without a `mask`: the keep-mask is estimated from the two prompts on the x0 the masked
+        path works on (auto_mask()) and that path runs with it; with auto_mask = none nothing below changes."""
+        if mask is None and self._auto_mask_on():
+            mask = AUTO_MASK
         if attn_ctrl is not None or self.cac_steps > 0:
             return self._translate_ctrl(image, encode_text, decode_text, mask, attn_ctrl)
         if mask is not None:
@@ -467,7 +531,7 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         like the rest."""
         sch = self._schedule()
         bsz = image.shape[0]
-        m = self._latent_mask(mask, bsz)
+        m = None if mask is AUTO_MASK else self._latent_mask(mask, bsz)  # AUTO_MASK: estimated below, once x0 exists
         encoder = self.mask_source == "encoder"
         whole = all(self._white_box_loop(len(sch) - sk, sk) == len(sch) - sk for sk in self.skip_steps)
         dec_scales = [float(sc) for sc in self.decoder_unconditional_guidance_scales]
@@ -491,6 +555,8 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
             coupled = bool(self.couple and whole and fits)
         self.last_translate_coupled = coupled
         x0, c_src, uc, members = self._encode_front(image, encode_text)
+        if m is None:
+            m = self._auto_mask_ctx(x0, c_src, self.get_condition(decode_text, bsz)[0])[0]
         if not coupled:
             z_ensemble = self._encode_members(x0, c_src, uc, members)
             return self._select(self.generate(z_ensemble, decode_text, mask=m, x0=x0), image, encode_text, decode_text)
@@ -566,8 +632,8 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                                                            for sc in self.encoder_unconditional_guidance_scales):
             raise ValueError("cross-attention control: every decoder scale must ride in the coupled loop (all guided, or one "
                              "unguided scale) and no scale may be 0 - the control acts on conditional rows")
-        m = self._latent_mask(mask, bsz) if mask is not None else None
-        encoder = m is not None and self.mask_source == "encoder"
+        m = self._latent_mask(mask, bsz) if mask is not None and mask is not AUTO_MASK else None
+        encoder = mask is not None and self.mask_source == "encoder"
         enc_cfg = any(self._kind(float(sc)) == "cfg" for sc in self.encoder_unconditional_guidance_scales)
         rows1 = (2 if enc_cfg else 1) + len(ride) * (2 if main == "cfg" else 1)  # rows of one sample of one member
         tokens = self.image_size ** 2
@@ -582,6 +648,8 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
             raise ValueError("attn_ctrl must carry one control per sample (%d), got %d" % (bsz, ctl[0].shape[0]))
         x0, c_src, uc, members = self._encode_front(image, encode_text)
         c_tgt, _ = self.get_condition(decode_text, bsz)
+        if mask is AUTO_MASK:
+            m = self._auto_mask_ctx(x0, c_src, c_tgt)[0]
         mask_noise = {}
         if m is not None and not encoder:  # the reference's order: every member encoded, then member -> decoder scale, K draws
             for i, mem in enumerate(members):
@@ -637,17 +705,21 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         if getattr(self, "cac_steps", 0.0) > 0:
             raise ValueError("cac_steps > 0 needs translate(): in encode() + forward() the source rows whose attention maps the "
                              "control injects no longer exist; use translate(image, encode_text, decode_text)")
+        if mask is None and self._auto_mask_on():
+            mask = AUTO_MASK  # estimated below on the re-encoded x0
         if mask is None:
             return self._select(self.generate(z_ensemble, decode_text), original_img, encode_text, decode_text)
         if self.mask_source == "encoder":
             raise ValueError("mask_source = 'encoder' needs translate(): in encode() + forward() the encoder's trajectory no "
                              "longer exists; use translate(image, encode_text, decode_text, mask=) or mask_source = q_sample")
         bsz = z_ensemble[0].shape[0]
-        m = self._latent_mask(mask, bsz)
+        m = None if mask is AUTO_MASK else self._latent_mask(mask, bsz)
         img = ((original_img - 0.5) * 2.0).to(self.device, torch.float32)
         per = self._vae_batch()
         x0 = torch.cat([self.engine.vae_encode(self.vae, img[i:i + per], sample=False, scale=self.SCALE_FACTOR)
                         for i in range(0, bsz, per)], 0)
+        if m is None:
+            m = self.auto_mask(x0, encode_text, decode_text)[0]
         return self._select(self.generate(z_ensemble, decode_text, mask=m, x0=x0), original_img, encode_text, decode_text)
 
     def _select(self, img_ensemble, original_img, encode_text, decode_text):

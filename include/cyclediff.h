@@ -301,6 +301,26 @@ int cd_ilvr_decode(cd_handle h, int net, int sched_kind, const float* z, int z_s
                    int down_n, int range_t, const float* qsample_coef_host, const float* ref_noise, uint64_t ref_seed,
                    float* x_out);
 
+/* Keep-mask estimation from the two prompts (DiffEdit, Couairon et al. 2022, step 1; no counterpart in the reference tree,
+ * DESIGN.md 16): where do the noise predictions under the source and under the target context disagree on the noised source?
+ *     x_i = qa*x0 + qb*n_i (fp32, in that order), i < n_draws; one forward over rows [src (i, b) | tgt (i, b)] at timestep t
+ *     (cd_unet_forward's call on those rows; the second half of its input is the copy of the first);
+ *     map[b, p]  = (sum_i sum_c |e_tgt[i,b,c,p] - e_src[i,b,c,p]|) / float(n_draws * C)   (i ascending, c ascending inside)
+ *     mean[b]    = (sum_p map[b, p]) / HW per image (fixed order, independent of B);  cl = ratio * mean[b]
+ *     v = min(map, cl) / cl (0 where cl == 0);  edit = v > thr;  edit' = max of edit over |dy|, |dx| <= dilate inside the image
+ *     keep_out [B,1,H,W] = 1 - edit' (exact 0 / 1; 1 = keep the source, the orientation of `mask` everywhere);
+ *     map_out [B,1,H,W] or NULL.
+ *   x0 [B,C,H,W]; ctx_src / ctx_tgt [B,L,Dc]; (t, qa, qb): the level - qa / qb as a row of cd_ddim_decode_masked's q-sample
+ *   table, t its timestep; noise [n_draws,B,C,H,W] or NULL -> Philox(seed), stream 0x6000 + i, element = the flat index in
+ *   [B,C,H,W]. max_rows: the most rows a forward may have; max(1, max_rows / (2B)) draws run per forward, and the result does not
+ *   depend on that cut, bit for bit. Classifier-free guidance needs no rows here: eps_g(tgt) - eps_g(src) = g (e_c(tgt) -
+ *   e_c(src)) for one x_t, and the division by the image's own mean cancels g. Any precision of the network.
+ * Refused (error text, nothing launched): networks without a text context (the pixel DDPMs), n_draws outside [1, 4095],
+ * ratio <= 0, thr outside [0, 1), dilate outside [0, 8], max_rows < 2B. */
+int cd_automask(cd_handle h, int net, const float* x0, const float* ctx_src, const float* ctx_tgt, int ctx_len, int B,
+                int n_draws, int t, float qa, float qb, const float* noise, uint64_t seed, int max_rows, float ratio, float thr,
+                int dilate, float* map_out, float* keep_out);
+
 /* Stochastic refinement (ddpm_ddim_wrapper.py:431-453): x_t = sa*x + s1a*n (row R of coef_host),
  * then R random-noise steps rows R-1..0. noise [R+1,B,C,H,W] or NULL. In/out x [B,C,H,W]. */
 int cd_pix_refine(cd_handle h, int net, int sched_kind, float* x, int B, int R,
@@ -420,6 +440,10 @@ int cd_op_sched_step(cd_handle h, int mode, int sched_kind, const cd_step_coef* 
  * The stream of every loop is tabulated in DESIGN.md section 3; a loop that draws refuses more than 4095 steps, the width
  * of its band. `first` reaches the element indices around 2^32 and 2^33 with a handful of elements. */
 int cd_op_gauss(cd_handle h, uint64_t seed, uint32_t stream, int64_t first, int64_t n, float* out);
+/* the reduction of cd_automask (the same kernels) on caller-built predictions: eps_src / eps_tgt fp32 device [n,B,C,H,W] ->
+ * map_out [B,1,H,W] (or NULL), mean_out [B] (or NULL), keep_out [B,1,H,W]; refused as cd_automask refuses n, ratio, thr, dilate */
+int cd_op_automask_reduce(cd_handle h, const float* eps_src, const float* eps_tgt, int n, int B, int C, int H, int W,
+                          float ratio, float thr, int dilate, float* map_out, float* mean_out, float* keep_out);
 /* the masked step kernels on explicit tensors (bit-exact checks). mode 0: x <- blend(x) (the blend ahead of the first forward);
  * mode 2: the CD_SCHED_DDIM decode step of cd_op_sched_step followed, when blend != 0, by the blend. src [B_mask,C,HW] is x0
  * (CD_MASK_QSAMPLE: src_k = qa*x0 + qb*mask_noise, mask_noise [B,C,HW] required) or the source latent itself (CD_MASK_ENCODER);

@@ -81,6 +81,11 @@ def folded_calls(model, batches, fold, seed, device):
             kw.update(mask=batch["mask"].to(device))
         with torch.no_grad():
             (orig, img), _loss, _ = model(**kw)
+        if "mask" not in batch:  # `[gan] auto_mask`: the keep-mask the wrapper estimated for this call, as pixels
+            for w in wrappers:
+                if getattr(getattr(w, "auto_mask_opts", None), "on", False) and w.last_auto_mask is not None:
+                    f = w.vae_factor  # nearest x f: every latent pixel becomes its f x f block
+                    batch["auto_keep"] = w.last_auto_mask.repeat_interleave(f, 2).repeat_interleave(f, 3).cpu()
         yield batch, orig, img
 
 
@@ -110,6 +115,9 @@ def main(argv=None):
     ap.add_argument("--fid_inception", default=None,
                     help="Inception-v3 state_dict for FID / KID (pytorch-fid pt_inception-2015-12-05-*.pth; default "
                          "CYCLEDIFF_FID_INCEPTION, or seeded synthetic weights with --synthetic-weights)")
+    ap.add_argument("--save_masks", action="store_true",
+                    help="`[gan] auto_mask = diffedit`: also write every sample's estimated keep-mask, upsampled to the image "
+                         "(white = kept), as <id>_mask.png beside its image")
     ap.add_argument("--text_metrics", action="store_true",
                     help="text tasks: per-sample CLIP and directional CLIP (evaluation/translate_text.py) on the unclamped "
                          "outputs; ViT-B/32 weights from CYCLEDIFF_CLIP_RANKER")
@@ -191,6 +199,16 @@ def main(argv=None):
                 for k, sel in (("psnr_keep", keep_px), ("psnr_edit", ~keep_px)):
                     if bool(sel.any()):
                         row[k] = float(metrics.calculate_psnr(g[sel], o[sel]))
+            if "auto_keep" in batch:  # the same against the estimated keep-mask, and the share of the image it edits
+                keep_px = (batch["auto_keep"][j] >= 0.5).expand_as(o)
+                for k, sel in (("psnr_keep", keep_px), ("psnr_edit", ~keep_px)):
+                    if bool(sel.any()):
+                        row[k] = float(metrics.calculate_psnr(g[sel], o[sel]))
+                row["edit_fraction"] = float(1.0 - batch["auto_keep"][j].mean())
+                if a.save_masks:
+                    from PIL import Image
+                    Image.fromarray((batch["auto_keep"][j, 0].numpy() * 255).astype("uint8")).save(
+                        os.path.join(a.output_dir, "%06d_mask.png" % sid))
             if scores is not None:
                 row["clip"], row["d-clip"] = scores[0][j], scores[1][j]
             if feats is not None:
@@ -214,7 +232,7 @@ def main(argv=None):
         assert len({r["sample_id"] for r in rows}) == len(rows)  # padding rows were skipped where they were produced
         rows.sort(key=lambda r: r["sample_id"])
         summary = {k: sum(r[k] for r in rows) / max(1, len(rows)) for k in ("psnr", "ssim", "l2")}
-        for k in ("psnr_keep", "psnr_edit"):  # only when masked samples exist
+        for k in ("psnr_keep", "psnr_edit", "edit_fraction"):  # only when masked / auto-masked samples exist
             masked = [r[k] for r in rows if k in r]
             if masked:
                 summary[k] = sum(masked) / len(masked)
