@@ -104,6 +104,9 @@ SIGNATURES = {
                        C.POINTER(_I)],
     "cd_op_attention": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _I, _VP],
     "cd_op_cross_attention_ctrl": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _VP],
+    "cd_op_cross_attention_ctrl_ex": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I,
+                                      _VP],
+    "cd_op_attention_ex": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _VP, _I, _I, _VP],
     "cd_op_lowpass": [_VP, _VP, _I, _I, _I, _I, _VP],
     "cd_op_softmax_rows": [_VP, _VP, _I64, _I, _VP],
     "cd_op_timestep_embedding": [_VP, _VP, _I, _I, _I, _VP],

@@ -1470,15 +1470,94 @@ int cd_op_attention(cd_handle h, const float* q, const float* k, const float* v,
   CD_API_END
 }
 
-int cd_op_cross_attention_ctrl(cd_handle h, const float* q_own, const float* q_src, const float* k_own, const float* k_src,
-                               const float* v_own, const float* mapper, const float* alpha, const float* weight, int B,
-                               int B_src, int B_ctrl, int H, int Tq, int L, int L_buf, int D, float scale, float* o) {
+// 16-bit staging for the *_ex test entries: every buffer starts as 0xFF bytes (a NaN in fp16 and in bf16) and carries one more
+// 64-row block of them behind its last row, so a read outside the operand columns / rows shows in the result
+static bf16_t* op_nan_rows16(cd_engine* h, int64_t rows, int ld) {
+  const size_t bytes = (size_t)(rows + 64) * ld * 2;
+  bf16_t* t = (bf16_t*)h->arena.alloc(bytes);
+  HIP_CHECK(hipMemsetAsync(t, 0xFF, bytes, h->st));
+  return t;
+}
+// columns [col0, col0 + C) of dst [rows][ld] (16-bit) <- fp32 src [rows][C], rounded by launch_nchw_to_nhwc
+static void op_put_cols16(cd_engine* h, bf16_t* dst, int ld, int col0, const float* src, int64_t rows, int C) {
+  ArenaScope tmp_scope(h->arena);  // stream order: the copy below has read tmp before any later kernel reuses the space
+  bf16_t* tmp = (bf16_t*)h->arena.alloc((size_t)rows * C * 2);
+  launch_nchw_to_nhwc(h->st, src, tmp, (int)rows, C, 1, C, 1.f, 0.f, 0);
+  HIP_CHECK(hipMemcpy2DAsync(dst + col0, (size_t)ld * 2, tmp, (size_t)C * 2, (size_t)C * 2, (size_t)rows,
+                             hipMemcpyDeviceToDevice, h->st));
+}
+
+int cd_op_attention_ex(cd_handle h, const float* q, const float* k, const float* v, int B, int H, int Tq, int Tk, int D,
+                       int layout, int pad, int v_transposed, int d_extra, int t_extra, float scale, int q_log2,
+                       const float* obias, int causal, int opad, float* o) {
   CD_API_BEGIN
   enter_engine(h);
-  CD_CHECK(h && q_own && q_src && k_own && k_src && v_own && mapper && alpha && weight && o, "bad argument");
-  CD_CHECK(B > 0 && B_src > 0 && B_ctrl > 0 && H > 0 && Tq > 0 && D > 0 && L > 0 && L_buf >= L, "bad argument");
+  CD_CHECK(h && q && k && v && o && B > 0 && H > 0 && Tq > 0 && Tk > 0 && D > 0 && D % 8 == 0, "bad argument");
+  CD_CHECK(layout >= 0 && layout <= 2, "bad argument (layout 0 = q, k, v apart, 1 = q | k in one tensor, 2 = q | k | v)");
+  CD_CHECK(layout == 0 || Tq == Tk, "a fused q | k (| v) tensor needs Tq = Tk");
+  CD_CHECK(!(layout == 2 && v_transposed), "the fused q | k | v tensor carries V token-major");
+  CD_CHECK(pad >= 0 && pad % 8 == 0, "pad: a multiple of 8 elements");
+  CD_CHECK(opad >= 0 && opad % 4 == 0, "opad: a multiple of 4 elements");
+  CD_CHECK(d_extra >= 0 && t_extra >= 0 && (v_transposed || (d_extra == 0 && t_extra == 0)),
+           "d_extra / t_extra pad V^T only");
   ArenaScope arena_scope(h->arena);
   const int C = H * D;
+  const int64_t rq = (int64_t)B * Tq, rk = (int64_t)B * Tk;
+  AttnParams p;
+  const bf16_t* vb;
+  int ldv;
+  if (layout == 0) {  // every tensor padded, and no two row strides equal: a stride taken from the wrong operand shows
+    const int lq = C + pad, lk = C + 2 * pad, lv = C + 3 * pad;
+    bf16_t* qb = op_nan_rows16(h, rq, lq);
+    bf16_t* kb = op_nan_rows16(h, rk, lk);
+    bf16_t* vv = op_nan_rows16(h, rk, lv);
+    op_put_cols16(h, qb, lq, 0, q, rq, C);
+    op_put_cols16(h, kb, lk, 0, k, rk, C);
+    op_put_cols16(h, vv, lv, 0, v, rk, C);
+    p.q = qb; p.k = kb; p.ldq = lq; p.ldk = lk; vb = vv; ldv = lv;
+  } else {
+    const int n = layout + 1, ld = n * C + pad;  // q | k (| v) as column blocks of one tensor
+    bf16_t* t = op_nan_rows16(h, rq, ld);
+    op_put_cols16(h, t, ld, 0, q, rq, C);
+    op_put_cols16(h, t, ld, C, k, rq, C);
+    p.q = t; p.k = t + C; p.ldq = p.ldk = ld;
+    if (layout == 2) {
+      op_put_cols16(h, t, ld, 2 * C, v, rq, C);
+      vb = t + 2 * C; ldv = ld;
+    } else {
+      bf16_t* vv = op_nan_rows16(h, rk, C + pad);
+      op_put_cols16(h, vv, C + pad, 0, v, rk, C);
+      vb = vv; ldv = C + pad;
+    }
+  }
+  const int ldo = C + opad;
+  bf16_t* ob = op_nan_rows16(h, rq, ldo);
+  p.o = ob; p.ldo = ldo;
+  p.B = B; p.H = H; p.Tq = Tq; p.Tk = Tk; p.D = D;
+  p.q_bs = (int64_t)Tq * p.ldq; p.k_bs = (int64_t)Tk * p.ldk; p.o_bs = (int64_t)Tq * ldo;
+  p.scale = scale; p.q_log2 = q_log2 != 0; p.obias = obias; p.causal = causal != 0;
+  if (v_transposed) {  // V^T [B][H][D + d_extra][round_up(Tk, 64) + 64 t_extra]: its padding is launch_transpose_v's zeros
+    const int Dpad = D + d_extra, Tpad = round_up(Tk, 64) + 64 * t_extra;
+    bf16_t* vt = (bf16_t*)h->arena.alloc((size_t)B * H * Dpad * Tpad * 2);
+    launch_transpose_v(h->st, vb, ldv, (int64_t)Tk * ldv, vt, B, H, Tk, D, Dpad, Tpad);
+    p.vt = vt; p.vt_dpad = Dpad; p.vt_tpad = Tpad;
+  } else {
+    p.v = vb; p.ldv = ldv; p.v_bs = (int64_t)Tk * ldv;
+  }
+  launch_attention(h->st, p);
+  launch_nhwc_to_nchw(h->st, ob, 0, ldo, o, (int)rq, ldo, 1, 1.f, 0.f);
+  CD_API_END
+}
+
+static void op_cross_attention_ctrl(cd_engine* h, const float* q_own, const float* q_src, const float* k_own,
+                                    const float* k_src, const float* v_own, const float* mapper, const float* alpha,
+                                    const float* weight, int B, int B_src, int B_ctrl, int H, int Tq, int L, int L_buf, int D,
+                                    float scale, int q_log2, int opad, float* o) {
+  CD_CHECK(h && q_own && q_src && k_own && k_src && v_own && mapper && alpha && weight && o, "bad argument");
+  CD_CHECK(B > 0 && B_src > 0 && B_ctrl > 0 && H > 0 && Tq > 0 && D > 0 && L > 0 && L_buf >= L, "bad argument");
+  CD_CHECK(opad >= 0 && opad % 4 == 0, "opad: a multiple of 4 elements");
+  ArenaScope arena_scope(h->arena);
+  const int C = H * D, ldo = C + opad;
   auto to16 = [&](const float* src, int64_t rows) {
     bf16_t* d = (bf16_t*)h->arena.alloc((size_t)rows * C * 2);
     launch_nchw_to_nhwc(h->st, src, d, (int)rows, C, 1, C, 1.f, 0.f, 0);
@@ -1491,14 +1570,34 @@ int cd_op_cross_attention_ctrl(cd_handle h, const float* q_own, const float* q_s
   bf16_t* va = (bf16_t*)h->arena.alloc((size_t)B * L * C * 2);
   bf16_t* vb = (bf16_t*)h->arena.alloc((size_t)B * L * C * 2);
   launch_ctrl_values(h->st, vb16, mapper, alpha, weight, B, B_ctrl, L, C, va, vb);
-  bf16_t* ob = (bf16_t*)h->arena.alloc((size_t)B * Tq * C * 2);
+  bf16_t* ob = op_nan_rows16(h, (int64_t)B * Tq, ldo);
   p.va = va; p.vb = vb; p.o = ob;
   p.B = B; p.B_src = B_src; p.H = H; p.Tq = Tq; p.L = L; p.D = D;
-  p.ldq = C; p.ldk = C; p.ldv = C; p.ldo = C;
-  p.q_bs = (int64_t)Tq * C; p.k_bs = (int64_t)L_buf * C; p.v_bs = (int64_t)L * C; p.o_bs = (int64_t)Tq * C;
-  p.scale = scale;
+  p.ldq = C; p.ldk = C; p.ldv = C; p.ldo = ldo;
+  p.q_bs = (int64_t)Tq * C; p.k_bs = (int64_t)L_buf * C; p.v_bs = (int64_t)L * C; p.o_bs = (int64_t)Tq * ldo;
+  p.scale = scale; p.q_log2 = q_log2 != 0;
   launch_cross_attention_ctrl(h->st, p);
-  launch_nhwc_to_nchw(h->st, ob, 0, C, o, B * Tq, C, 1, 1.f, 0.f);
+  launch_nhwc_to_nchw(h->st, ob, 0, ldo, o, B * Tq, ldo, 1, 1.f, 0.f);
+}
+
+int cd_op_cross_attention_ctrl(cd_handle h, const float* q_own, const float* q_src, const float* k_own, const float* k_src,
+                               const float* v_own, const float* mapper, const float* alpha, const float* weight, int B,
+                               int B_src, int B_ctrl, int H, int Tq, int L, int L_buf, int D, float scale, float* o) {
+  CD_API_BEGIN
+  enter_engine(h);
+  op_cross_attention_ctrl(h, q_own, q_src, k_own, k_src, v_own, mapper, alpha, weight, B, B_src, B_ctrl, H, Tq, L, L_buf, D,
+                          scale, 0, 0, o);
+  CD_API_END
+}
+
+int cd_op_cross_attention_ctrl_ex(cd_handle h, const float* q_own, const float* q_src, const float* k_own, const float* k_src,
+                                  const float* v_own, const float* mapper, const float* alpha, const float* weight, int B,
+                                  int B_src, int B_ctrl, int H, int Tq, int L, int L_buf, int D, float scale, int q_log2,
+                                  int opad, float* o) {
+  CD_API_BEGIN
+  enter_engine(h);
+  op_cross_attention_ctrl(h, q_own, q_src, k_own, k_src, v_own, mapper, alpha, weight, B, B_src, B_ctrl, H, Tq, L, L_buf, D,
+                          scale, q_log2, opad, o);
   CD_API_END
 }
 

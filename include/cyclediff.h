@@ -426,6 +426,25 @@ int cd_op_attention(cd_handle h, const float* q, const float* k, const float* v,
 int cd_op_cross_attention_ctrl(cd_handle h, const float* q_own, const float* q_src, const float* k_own, const float* k_src,
                                const float* v_own, const float* mapper, const float* alpha, const float* weight, int B,
                                int B_src, int B_ctrl, int H, int Tq, int L, int L_buf, int D, float scale, float* o);
+/* cd_op_cross_attention_ctrl with q_log2 (both q tensors already carry scale * log2 e; scale is then ignored) and an output
+   row stride of H*D + opad (opad % 4 == 0): o [B*Tq][H*D + opad] comes back pad columns included - the 16-bit output buffer
+   starts as NaN, so a column the kernel did not write reads NaN. */
+int cd_op_cross_attention_ctrl_ex(cd_handle h, const float* q_own, const float* q_src, const float* k_own, const float* k_src,
+                                  const float* v_own, const float* mapper, const float* alpha, const float* weight, int B,
+                                  int B_src, int B_ctrl, int H, int Tq, int L, int L_buf, int D, float scale, int q_log2,
+                                  int opad, float* o);
+/* launch_attention in the operand forms the networks use. q [B,Tq,H*D], k, v [B,Tk,H*D] fp32 as cd_op_attention takes them,
+ * staged as 16-bit tensors by `layout`: 0 = three tensors, each padded: row strides H*D + pad (q), H*D + 2 pad (k),
+ * H*D + 3 pad (v), so that no two are equal; 1 = q | k as column blocks of one
+ * tensor of row stride 2 H*D + pad (k = q + H*D; Tq = Tk), v apart with stride H*D + pad; 2 = q | k | v in one tensor of row
+ * stride 3 H*D + pad (Tq = Tk, token-major V only). pad % 8 == 0. v_transposed: V^T [B][H][D + d_extra][round_up(Tk, 64) +
+ * 64 t_extra] made by the transpose kernel (its padding: zeros), else V token-major where it was staged. q_log2: q already
+ * carries scale * log2 e (scale is then ignored); obias: fp32 [H*D] or NULL; causal: key j visible to query i iff j <= i.
+ * o: fp32 [B*Tq][H*D + opad] (opad % 4 == 0), pad columns included. Every staged 16-bit buffer, the output included, starts
+ * as 0xFF bytes (NaN in fp16 and bf16) and has one more 64-row block of them behind its last row. */
+int cd_op_attention_ex(cd_handle h, const float* q, const float* k, const float* v, int B, int H, int Tq, int Tk, int D,
+                       int layout, int pad, int v_transposed, int d_extra, int t_extra, float scale, int q_log2,
+                       const float* obias, int causal, int opad, float* o);
 /* y = phi_N(x) on caller tensors, fp32 NCHW [B,C,R,R], through the two kernels of cd_ilvr_decode (x' = 0, qa = 1, qb = 0);
  * refused as cd_ilvr_decode refuses its geometry. */
 int cd_op_lowpass(cd_handle h, const float* x, int B, int C, int R, int down_n, float* y);

@@ -289,6 +289,33 @@ def attention(eng, q, k, v, heads, scale, v_transposed=False):
     return o.cpu()
 
 
+def attention_ex(eng, q, k, v, heads, scale, layout=0, pad=0, v_transposed=False, d_extra=0, t_extra=0, q_log2=False,
+                 obias=None, causal=False, opad=0):
+    """cd_op_attention_ex: launch_attention on strided / fused operands. -> [B, Tq, H D + opad], pad columns included"""
+    B, Tq, Cc = q.shape
+    Tk = k.shape[1]
+    o = torch.zeros((B, Tq, Cc + opad), device="cuda", dtype=torch.float32)
+    qs, ks, vs = dev(q), dev(k), dev(v)
+    ob = dev(obias) if obias is not None else None
+    check(eng.lib.cd_op_attention_ex(eng.h, ptr(qs), ptr(ks), ptr(vs), B, heads, Tq, Tk, Cc // heads, layout, pad,
+                                     int(v_transposed), d_extra, t_extra, C.c_float(scale), int(q_log2), ptr(ob), int(causal),
+                                     opad, ptr(o)))
+    torch.cuda.synchronize()
+    return o.cpu()
+
+
+def cross_attention_ctrl_ex(eng, q_own, q_src, k_own, k_src, v_own, M, alpha, w, heads, scale, q_log2=False, opad=0):
+    """cd_op_cross_attention_ctrl_ex -> [B, Tq, H D + opad], pad columns included"""
+    B, Tq, Cc = q_own.shape
+    L = k_own.shape[1]
+    t = [dev(x) for x in (q_own, q_src, k_own, k_src, v_own, M, alpha, w)]
+    o = torch.zeros((B, Tq, Cc + opad), device="cuda", dtype=torch.float32)
+    check(eng.lib.cd_op_cross_attention_ctrl_ex(eng.h, *[ptr(x) for x in t], B, q_src.shape[0], M.shape[0], heads, Tq, L, L,
+                                                Cc // heads, C.c_float(scale), int(q_log2), opad, ptr(o)))
+    torch.cuda.synchronize()
+    return o.cpu()
+
+
 def softmax_rows(eng, s):
     rows, cols = s.shape
     p = torch.empty_like(s, device="cuda")
