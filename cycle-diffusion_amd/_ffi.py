@@ -114,6 +114,13 @@ SIGNATURES = {
     "cd_op_gauss": [_VP, _U64, C.c_uint32, _I64, _I64, _VP],
     "cd_op_automask_reduce": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _F, _I, _VP, _VP, _VP],
     "cd_op_sched_step_masked": [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, _VP, _VP, _I, _I, _F, _F, _VP, _I, _I, _I, _I, _VP, _I],
+    "cd_op_layout": [_VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _F, _F, _I],
+    "cd_op_resample16": [_VP, _I, _VP, _VP, _I, _I, _I, _I],
+    "cd_op_copy_rows16": [_VP, _VP, _I, _VP, _I, _I64, _I],
+    "cd_op_vec_linear": [_VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I],
+    "cd_op_tokens": [_VP, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I],
+    "cd_op_posterior_sample": [_VP, _VP, _I, _VP, _U64, _VP, _I, _I, _I, _F, _I],
+    "cd_op_vq_quantize": [_VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _I],
     "cd_op_bench_conv": [_VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float)],
     "cd_op_bench_mfma_sustained": [_VP, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)],
     "cd_op_probe": [_VP, _I, _VP, _VP, _SZ],

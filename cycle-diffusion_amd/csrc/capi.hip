@@ -2145,4 +2145,101 @@ int cd_op_resample_prec(cd_handle h, int op, const float* x, int B, int C, int H
   CD_API_END
 }
 
+// ---- bare entry points of the small kernels of elementwise.hip: the caller's device bytes in, one launch, the kernel's bytes
+// out. No staging kernel of the engine's touches either side (16-bit tensors are the storage words themselves).
+static void op_bare_done(cd_handle h) {
+  HIP_CHECK(hipGetLastError());  // a launch the runtime refused (its dynamic LDS, its grid) is an error, not an unchanged output
+  HIP_CHECK(hipStreamSynchronize(h->st));
+}
+
+int cd_op_layout(cd_handle h, int to_nchw, const void* x, void* y, int B, int C, int HW, int ld, int src_f32, float scale,
+                 float shift, int dup) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && y && B > 0 && C > 0 && HW > 0 && ld >= C, "bad argument");
+  if (to_nchw) {
+    CD_CHECK(dup == 0, "bad argument (dup: NCHW -> NHWC only)");
+    launch_nhwc_to_nchw(h->st, x, src_f32 != 0, ld, (float*)y, B, C, HW, scale, shift);
+  } else {
+    CD_CHECK(src_f32 == 1, "bad argument (NCHW -> NHWC reads fp32)");
+    launch_nchw_to_nhwc(h->st, (const float*)x, (bf16_t*)y, B, C, HW, ld, scale, shift, dup);
+  }
+  op_bare_done(h);
+  CD_API_END
+}
+
+int cd_op_resample16(cd_handle h, int op, const void* x, void* y, int B, int H, int W, int C) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && y && B > 0 && H > 0 && W > 0 && C > 0 && (op == 0 || op == 1), "bad argument");
+  if (op == 0) {
+    CD_CHECK(H >= 2 && W >= 2, "bad argument (avgpool: H, W >= 2)");
+    launch_avgpool2(h->st, (const bf16_t*)x, (bf16_t*)y, B, H, W, C);
+  } else {
+    launch_upsample2(h->st, (const bf16_t*)x, (bf16_t*)y, B, H, W, C);
+  }
+  op_bare_done(h);
+  CD_API_END
+}
+
+int cd_op_copy_rows16(cd_handle h, const void* src, int lds, void* dst, int ldd, int64_t rows, int cols) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && src && dst && rows > 0 && cols > 0 && lds >= cols && ldd >= cols, "bad argument");
+  launch_copy_strided_bf16(h->st, (const bf16_t*)src, lds, (bf16_t*)dst, ldd, rows, cols);
+  op_bare_done(h);
+  CD_API_END
+}
+
+int cd_op_vec_linear(cd_handle h, const float* x, int ldx, const float* W, const float* bias, float* y, int ldy, int B, int K,
+                     int N, int silu_in, int silu_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && W && y && B > 0 && K > 0 && N > 0 && ldx >= K && ldy >= N, "bad argument");
+  launch_vec_linear(h->st, x, ldx, W, bias, y, ldy, B, K, N, silu_in, silu_out);
+  op_bare_done(h);
+  CD_API_END
+}
+
+int cd_op_tokens(cd_handle h, int op, const int* ids, const void* x16, const float* tok, const float* pos, void* out, int B,
+                 int L, int D, int vocab) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && out && B > 0 && L > 0 && D > 0, "bad argument");
+  if (op == 0) {
+    CD_CHECK(ids && tok && pos && vocab > 0, "bad argument (embed_tokens: ids, table, positions)");
+    launch_embed_tokens(h->st, ids, tok, pos, (bf16_t*)out, B, L, D, vocab);
+  } else if (op == 1) {
+    CD_CHECK(x16 && tok && pos, "bad argument (vit_tokens: patches, class row, positions)");
+    launch_vit_tokens(h->st, (const bf16_t*)x16, tok, pos, (bf16_t*)out, B, L, D);
+  } else if (op == 2) {
+    CD_CHECK(x16 && ids, "bad argument (gather_eot: rows, ids)");
+    launch_gather_eot(h->st, (const bf16_t*)x16, ids, (bf16_t*)out, B, L, D);
+  } else {
+    CD_CHECK(false, "bad argument (op 0 = embed_tokens, 1 = vit_tokens, 2 = gather_eot)");
+  }
+  op_bare_done(h);
+  CD_API_END
+}
+
+int cd_op_posterior_sample(cd_handle h, const float* mom, int ld, const float* noise, uint64_t seed, float* z, int B, int zc,
+                           int HW, float scale, int use_mean) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && mom && z && B > 0 && zc > 0 && HW > 0 && ld >= 2 * zc, "bad argument");
+  launch_posterior_sample(h->st, mom, ld, noise, seed, z, B, zc, HW, scale, use_mean);
+  op_bare_done(h);
+  CD_API_END
+}
+
+int cd_op_vq_quantize(cd_handle h, const float* z, float in_mul, const float* codebook, int n_embed, int zc, int B, int HW,
+                      void* out16, int Cpad) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && z && codebook && out16 && B > 0 && HW > 0 && Cpad >= zc, "bad argument");
+  launch_vq_quantize(h->st, z, in_mul, codebook, n_embed, zc, B, HW, (bf16_t*)out16, Cpad);
+  op_bare_done(h);
+  CD_API_END
+}
+
 }  // extern "C"

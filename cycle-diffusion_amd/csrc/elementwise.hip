@@ -332,6 +332,7 @@ void launch_vec_linear(hipStream_t st, const float* x, int ldx, const float* W, 
                      bias, y, ldy, B, K, N, silu_in, silu_out);
 }
 void launch_avgpool2(hipStream_t st, const bf16_t* x, bf16_t* y, int B, int H, int W, int C) {
+  CD_CHECK(C % 8 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0, "avgpool2: 16-byte vectors");
   const int64_t n = (int64_t)B * (H / 2) * (W / 2) * (C / 8);
   hipLaunchKernelGGL(k_avgpool2, dim3(ew_grid(n)), dim3(256), 0, st, x, y, B, H, W, C);
 }
@@ -341,6 +342,7 @@ void launch_up_phase_reorder(hipStream_t st, const bf16_t* x, bf16_t* y, int B, 
   hipLaunchKernelGGL(k_up_phase_reorder, dim3(ew_grid(n)), dim3(256), 0, st, x, y, B, H, W, C, ldy);
 }
 void launch_upsample2(hipStream_t st, const bf16_t* x, bf16_t* y, int B, int H, int W, int C) {
+  CD_CHECK(C % 8 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0, "upsample2: 16-byte vectors");
   const int64_t n = (int64_t)B * H * 2 * W * 2 * (C / 8);
   hipLaunchKernelGGL(k_upsample2, dim3(ew_grid(n)), dim3(256), 0, st, x, y, B, H, W, C);
 }
@@ -385,6 +387,8 @@ void launch_fill_f32(hipStream_t st, float* p, float v, int64_t n) {
 }
 void launch_copy_strided_bf16(hipStream_t st, const bf16_t* src, int lds_, bf16_t* dst, int ldd,
                               int64_t rows, int cols) {
+  CD_CHECK(cols % 8 == 0 && lds_ % 8 == 0 && ldd % 8 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0,
+           "copy_strided_bf16: 16-byte vectors");
   const int64_t n = rows * (cols / 8);
   hipLaunchKernelGGL(k_copy_strided_bf16, dim3(ew_grid(n)), dim3(256), 0, st, src, lds_, dst, ldd,
                      rows, cols);

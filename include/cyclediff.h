@@ -471,6 +471,35 @@ int cd_op_sched_step_masked(cd_handle h, int mode, const cd_step_coef* coef_host
                             float guidance, const float* eps_in, const float* mask, const float* src, int B_mask,
                             int mask_source, float qa, float qb, const float* mask_noise, int blend, int B, int C, int HW,
                             void* xin16_out, int cfg_dup);
+/* ---- bare single-kernel entry points of the small HBM-bound kernels (csrc/elementwise.hip), test-only ----
+ * Every pointer is device memory that the caller laid out itself; a 16-bit tensor is the storage words of cd_act_format().
+ * Each call checks its arguments, makes exactly one launch and synchronises: no staging kernel of the engine's sits between
+ * the caller's bytes and the kernel, or between the kernel and the bytes read back. */
+/* to_nchw = 0: x fp32 NCHW [B,C,HW] -> y 16-bit [B*HW][ld] (ld = Cpad >= C, columns C.. zero), y = x * scale + shift; dup:
+ * the same rows again behind the first B*HW*ld words. to_nchw = 1: x [B*HW][ld] 16-bit (src_f32 = 0) or fp32 (src_f32 = 1)
+ * -> y fp32 NCHW [B,C,HW] = x * scale + shift */
+int cd_op_layout(cd_handle h, int to_nchw, const void* x, void* y, int B, int C, int HW, int ld, int src_f32, float scale,
+                 float shift, int dup);
+/* op 0: 2 x 2 average pool [B,H,W,C] -> [B,H/2,W/2,C]; op 1: nearest x2 upsample -> [B,2H,2W,C]; 16-bit NHWC, C % 8 == 0 */
+int cd_op_resample16(cd_handle h, int op, const void* x, void* y, int B, int H, int W, int C);
+/* rows x cols 16-bit words from row stride lds to row stride ldd (cols, lds, ldd multiples of 8) */
+int cd_op_copy_rows16(cd_handle h, const void* src, int lds, void* dst, int ldd, int64_t rows, int cols);
+/* y[b][n] = act_out(sum_k act_in(x[b][k]) W[n][k] + bias[n]), fp32, act = SiLU where the flag is set; bias may be NULL */
+int cd_op_vec_linear(cd_handle h, const float* x, int ldx, const float* W, const float* bias, float* y, int ldy, int B, int K,
+                     int N, int silu_in, int silu_out);
+/* op 0: out[b][l] = tok[clamp(ids[b][l], 0, vocab - 1)] + pos[l] (tok [vocab][D], pos [L][D] fp32, out 16-bit [B][L][D]);
+ * op 1: out [B][L + 1][D] = [tok (the class row [D]) ; x16 (patches, 16-bit [B][L][D])] + pos [L + 1][D];
+ * op 2: out [B][D] = x16[b][first argmax_l ids[b][l]] (x16 16-bit [B][L][D]). D % 8 == 0 for op 0 and 1. */
+int cd_op_tokens(cd_handle h, int op, const int* ids, const void* x16, const float* tok, const float* pos, void* out, int B,
+                 int L, int D, int vocab);
+/* mom fp32 [B*HW][ld] = mean(zc) | logvar(zc) | ...; z fp32 NCHW [B,zc,HW] = scale * (mean + exp(0.5 clamp(logvar, -30, 20))
+ * * noise) or scale * mean with use_mean; noise fp32 [B,zc,HW], NULL = the generator's draws for `seed` */
+int cd_op_posterior_sample(cd_handle h, const float* mom, int ld, const float* noise, uint64_t seed, float* z, int B, int zc,
+                           int HW, float scale, int use_mean);
+/* z fp32 NCHW [B,zc,HW], codebook fp32 [n_embed][zc] -> out16 [B*HW][Cpad]: the nearest code (first minimum) of z * in_mul in
+ * columns < zc, zero words behind; zc <= 8 and a codebook of at most 150 KB */
+int cd_op_vq_quantize(cd_handle h, const float* z, float in_mul, const float* codebook, int n_embed, int zc, int B, int HW,
+                      void* out16, int Cpad);
 /* micro-benchmark of one conv / GEMM shape on synthetic data (scripts/bench_gemm.py): average ms per launch.
  * act: low byte = activation; | 0x100 = in-place residual update of the output; | 0x200 = fused GroupNorm statistics */
 int cd_op_bench_conv(cd_handle h, int B, int H, int W, int C0, int C1, int N, int k, int stride, int up,

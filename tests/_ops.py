@@ -356,3 +356,99 @@ def probe(eng, which, nfloats):
     check(eng.lib.cd_op_probe(eng.h, which, None, ptr(out), nfloats * 4))
     torch.cuda.synchronize()
     return out.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------ bare entry points of csrc/elementwise.hip
+# The caller's bytes in, one launch, the kernel's bytes out (tests/_glue_ref.py: operands, sentinels, guards). 16-bit tensors
+# are torch.int16 storage words; nothing here converts, pads or transposes on the device.
+def _up(t):
+    return None if t is None else t.contiguous().cuda()
+
+
+def _out16(words, guard, sent):
+    return torch.full((words + guard,), sent, dtype=torch.int16, device="cuda")
+
+
+def _out32(n, guard, sent):
+    return torch.full((n + guard,), sent, dtype=torch.float32, device="cuda")
+
+
+def _finish(eng, rc, y, refusal):
+    """the output buffer; with refusal = True the call must have been refused: (its error text, the buffer as it left it)"""
+    if not refusal:
+        check(rc)
+        return y.cpu()
+    assert rc != 0, "the call was not refused"
+    msg = eng.lib.cd_last_error().decode("utf-8", "replace")
+    torch.cuda.synchronize()
+    return msg, y.cpu()
+
+
+def glue_nchw_to_nhwc(eng, x, Cpad, scale, shift, dup, guard, sent):
+    """k_nchw_to_nhwc: x fp32 [B, C, HW] -> int16 [(1 + dup) B HW Cpad + guard]"""
+    B, Cc, HW = x.shape
+    xs, y = _up(x), _out16((1 + dup) * B * HW * Cpad, guard, sent)
+    check(eng.lib.cd_op_layout(eng.h, 0, ptr(xs), ptr(y), B, Cc, HW, Cpad, 1, C.c_float(scale), C.c_float(shift), dup))
+    return y.cpu()
+
+
+def glue_nhwc_to_nchw(eng, x, B, Cc, HW, scale, shift, guard, sent):
+    """k_nhwc_to_nchw: x [B HW][ld] int16 words or fp32 -> fp32 [B C HW + guard]"""
+    xs, y = _up(x), _out32(B * Cc * HW, guard, sent)
+    check(eng.lib.cd_op_layout(eng.h, 1, ptr(xs), ptr(y), B, Cc, HW, x.shape[1], int(x.dtype == torch.float32),
+                               C.c_float(scale), C.c_float(shift), 0))
+    return y.cpu()
+
+
+def glue_resample16(eng, op, x, guard, sent, refusal=False):
+    """k_avgpool2 / k_upsample2: x int16 [B, H, W, C] -> int16 [B Ho Wo C + guard]"""
+    B, H, W, Cc = x.shape
+    Ho, Wo = (H // 2, W // 2) if op == "avgpool" else (2 * H, 2 * W)
+    xs, y = _up(x), _out16(B * Ho * Wo * Cc, guard, sent)
+    rc = eng.lib.cd_op_resample16(eng.h, 0 if op == "avgpool" else 1, ptr(xs), ptr(y), B, H, W, Cc)
+    return _finish(eng, rc, y, refusal)
+
+
+def glue_copy_rows16(eng, src, ldd, cols, launches, total_rows, guard, sent, refusal=False):
+    """k_copy_strided_bf16: src int16 [rows][lds]; launches = (first source row, first destination row, rows) each"""
+    lds = src.shape[1]
+    xs, y = _up(src), _out16(total_rows * ldd, guard, sent)
+    rc = 0
+    for r0, d0, rows in launches:
+        rc = rc or eng.lib.cd_op_copy_rows16(eng.h, ptr(xs[r0:]), lds, ptr(y[d0 * ldd:]), ldd, rows, cols)
+    return _finish(eng, rc, y, refusal)
+
+
+def glue_vec_linear(eng, x, W, bias, K, ldy, silu_in, silu_out, sent):
+    """k_vec_linear: x fp32 [B][ldx], W [N][K] -> fp32 [B][ldy], the columns >= N as they were"""
+    B, N = x.shape[0], W.shape[0]
+    xs, ws, bs = _up(x), _up(W), _up(bias)
+    y = torch.full((B, ldy), sent, dtype=torch.float32, device="cuda")
+    check(eng.lib.cd_op_vec_linear(eng.h, ptr(xs), x.shape[1], ptr(ws), ptr(bs), ptr(y), ldy, B, K, N, int(silu_in),
+                                   int(silu_out)))
+    return y.cpu()
+
+
+def glue_tokens(eng, op, B, L, D, vocab, out_words, guard, sent, ids=None, x16=None, tok=None, pos=None):
+    """k_embed_tokens / k_vit_tokens / k_gather_eot -> int16 [out_words + guard]"""
+    t = [_up(v) for v in (ids, x16, tok, pos)]
+    y = _out16(out_words, guard, sent)
+    check(eng.lib.cd_op_tokens(eng.h, {"embed": 0, "vit": 1, "eot": 2}[op], ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), ptr(y),
+                               B, L, D, vocab))
+    return y.cpu()
+
+
+def glue_posterior_sample(eng, mom, noise, B, zc, HW, scale, use_mean, guard, sent, seed=0):
+    """k_posterior_sample: mom fp32 [B HW][ld] -> fp32 [B zc HW + guard]"""
+    ms, ns, z = _up(mom), _up(noise), _out32(B * zc * HW, guard, sent)
+    check(eng.lib.cd_op_posterior_sample(eng.h, ptr(ms), mom.shape[1], ptr(ns), seed, ptr(z), B, zc, HW, C.c_float(scale),
+                                         int(use_mean)))
+    return z.cpu()
+
+
+def glue_vq_quantize(eng, z, in_mul, codebook, B, HW, Cpad, guard, sent, refusal=False):
+    """k_vq_quantize: z fp32 [B, zc, HW], codebook [n_embed][zc] -> int16 [B HW Cpad + guard]"""
+    zs, cs, y = _up(z), _up(codebook), _out16(B * HW * Cpad, guard, sent)
+    rc = eng.lib.cd_op_vq_quantize(eng.h, ptr(zs), C.c_float(in_mul), ptr(cs), codebook.shape[0], codebook.shape[1], B, HW, ptr(y),
+                                   Cpad)
+    return _finish(eng, rc, y, refusal)
