@@ -43,22 +43,6 @@ def build(force=False, verbose=False, variant=None):
         objdir = os.path.join(HERE, "build", "bf16")
         lib = os.path.join(LIBDIR, "libcyclediff_bf16.so")
         defines = ["-DCD_ACT_FP16=0"]
-    elif variant == "probe":  # phase-timing instrumentation of k_conv_gemm (scripts/probe_report.py); never the product
-        objdir = os.path.join(HERE, "build", "probe")
-        lib = os.path.join(LIBDIR, "libcyclediff_probe.so")
-        defines = ["-DCD_PROBE"]
-    elif variant == "pack8old":  # round-6 A/B: the f2bf-based pack8 / pack2 (measurement only)
-        objdir = os.path.join(HERE, "build", "pack8old")
-        lib = os.path.join(LIBDIR, "libcyclediff_pack8old.so")
-        defines = ["-DCD_PACK8_F2BF"]
-    elif variant == "geluold":  # round-6 A/B: the select form of gelu_fast (measurement only)
-        objdir = os.path.join(HERE, "build", "geluold")
-        lib = os.path.join(LIBDIR, "libcyclediff_geluold.so")
-        defines = ["-DCD_GELU_SELECT_FORM"]
-    elif variant in ("ntst", "ntld"):  # round-6 A/B: streaming (nt) output stores / residual loads of the GEMM epilogue (measurement only)
-        objdir = os.path.join(HERE, "build", variant)
-        lib = os.path.join(LIBDIR, "libcyclediff_%s.so" % variant)
-        defines = ["-DCD_EPI_STORE_AUX=2"] if variant == "ntst" else ["-DCD_EPI_RESID_AUX=2"]
     elif variant is not None:
         raise ValueError("unknown build variant %r" % (variant,))
     os.makedirs(LIBDIR, exist_ok=True)
@@ -95,5 +79,4 @@ def build(force=False, verbose=False, variant=None):
 
 
 if __name__ == "__main__":
-    _variant = next((v for v in ("bf16", "probe", "pack8old", "geluold", "ntst", "ntld") if "--" + v in sys.argv), None)
-    print(build(force="--force" in sys.argv, verbose=True, variant=_variant))
+    print(build(force="--force" in sys.argv, verbose=True, variant="bf16" if "--bf16" in sys.argv else None))

@@ -30,8 +30,6 @@
 //   * the ragged last tile alone is masked, P is packed with one convert per pair and - where V^T has a
 //     spare padded row - the row sums fall out of the PV MFMA itself.
 // fp32 softmax statistics and accumulation, 16-bit operands.
-#include <stdlib.h>
-
 #include "common.h"
 #include "kernels.h"
 
@@ -48,10 +46,7 @@ constexpr int KT = 64;  // keys per tile
 // written to the other LDS buffer after it - one barrier per tile.
 // NWV = waves per workgroup (32 queries each): 4, or 8 - a 256-query workgroup stages every K / V tile once for twice
 // the queries (half the L2 -> LDS traffic and half the staging instructions per query; same waves per SIMD)
-// DBG (probe build only, CD_ATTN_DBG: timing experiments whose RESULTS ARE WRONG - which part of a tile costs what):
-//   1 no K / V fetch and commit after the first tile   2 no barrier in the loop   8 no exponentials (p = s)
-//   16 no PV MFMAs   32 no QK^T MFMAs   64 no maximum / deferred-maximum test
-template <int DQK, int DV, int DH, int NBUF, bool VTOK, int KG, int NWV = 4, int DBG = 0>
+template <int DQK, int DV, int DH, int NBUF, bool VTOK, int KG, int NWV = 4>
 __global__ __launch_bounds__(64 * NWV, DV <= 96 ? (KG == 32 ? (DV <= 64 ? 4 : 3) : 2) : 1) void k_attention(AttnParams p) {
   constexpr int NT = 64 * NWV;  // threads per workgroup
   constexpr int KLD = DQK + 8;  // elements per K row in LDS (16 B pad)
@@ -200,9 +195,9 @@ __global__ __launch_bounds__(64 * NWV, DV <= 96 ? (KG == 32 ? (DV <= 64 ? 4 : 3)
     const int key0 = t * KT;
     const int buf = NBUF == 2 ? (t & 1) : 0;
     const bool more = t + 1 < ntiles;
-    if (more && !(DBG & 1)) fetch(key0 + KT);
-    const bf16_t* Kt = Ks[(DBG & 1) ? 0 : buf];
-    const bf16_t* Vt = Vs[(DBG & 1) ? 0 : buf];
+    if (more) fetch(key0 + KT);
+    const bf16_t* Kt = Ks[buf];
+    const bf16_t* Vt = Vs[buf];
 
     // The tile is consumed in groups of KG keys (KG = 64: both 32-key halves at once; KG = 32: one half at a time -
     // half the score / probability registers live, one more wave per SIMD where that crosses an occupancy step).
@@ -222,16 +217,8 @@ __global__ __launch_bounds__(64 * NWV, DV <= 96 ? (KG == 32 ? (DV <= 64 ? 4 : 3)
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
-          for (int kh = 0; kh < HPG; ++kh) {  // the 32-key halves alternate: no back-to-back dependent MFMAs
-            if constexpr (DBG & 32) {
-              if (ks == 0) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s[kh][r] = negm[r] + __builtin_bit_cast(float, (uint32_t)kf[kh][NKS - 1][r & 7] << 16) * 1e-30f;
-              }
-            } else {
-              s[kh] = CD_MFMA_32x32x16(kf[kh][ks], qf[ks], ks == 0 ? negm : s[kh]);
-            }
-          }
+          for (int kh = 0; kh < HPG; ++kh)  // the 32-key halves alternate: no back-to-back dependent MFMAs
+            s[kh] = CD_MFMA_32x32x16(kf[kh][ks], qf[ks], ks == 0 ? negm : s[kh]);
       }
       // ---- keys beyond Tk (last tile only) / causal mask
       if (key0 + KT > p.Tk || p.causal) {
@@ -251,7 +238,6 @@ __global__ __launch_bounds__(64 * NWV, DV <= 96 ? (KG == 32 ? (DV <= 64 ? 4 : 3)
       // (Rounds 1-2a started with the asm op: a latent hazard, visible as run-to-run differences once the 32-key groups
       // put the reader right behind a dependent MFMA chain.)
       float mx = __builtin_amdgcn_fmed3f(s[HPG - 1][14], s[HPG - 1][15], INFINITY);
-      if constexpr (!(DBG & 64)) {
       if (HPG == 2) {
 #pragma unroll
         for (int r = 0; r < 14; r += 2)
@@ -260,12 +246,11 @@ __global__ __launch_bounds__(64 * NWV, DV <= 96 ? (KG == 32 ? (DV <= 64 ? 4 : 3)
 #pragma unroll
       for (int r = 0; r < (HPG == 2 ? 16 : 14); r += 2)
         asm("v_max3_f32 %0, %1, %2, %3" : "=v"(mx) : "v"(mx), "v"(s[0][r]), "v"(s[0][r + 1]));
-      }
       // ---- move m (rare, wave-uniform): always on the first group, later only if a row grew past 2^kDefer.
       // Textbook order: the decision precedes the exponentiation of the keys it covers, and everything
       // accumulated against the old m (o, the row sums inside o or l_part) is rescaled exactly once.
       const bool first = t == 0 && g == 0;
-      if (first || (!(DBG & 64) && __any(mx > kDefer))) {
+      if (first || __any(mx > kDefer)) {
         const float mxq = fmaxf(mx, __shfl_xor(mx, 32));  // both half-lanes of a query agree
         float delta = first ? mxq : fmaxf(mxq, 0.f);
         delta = delta == -INFINITY ? 0.f : delta;
@@ -290,8 +275,8 @@ __global__ __launch_bounds__(64 * NWV, DV <= 96 ? (KG == 32 ? (DV <= 64 ? 4 : 3)
       for (int kh = 0; kh < HPG; ++kh)
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {
-          const float e0 = (DBG & 8) ? s[kh][r] : __builtin_amdgcn_exp2f(s[kh][r]);
-          const float e1 = (DBG & 8) ? s[kh][r + 1] : __builtin_amdgcn_exp2f(s[kh][r + 1]);
+          const float e0 = __builtin_amdgcn_exp2f(s[kh][r]);
+          const float e1 = __builtin_amdgcn_exp2f(s[kh][r + 1]);
           if (!ONES) ps += e0 + e1;
           pw[kh][r >> 1] = pack2_prob(e0, e1);
         }
@@ -317,15 +302,14 @@ __global__ __launch_bounds__(64 * NWV, DV <= 96 ? (KG == 32 ? (DV <= 64 ? 4 : 3)
             } else {
               vf = *(const bf16x8*)(Vt + (dt * 32 + qi) * VLD + k16 + 8 * half);
             }
-            if constexpr (DBG & 16) o[dt][0] += __builtin_bit_cast(float, (uint32_t)vf[0] << 16) * __builtin_bit_cast(float, praw.x);
-            else o[dt] = CD_MFMA_32x32x16(vf, pf, o[dt]);
+            o[dt] = CD_MFMA_32x32x16(vf, pf, o[dt]);
           }
         }
     }
 
-    if (NBUF == 1 && !(DBG & 2)) __syncthreads();
-    if (more && !(DBG & 1)) commit(NBUF == 2 ? (buf ^ 1) : 0);
-    if (!(DBG & 2)) __syncthreads();
+    if (NBUF == 1) __syncthreads();
+    if (more) commit(NBUF == 2 ? (buf ^ 1) : 0);
+    __syncthreads();
   }
 
   // ---- normalise and store: lane owns query q0+qi and 4 consecutive d per register quad
@@ -829,60 +813,31 @@ void launch_attention(hipStream_t st, const AttnParams& p) {
   else CD_CHECK((p.ldv % 8) == 0 && ((uintptr_t)p.v & 15) == 0, "attention: V row stride / alignment");
   CD_CHECK((p.ldq % 8) == 0 && (p.ldk % 8) == 0 && (p.ldo % 4) == 0, "attention: leading dims");
   dim3 grid(ceil_div(p.Tq, 128), p.H, p.B);
-#define CD_ATTN_KG(DQK, DV, DH, NBUF, KG)                                                                    \
+#define CD_LAUNCH_KG(DQK, DV, DH, NBUF, KG)                                                                  \
   do {                                                                                                      \
     if (p.v) hipLaunchKernelGGL((k_attention<DQK, DV, DH, NBUF, true, KG>), grid, dim3(256), 0, st, p);      \
     else hipLaunchKernelGGL((k_attention<DQK, DV, DH, NBUF, false, KG>), grid, dim3(256), 0, st, p);         \
   } while (0)
-#define CD_ATTN(DQK, DV, DH, NBUF) CD_ATTN_KG(DQK, DV, DH, NBUF, 64)
+#define CD_ATTN(DQK, DV, DH, NBUF) CD_LAUNCH_KG(DQK, DV, DH, NBUF, 64)
   // d = 40 (SD / LDM 320-channel level): 32-key softmax groups fit 128 VGPRs = four waves per SIMD (2 % faster than
-  // 64-key groups at three: profiles/r2b_attention_v_layouts.txt); CD_ATTN_KG32=0 selects the 64-key form for A/B runs
-  static const bool half_groups = [] { const char* e = getenv("CD_ATTN_KG32"); return !(e && e[0] == '0'); }();
-  // 256-query workgroups (8 waves) for the long self-attention of the 64 x 64 level: CD_ATTN_W8=0 selects 128 (A/B)
-  static const bool wide_wg = [] { const char* e = getenv("CD_ATTN_W8"); return !(e && e[0] == '0'); }();
-  if (p.D == 40 && half_groups && wide_wg && p.Tq >= 1024 && p.Tk >= 1024 && p.vt) {
-#ifdef CD_PROBE
-    static const int dbg = [] { const char* e = getenv("CD_ATTN_DBG"); return e ? atoi(e) : 0; }();
-    const dim3 g8(ceil_div(p.Tq, 256), p.H, p.B);
-    // CD_ATTN_TIME=1: kernel time of every launch by events on its stream (printed; the probe build is never the product)
-    static const bool timed = getenv("CD_ATTN_TIME") != nullptr;
-    struct Timer {
-      hipStream_t st; bool on; hipEvent_t e0, e1;
-      Timer(hipStream_t s, bool o) : st(s), on(o) { if (on) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, st); } }
-      ~Timer() {
-        if (!on) return;
-        hipEventRecord(e1, st); hipEventSynchronize(e1);
-        float ms = 0; hipEventElapsedTime(&ms, e0, e1);
-        printf("[attn d40 w8 dbg %d] %.1f us\n", dbg, ms * 1e3f);
-        hipEventDestroy(e0); hipEventDestroy(e1);
-      }
-    } timer(st, timed);
-#define CD_ATTN_DBG_CASE(V) case V: hipLaunchKernelGGL((k_attention<48, 64, 40, 2, false, 32, 8, V>), g8, dim3(512), 0, st, p); return;
-    switch (dbg) {
-      CD_ATTN_DBG_CASE(1) CD_ATTN_DBG_CASE(2) CD_ATTN_DBG_CASE(3) CD_ATTN_DBG_CASE(8) CD_ATTN_DBG_CASE(16) CD_ATTN_DBG_CASE(32)
-      CD_ATTN_DBG_CASE(48) CD_ATTN_DBG_CASE(64) CD_ATTN_DBG_CASE(72) CD_ATTN_DBG_CASE(75) CD_ATTN_DBG_CASE(51)
-      default: break;
-    }
-#undef CD_ATTN_DBG_CASE
-#endif
-    // round 5: the LDS-DMA / 16-row-block form (k_attention_d40); CD_ATTN_D40=0 selects the round-3 kernel for A/B runs
-    static const bool d40_new = [] { const char* e = getenv("CD_ATTN_D40"); return !(e && e[0] == '0'); }();
+  // 64-key groups at three: profiles/r2b_attention_v_layouts.txt)
+  if (p.D == 40 && p.Tq >= 1024 && p.Tk >= 1024 && p.vt) {
+    // the long self-attention of the 64 x 64 level: 256-query workgroups (8 waves), the LDS-DMA / 16-row-block form
+    // (k_attention_d40) where the launch meets
     // what the kernel's 16-byte accesses and its ragged last key tile assume (round-5 advisor): V^T rows padded to whole
     // 64-key tiles (a tighter pad would let the last tile of one d row read the next row's data), q / k / V^T row strides
     // and base pointers on 16-byte boundaries; anything else takes the round-3 kernel
     const bool aligned16 = ((((uintptr_t)p.q | (uintptr_t)p.k | (uintptr_t)p.vt | (uintptr_t)p.o) & 15) == 0) &&
                            (p.ldq % 8) == 0 && (p.ldk % 8) == 0 && (p.ldo % 8) == 0 && (p.q_bs % 8) == 0 && (p.k_bs % 8) == 0 &&
                            (p.o_bs % 8) == 0;
-    if (d40_new && p.vt_dpad >= 40 && aligned16 && (p.vt_tpad % 8) == 0 && p.vt_tpad >= ceil_div(p.Tk, 64) * 64 &&
+    if (p.vt_dpad >= 40 && aligned16 && (p.vt_tpad % 8) == 0 && p.vt_tpad >= ceil_div(p.Tk, 64) * 64 &&
         (int64_t)p.Tk * p.ldk * 2 < (1ll << 31) && (int64_t)p.vt_dpad * p.vt_tpad * 2 < (1ll << 31))
       hipLaunchKernelGGL((k_attention_d40<8>), dim3(ceil_div(p.Tq, 256), p.H, p.B), dim3(512), 0, st, p);
     else
       hipLaunchKernelGGL((k_attention<48, 64, 40, 2, false, 32, 8>), dim3(ceil_div(p.Tq, 256), p.H, p.B), dim3(512), 0, st,
                          p);
-  } else if (p.D == 40 && half_groups) CD_ATTN_KG(48, 64, 40, 2, 32);
-  else if (p.D == 40) CD_ATTN(48, 64, 40, 2);
-  else if (p.D == 80 && half_groups) CD_ATTN_KG(80, 96, 80, 2, 32);  // 640-channel level: three waves per SIMD
-  else if (p.D == 80) CD_ATTN(80, 96, 80, 2);
+  } else if (p.D == 40) CD_LAUNCH_KG(48, 64, 40, 2, 32);
+  else if (p.D == 80) CD_LAUNCH_KG(80, 96, 80, 2, 32);  // 640-channel level: three waves per SIMD
   else if (p.D <= 32) CD_ATTN(32, 32, 0, 2);
   else if (p.D <= 48) CD_ATTN(48, 64, 0, 2);
   else if (p.D <= 64) CD_ATTN(64, 64, 0, 2);
@@ -891,7 +846,7 @@ void launch_attention(hipStream_t st, const AttnParams& p) {
   else if (p.D <= 128) CD_ATTN(128, 128, 0, 1);
   else CD_ATTN(160, 160, 0, 1);
 #undef CD_ATTN
-#undef CD_ATTN_KG
+#undef CD_LAUNCH_KG
 }
 
 void launch_transpose_v(hipStream_t st, const bf16_t* v, int ldv, int64_t v_bs, bf16_t* vt, int B,

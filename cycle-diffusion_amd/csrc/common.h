@@ -80,7 +80,7 @@ __device__ inline void unpack8(const uint4& raw, float* f) {
 #endif
 
 __device__ inline uint32_t pack2(float lo, float hi) {
-#if CD_ACT_FP16 && defined(__HIP_DEVICE_COMPILE__) && !defined(CD_PACK8_F2BF)  // two v_med3_f32 + one v_cvt_pk_f16_f32 (see pack8)
+#if CD_ACT_FP16 && defined(__HIP_DEVICE_COMPILE__)  // two v_med3_f32 + one v_cvt_pk_f16_f32 (see pack8)
   typedef __attribute__((ext_vector_type(2))) _Float16 h2;
   const h2 v = {(_Float16)__builtin_amdgcn_fmed3f(lo, -65504.0f, 65504.0f),
                 (_Float16)__builtin_amdgcn_fmed3f(hi, -65504.0f, 65504.0f)};
@@ -113,7 +113,7 @@ constexpr uint32_t kOnePair = 0x3F803F80u;
 // every k_conv_gemm tile spends 13-40 % of its time in its row passes). Same bits as f2bf for every non-NaN input; a NaN
 // saturates instead of passing through.
 __device__ inline uint4 pack8(const float* f) {
-#if CD_ACT_FP16 && defined(__HIP_DEVICE_COMPILE__) && !defined(CD_PACK8_F2BF)  // (-DCD_PACK8_F2BF: the old form, A/B builds only)
+#if CD_ACT_FP16 && defined(__HIP_DEVICE_COMPILE__)
   typedef __attribute__((ext_vector_type(2))) _Float16 h2;
   uint32_t w[4];
 #pragma unroll
@@ -165,16 +165,6 @@ __device__ inline float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.7
 // Measured against fp64 erf over [-12, 12]: |error| <= 3.4e-7 absolute.
 __device__ inline float gelu_fast(float x) {
 #pragma clang fp contract(off)  // the same bits wherever it is inlined (conv_gemm.hip and lin_stream.hip must agree)
-#ifdef CD_GELU_SELECT_FORM  // rounds 3-5: 0.5 x (x < 0 ? q : 2 - q), 16 operations (A/B builds only: build.py --geluold)
-  const float z = fabsf(x) * 0.70710678118654752440f;
-  const float tt = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, z, 1.0f));
-  float pp = __builtin_fmaf(tt, 1.061405429f, -1.453152027f);
-  pp = __builtin_fmaf(tt, pp, 1.421413741f);
-  pp = __builtin_fmaf(tt, pp, -0.284496736f);
-  pp = __builtin_fmaf(tt, pp, 0.254829592f);
-  const float q = pp * tt * __builtin_amdgcn_exp2f(-z * z * 1.44269504088896340736f);
-  return 0.5f * x * (x < 0.0f ? q : 2.0f - q);
-#endif
   const float ax = fabsf(x);
   const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.231641888f, ax, 1.0f));  // 0.3275911 / sqrt 2
   float poly = __builtin_fmaf(t, 0.5307027145f, -0.7265760135f);                   // A-S coefficients, halved

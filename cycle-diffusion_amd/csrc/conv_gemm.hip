@@ -33,15 +33,6 @@ namespace cd {
 
 namespace gemm_detail {
 
-// cache-policy bits of the fast epilogue's output stores / residual loads (2 = nt: streaming). A/B builds only
-// (build.py --ntst / --ntld): measured round 6, see docs/optimisation_log.md
-#ifndef CD_EPI_STORE_AUX
-#define CD_EPI_STORE_AUX 0
-#endif
-#ifndef CD_EPI_RESID_AUX
-#define CD_EPI_RESID_AUX 0
-#endif
-
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
@@ -90,25 +81,6 @@ __device__ __forceinline__ void wait_vmcnt_barrier() {
   asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
-#ifdef CD_PROBE
-// Phase-timing instrumentation (probe build only): s_memtime stamps kept in SGPRs, sums formed on the scalar unit; the
-// stamp sits where no LDS read is outstanding (top / bottom of a K step), so its lgkmcnt(0) costs nothing extra.
-__device__ __forceinline__ unsigned long long probe_time() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-// the 100 MHz reference clock: the same origin on every CU (s_memtime counters are per-CU), calibrates ticks -> us
-__device__ __forceinline__ unsigned long long probe_realtime() {
-  unsigned long long t;
-  asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-#define CD_PROBE_ONLY(...) __VA_ARGS__
-#else
-#define CD_PROBE_ONLY(...)
-#endif
-
 // A buffer descriptor for the epilogue. The words go through v_readfirstlane: behind the split-K fix-up's data-dependent return
 // the compiler no longer treats them as wave-uniform and would wrap every buffer operation in a waterfall loop.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* base, int bytes) {
@@ -140,31 +112,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
-  // (launch_bounds below) two workgroups per CU: de-phase them once per launch, see ConvGemmParams::dephase_ticks
-  if constexpr (WM * WN == 4 && BK == 32 && NSTAGE == 3 && BM * BN >= 128 * 256) {
-    if (p.dephase_ticks > 0 && (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) < 2 * p.num_cus) {
-      unsigned hwid;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-      if (tid == 0) *(volatile int*)smem = (int)(hwid & 1u);  // wave slot of wave 0: the second workgroup of a SIMD sits in slot 1
-      __syncthreads();
-      const int odd = *(volatile int*)smem;
-      __syncthreads();
-      if (odd) {
-        unsigned long long t0, t1;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0)::"memory");
-        do {
-          __builtin_amdgcn_s_sleep(32);
-          asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t1)::"memory");
-        } while ((long long)(t1 - t0) < (long long)p.dephase_ticks);
-      }
-    }
-  }
-  CD_PROBE_ONLY(
-  const unsigned long long pr_rt0 = probe_realtime();
-  unsigned long long pr_t0 = probe_time(), pr_prol = 0, pr_first = 0, pr_wait = 0, pr_comp = 0, pr_maxw = 0, pr_loop = 0,
-                     pr_drain = 0, pr_stage = 0, pr_rows = 0, pr_issued = 0, pr_last = 0;
-  unsigned* pr_log = (unsigned*)(smem + T::LDS_BYTES + T::TAB_BYTES) + wave * 64;  // (arrive, pass) of the first 32 K steps
-  if (lane < 64) pr_log[lane] = 0;)
 
   // ---- block -> tile, XCD-aware (block b runs on XCD b%8; give each XCD a contiguous tile range
   // so neighbouring n-tiles of one m-tile share the A panel in that XCD's L2)
@@ -208,7 +155,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
   const bool pow2 = ((HWo & (HWo - 1)) == 0) && ((p.Wout & (p.Wout - 1)) == 0);
   const int sh_hw = 31 - __builtin_clz(HWo), sh_w = 31 - __builtin_clz(p.Wout);
   int b_first = pow2 ? (m0 >> sh_hw) : (m0 / HWo);
-  CD_PROBE_ONLY(if (p.dbg & 4) b_first = 0;)
   // phase form of the x2 convs (ConvGemmParams::up_phase): the rows' "sample" index is (image, phase); the tile lies in one
   // phase of one image, whose parity (a, b) moves the first tap and selects the weight matrix (all uniform)
   int pad_t = p.pad_t, pad_l = p.pad_l, w_ph = 0;
@@ -237,7 +183,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
   for (int i = 0; i < A_IPW; ++i) {
     const int row = (i * NW + wave) * RPI + srow;
     int m = m0 + row;
-    CD_PROBE_ONLY(if (p.dbg & 4) m = (m0 & 0x3ff) + row;)  // timing experiment: every tile gathers A from the first images (L2-hot)
     a_lc8[i] = (pchunk ^ ((row >> T::SWZ_SHIFT) & (CPR - 1))) * 8;
     a_voff[i] = kInvalid;
     a_mk[i] = 0; a_base[i] = 0;
@@ -446,10 +391,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
       }
     }
   }
-  CD_PROBE_ONLY(pr_prol = probe_time(); pr_last = pr_prol;)
   static_assert((NSTAGE - 1) * LPT + TABI <= 63, "vmcnt field");
   wait_vmcnt_barrier<(NSTAGE - 1) * LPT + TABI>();  // tile kt0 has landed everywhere (younger: the other tiles, the table copies)
-  CD_PROBE_ONLY(pr_first = probe_time(); pr_last = pr_first;)
 
   bf16x8 af[KS][MT], bfr[KS][NT];
   auto read_frags = [&](int slot, int ks) {
@@ -486,15 +429,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
       };
       if (ks == SYNC) {
         mfma_range(0, HALF);
-        CD_PROBE_ONLY(const unsigned long long pr_arr = probe_time();)
         // own LDS reads of tile kt done, own pieces of tile kt+1 landed ((NSTAGE-2) younger tiles may fly) -> barrier
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((NSTAGE - 2) * LPT) : "memory");
-        CD_PROBE_ONLY({
-          const unsigned long long now = probe_time();
-          pr_comp += pr_arr - pr_last; pr_wait += now - pr_arr; if (now - pr_arr > pr_maxw) pr_maxw = now - pr_arr;
-          if (kt - kt0 < 32 && lane == 0) { pr_log[2 * (kt - kt0)] = (unsigned)(pr_arr - pr_t0); pr_log[2 * (kt - kt0) + 1] = (unsigned)(now - pr_t0); }
-          pr_last = now;
-        })
         prepare(kt + NSTAGE);
         fill = cur;
 #pragma unroll
@@ -514,10 +450,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
     }
     cur = nslot;
   }
-  CD_PROBE_ONLY(pr_loop = probe_time(); pr_comp += pr_loop - pr_last;)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the dummy tail loads before LDS is reused
   __syncthreads();  // all waves done with the ring before the epilogue reuses LDS
-  CD_PROBE_ONLY(pr_drain = probe_time();)
 
   // ---- split-K fix-up: every split stores its fp32 partial tile (register layout, coalesced), the last
   // one to arrive sums all partials in split order (so the result does not depend on arrival order) and
@@ -640,7 +574,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
       const unsigned vo = nx < p.N ? (unsigned)(((rbx * 32 + lane_ep / vprx) * p.resid_ld + nx) * 2) : kInvalid;
 #pragma unroll
       for (int ps = 0; ps < 4; ++ps)
-        if (ps < npx) dst[ps] = __builtin_amdgcn_raw_buffer_load_b128(rs_r, vo + (unsigned)(ps * rppx * p.resid_ld * 2), 0, CD_EPI_RESID_AUX);
+        if (ps < npx) dst[ps] = __builtin_amdgcn_raw_buffer_load_b128(rs_r, vo + (unsigned)(ps * rppx * p.resid_ld * 2), 0, 0);
     };
     if constexpr (PIPE) resid_issue(0, 0, rq[0]);
 #pragma unroll
@@ -650,7 +584,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
       const int RPP = 64 / (cw / 8), NP = 32 / RPP;    // rows per pass, passes per 32-row block
       const int vr = lane_ep / (cw / 8), col = (lane_ep % (cw / 8)) * 8;  // row within a pass, column inside the chunk
       const int n = n0 + wn * TN + jc * 32 + col;
-      CD_PROBE_ONLY(const unsigned long long pr_c0 = probe_time();)
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
       for (int i = 0; i < MT; ++i)
@@ -664,7 +597,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
             }
           }
       __builtin_amdgcn_wave_barrier();
-      CD_PROBE_ONLY(const unsigned long long pr_c1 = probe_time(); pr_stage += pr_c1 - pr_c0;)
       const f32x4 b0 = *(const f32x4*)(TB + jc * 32 + col), b1 = *(const f32x4*)(TB + jc * 32 + col + 4);
       const unsigned vo_out = n < p.N ? (unsigned)((vr * p.out_ld + n) * 2) : kInvalid;  // + the pass's row offset
 #pragma unroll
@@ -707,9 +639,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
               for (int e = 0; e < 8; ++e) vp[e] += rf[e];
             }
             const uint4 pk = pack8(vp);
-            CD_PROBE_ONLY(if (!(p.dbg & 1)))
             __builtin_amdgcn_raw_buffer_store_b128((u32x4e){pk.x, pk.y, pk.z, pk.w}, rs_o,
-                                                   vo_blk + (unsigned)(ps * RPP * p.out_ld * 2), 0, CD_EPI_STORE_AUX);
+                                                   vo_blk + (unsigned)(ps * RPP * p.out_ld * 2), 0, 0);
             if constexpr (!KEEP) {
               const float on = (mb + ps * RPP + vr) < p.M ? 1.0f : 0.0f;
 #pragma unroll
@@ -769,14 +700,12 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
           }
         }
       }
-      CD_PROBE_ONLY(pr_rows += probe_time() - pr_c1;)
     }
   } else {
 #pragma unroll
     for (int jc = 0; jc < NT; jc += CJ) {
       const int cj = (NT - jc) < CJ ? (NT - jc) : CJ;  // blocks in this chunk (compile-time after unrolling)
       const int cw = cj * 32;
-      CD_PROBE_ONLY(const unsigned long long pr_c0 = probe_time();)
       __builtin_amdgcn_wave_barrier();
 #pragma unroll
       for (int i = 0; i < MT; ++i)
@@ -790,7 +719,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
             }
           }
       __builtin_amdgcn_wave_barrier();
-      CD_PROBE_ONLY(const unsigned long long pr_c1 = probe_time(); pr_stage += pr_c1 - pr_c0;)
       // GEGLU: packed columns come in blocks of 64 = [32 value | 32 gate] (k_pack_rows) = one chunk; only the value
       // half produces output, at column (n/64)*32 + n%32.
       const int vpr = geglu ? 4 : (cw / 8);  // 8-wide vectors per row handled
@@ -843,12 +771,10 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
             }
             mul_gelu8(va, ga, v);
             const uint4 pk = pack8(v);
-            CD_PROBE_ONLY(if (!(p.dbg & 1)))
             __builtin_amdgcn_raw_buffer_store_b128((u32x4e){pk.x, pk.y, pk.z, pk.w}, rs_o,
                                                    vo_out + (unsigned)((rb * 32 + ps * 16) * p.out_ld * 2), 0, 0);
           }
         }
-        CD_PROBE_ONLY(pr_rows += probe_time() - pr_c1;)
         continue;
       }
       float bias_v[8];
@@ -936,7 +862,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
             for (int e = 0; e < 8; ++e) if (e < nvalid) v[e] += bf2f(rp[e]);
           }
         }
-        CD_PROBE_ONLY(if (!(p.dbg & 1)))
         if (p.out_f32) {
           float* op = (float*)outp + (int64_t)m * p.out_ld + on;
           if (nvalid == 8 && ((p.out_ld & 3) == 0)) {
@@ -955,7 +880,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
             for (int e = 0; e < 8; ++e) if (e < nvalid) op[e] = f2bf(v[e]);
           }
         }
-        CD_PROBE_ONLY(if (p.dbg & 1) { if (v[0] == 1.2345e-33f) ((float*)outp)[0] = v[1] + v[2] + v[3] + v[4] + v[5] + v[6] + v[7]; })
         if (p.stats) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) { ssum[e] += v[e]; ssq[e] += v[e] * v[e]; }
@@ -977,26 +901,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4 && BK == 32 && NSTAGE =
           for (int e = 0; e < 8; ++e) { ssum[e] = 0.f; ssq[e] = 0.f; }
         }
       }
-      CD_PROBE_ONLY(pr_rows += probe_time() - pr_c1;)
     }
   }
-  CD_PROBE_ONLY({
-    pr_issued = probe_time();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long pr_done = probe_time();
-    if (p.probe) {
-      unsigned hwid, xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      unsigned long long* o = p.probe + ((size_t)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * NW + wave) * kProbeWords;
-      if (lane == 0) {
-        o[0] = pr_t0; o[1] = pr_prol; o[2] = pr_first; o[3] = pr_wait; o[4] = pr_comp; o[5] = pr_maxw; o[6] = pr_loop;
-        o[7] = pr_drain; o[8] = pr_stage; o[9] = pr_rows; o[10] = pr_issued; o[11] = pr_done; o[12] = kt1 - kt0;
-        o[13] = ((unsigned long long)xcc << 32) | hwid; o[14] = pr_rt0; o[15] = probe_realtime();
-      }
-      ((unsigned*)(o + 16))[lane] = pr_log[lane];  // the log lies beyond the tile's LDS: the epilogue did not touch it
-    }
-  })
 #endif  // __HIP_DEVICE_COMPILE__
 }
 
@@ -1013,11 +919,7 @@ int launch_cfg(hipStream_t st, const ConvGemmParams& p) {
   using T = TileCfg<BM, BN, BK, WM, WN, NSTAGE>;
   const int tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
   const int split = p.splitk > 1 ? p.splitk : 1;
-#ifdef CD_PROBE
-  constexpr int kLds = T::LDS_BYTES + T::TAB_BYTES + T::NW * 256;  // + the per-wave stamp log
-#else
   constexpr int kLds = T::LDS_BYTES + T::TAB_BYTES;
-#endif
   // channel-major K order (ConvGemmParams::korder): 3 x 3 .. 8 x 8 filters without upsampling; everything else - 1 x 1, the
   // CLIP patch embeddings, the nearest-x2 convs - runs the tap-major instantiation
   // ... and only where it pays: the tap re-reads of a LARGE activation (>= 64 x 64 per sample, >= 32 MiB in all: the 64 x 64
@@ -1085,7 +987,6 @@ inline bool cfg_always_bk32(int id) { return id == 24 || id == 25; }
 
 }  // namespace gemm_detail
 thread_local SplitKWorkspace g_conv_splitk;
-thread_local unsigned long long* g_conv_probe = nullptr;
 namespace gemm_detail {
 
 template <int BK>
@@ -1390,7 +1291,6 @@ void launch_conv_gemm(hipStream_t st, const ConvGemmParams& p) {
   if ((id >> 8) > 1) pk.splitk = id >> 8;  // from the tuner, or packed into an explicit `tile` (tests, sweeps)
   id &= 0xff;
   if (pk.splitk > 1 && !pk.sk_scratch) { pk.sk_scratch = g_conv_splitk.scratch; pk.sk_flags = g_conv_splitk.flags; }
-  pk.probe = g_conv_probe;
   static const int korder_env = [] { const char* e = getenv("CYCLEDIFF_KORDER"); return e ? atoi(e) : -1; }();
   if (korder_env >= 0) pk.korder = korder_env;
   // grouped tile walk for wide-N contractions (>= CYCLEDIFF_TILE_GROUP_MIN_N column tiles of 256): both operands exceed an
@@ -1402,13 +1302,6 @@ void launch_conv_gemm(hipStream_t st, const ConvGemmParams& p) {
   static const int tg_env = [] { const char* e = getenv("CYCLEDIFF_TILE_GROUP"); return e ? atoi(e) : 8; }();
   static const int tg_min_n = [] { const char* e = getenv("CYCLEDIFF_TILE_GROUP_MIN_N"); return e ? atoi(e) : 2048; }();
   if (tg_env > 0 && p.N >= tg_min_n && p.nbatch == 1) pk.tile_group = tg_env;
-#ifdef CD_PROBE
-  if (const char* e = getenv("CYCLEDIFF_PROBE_DBG")) pk.dbg = atoi(e);
-  static const int dephase_env = [] { const char* e = getenv("CYCLEDIFF_DEPHASE_TICKS"); return e ? atoi(e) : 0; }();
-  pk.dephase_ticks = dephase_env;
-  pk.num_cus = device_cu_count();
-  if (pk.dbg & 2) pk.stats = nullptr;
-#endif
   static const CfgInfo kLinStreamCfg = {kLinStreamTile, 256, 64, 64, "lin_stream 256 x N, K = 320"};
   const CfgInfo* ci = nullptr;
   if (id == kLinStreamTile) {

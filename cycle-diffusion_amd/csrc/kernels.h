@@ -205,9 +205,6 @@ struct ConvGemmParams {
   int splitk = 0;
   float* sk_scratch = nullptr;    // defaults to g_conv_splitk when splitk > 1
   int* sk_flags = nullptr;
-  // phase-timing build only (-DCD_PROBE, lib/libcyclediff_probe.so; scripts/probe_report.py): every wave leaves
-  // kProbeWords 64-bit words of s_memtime stamps here, [block][wave][kProbeWords]; null = off
-  unsigned long long* probe = nullptr;
   // order of the K steps of a KH x KW > 1 convolution: tap-major (all channels of a filter tap, then the next tap) or
   // channel-major (the KH * KW taps of one BK-channel slice, then the next slice: the re-reads of an activation line by
   // neighbouring taps follow each other within KH * KW steps and hit the XCD's L2 - round 4: hit rate 54 -> 72 %, fabric fetch
@@ -218,13 +215,6 @@ struct ConvGemmParams {
   // G > 0 = groups of G row tiles walked m-fastest (the 32 CUs of an XCD then run G row tiles x 32 / G column tiles at a time:
   // G A panels + 32 / G W panels in its L2 instead of 1 + 32) - for the wide-N layers whose operands both exceed the L2
   int tile_group = 0;
-  // two-per-CU tile configurations (24, 25) only: the workgroups of the launch's first wave front that sit in an odd wave slot
-  // wait this many shader cycles before they start, so that the two co-resident workgroups of a CU run half a tile apart (one's
-  // prologue / epilogue under the other's K loop). 0 = off. Experiment of round 6 (CYCLEDIFF_DEPHASE_TICKS), docs/optimisation_log.md
-  int dephase_ticks = 0;
-  int num_cus = 256;
-  int dbg = 0;  // probe build: 1 = the epilogue skips its global stores, 2 = skips the statistics, 4 = every tile gathers
-                // its A rows from the first 1024 + BM rows (an L2-resident operand: what would the K loop do without misses?)
   // 1: the nearest-x2 3 x 3 convolution in its phase form. After the x2 replication only 2 x 2 stored
   // pixels feed an output pixel, so the taps that share one are summed ahead of time (launch_up_phase_weights): four 2 x 2
   // convs on the stored grid, one per output parity (a, b), K = 4 C instead of 9 C. GEMM row m = (image, phase = 2 a + b,
@@ -235,8 +225,6 @@ struct ConvGemmParams {
   int up_phase = 0;
   int w_ps = 0;  // element stride between the four phase matrices
 };
-constexpr int kProbeWords = 48;
-extern thread_local unsigned long long* g_conv_probe;  // picked up by launch_conv_gemm in the probe build
 struct SplitKWorkspace {
   float* scratch = nullptr;
   size_t scratch_bytes = 0;
@@ -274,7 +262,6 @@ struct LinStreamParams {
   float* stats = nullptr;
   int M = 0, N = 0;
   float ln_eps = 1e-5f;  // LayerNorm-folded variants
-  int geglu_direct = 0;  // GEGLU epilogue straight from the accumulators (no LDS transpose), lin_stream.hip
   // V^T variants (the q | k | v projection of the 64 x 64 transformer blocks): packed columns [nsplit, N) leave
   // untransposed into vt[row / hw][column - nsplit][vt_ld], token row % hw; nsplit % 64 == 0, hw % 256 == 0
   int nsplit = 0, hw = 0;

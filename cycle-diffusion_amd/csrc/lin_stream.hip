@@ -45,7 +45,6 @@ constexpr int OFF_A = WSLOTS * WPIECE, OFF_ST = OFF_A + ASLOTS * APIECE, OFF_BIA
 constexpr int LDS_BYTES = OFF_BIAS + BIAS_MAX * 4;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS");
 constexpr unsigned kNoLoad = 0x80000000u;
-constexpr int kGegluDirectDefault = 1;  // LinStreamParams::geglu_direct unless CYCLEDIFF_GEGLU_DIRECT says otherwise
 
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (rounded DOWN to a multiple of 4: waiting for a few more
 // operations than necessary is always correct)
@@ -437,18 +436,17 @@ __global__ __launch_bounds__(512, 2) void k_lin_stream(LinStreamParams p) {
         wait_vmcnt_le(seq - rmark);
         touch4(rres[0], rres[1], rres[2], rres[3]);
       }
-      float vv[2][8];  // GEGLU: the value half waits for its gate
       int l2 = lane;
       asm volatile("" : "+v"(l2));  // as above: nothing lane-derived stays live across the MFMA loop
       const int prow = l2 >> 2, pcol = (l2 & 3) * 8, mi2 = l2 & 31, half2 = l2 >> 5;
       const unsigned o_lane = (unsigned)(((wave * 32 + prow) * p.ldo + pcol) * 2);
-      if (GEGLU && p.geglu_direct) {
+      if constexpr (GEGLU) {
         // GEGLU straight from the accumulators: value (acc[0]) and gate (acc[1]) of an output element sit in the same
         // register of the same lane, so the tile needs no transpose - the LDS round trip of the staged form (4 writes,
         // a wait, 4 reads per column block, each behind the other) is this epilogue's critical path, not its VALU count
         // (round 6: running the SIMD's two waves' epilogues one after the other instead of against each other LOST 5 %).
         // A lane stores 4 consecutive columns of its row per register quad (8 bytes; lanes l and l + 32 are neighbours).
-        // Same operations per element as the staged form (bias add, gelu_fast2 on column pairs, product, one rounding).
+        // Same operations per element as the tile kernels' GEGLU epilogue (bias add, gelu_fast2 on column pairs, product, one rounding).
         const unsigned od_lane = (unsigned)(((wave * 32 + mi2) * p.ldo + 4 * half2) * 2);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -516,39 +514,25 @@ __global__ __launch_bounds__(512, 2) void k_lin_stream(LinStreamParams p) {
           const f32x4 lo = *(const f32x4*)srow, hi = *(const f32x4*)(srow + 4);
           float v[8] = {lo[0] + b0[0], lo[1] + b0[1], lo[2] + b0[2], lo[3] + b0[3],
                         hi[0] + b1[0], hi[1] + b1[1], hi[2] + b1[2], hi[3] + b1[3]};
-          if (GEGLU) {
-            if (nb == 0) {
+          if (RESID && rows_ok) {
+            float rr[8];
+            unpack8(__builtin_bit_cast(uint4, rres[nb * 2 + ps]), rr);
 #pragma unroll
-              for (int e = 0; e < 8; ++e) vv[ps][e] = v[e];
-            } else {
-              mul_gelu8(vv[ps], v, v);
-              if (rows_ok) {
-                const uint4 o = pack8_sat(v);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs_o, o_lane,
-                                                       ((row0 + 16 * ps) * p.ldo + t * 32) * 2, 0);
-              }
-            }
-          } else {
-            if (RESID && rows_ok) {
-              float rr[8];
-              unpack8(__builtin_bit_cast(uint4, rres[nb * 2 + ps]), rr);
-#pragma unroll
-              for (int e = 0; e < 8; ++e) v[e] += rr[e];
-            }
-            if (rows_ok) {
-              const uint4 o = pack8_sat(v);
-              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs_o, o_lane,
-                                                     ((row0 + 16 * ps) * p.ldo + ncol0) * 2, 0);
-            }
-            if (STATS) {  // the final fp32 values go back to the transpose buffer for the column sums below
-              *(f32x4*)srow = (f32x4){v[0], v[1], v[2], v[3]};
-              *(f32x4*)(srow + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-              // retire these stores before their source registers are reused: on hardware, without this wait, a few
-              // waves per launch stored a wrong third dword in the NEXT pass (lanes 12-15 of every 16, this column
-              // block only) although the instruction stream is correct - the following ds_read_b128 lands in the
-              // registers the pending ds_write_b128 takes its data from (profiles/r3_lds_store_hazard_bisection.txt)
-              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            }
+            for (int e = 0; e < 8; ++e) v[e] += rr[e];
+          }
+          if (rows_ok) {
+            const uint4 o = pack8_sat(v);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rs_o, o_lane,
+                                                   ((row0 + 16 * ps) * p.ldo + ncol0) * 2, 0);
+          }
+          if (STATS) {  // the final fp32 values go back to the transpose buffer for the column sums below
+            *(f32x4*)srow = (f32x4){v[0], v[1], v[2], v[3]};
+            *(f32x4*)(srow + 4) = (f32x4){v[4], v[5], v[6], v[7]};
+            // retire these stores before their source registers are reused: on hardware, without this wait, a few
+            // waves per launch stored a wrong third dword in the NEXT pass (lanes 12-15 of every 16, this column
+            // block only) although the instruction stream is correct - the following ds_read_b128 lands in the
+            // registers the pending ds_write_b128 takes its data from (profiles/r3_lds_store_hazard_bisection.txt)
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
           }
           __builtin_amdgcn_sched_barrier(0);  // one (column block, pass) at a time: the temporaries must not pile up
         }
@@ -723,9 +707,6 @@ void launch_lin_stream(hipStream_t st, const ConvGemmParams& c) {
   p.resid = c.resid; p.ldr = c.resid_ld; p.out = (bf16_t*)c.out; p.ldo = c.out_ld;
   p.stats = c.stats; p.M = c.M; p.N = c.N;
   const int grid = lin_stream_grid(p.M);
-  // CYCLEDIFF_GEGLU_DIRECT=0 / 1 (A/B runs): the staged / the straight-from-the-accumulators GEGLU epilogue
-  static const int geglu_direct = [] { const char* e = getenv("CYCLEDIFF_GEGLU_DIRECT"); return e && e[0] ? atoi(e) : kGegluDirectDefault; }();
-  p.geglu_direct = geglu_direct;
   if (c.ln_fold) {  // LayerNorm folded in: the feed-forward GEGLU projection and the plain projections behind norm1-3
     p.ln_eps = c.ln_eps;
     CD_CHECK(!c.resid && !c.stats, "lin_stream: a LayerNorm-folded layer has neither residual nor statistics");

@@ -93,8 +93,8 @@ class UNetOpenAI : public UNet {
   // (UNetIO::dup_tail; a classifier-free-guidance batch is dup_tail = x.B); everything ahead of the cross-attention runs on
   // x, then the token stream and the block input get the repeated samples appended and the rest runs on x.B + dup_tail
   Act st_fwd(Ctx& c, STW& s, const Act& x, int dup_tail = 0);
-  // the block on images [b0, b0 + x.B) of the batch the context was set for, into the caller's output rows
-  void st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x_resid, Act& out, int b0, int dup_tail);
+  // the 16-bit path of the block, into the caller's output rows
+  void st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x_resid, Act& out, int dup_tail);
   Act ab_fwd(Ctx& c, const ABW& a, const Act& x);
  public:
   ~UNetOpenAI() override { for (void* p : ctx_allocs_) (void)hipFree(p); }
@@ -511,42 +511,19 @@ Act UNetOpenAI::st_fwd(Ctx& c, STW& s, const Act& x_in, int dup_tail) {
     c.arena->release(mk);
     return out;
   }
-  // 16-bit path. Every image is independent through the whole block: at the 64 x 64 level a large batch runs depth-first in
-  // chunks of ST_CHUNK images, so that the chunk's token tensors (42 MB per 320-channel tensor and 16 images, 168 MB for the
-  // GEGLU hidden tensor) stay in the 256 MB Infinity Cache between the block's ~15 kernels instead of making an HBM round
-  // trip each - the N = K = 320 projections, the norm passes and the feed-forward pair are bound by exactly those trips
-  // (DESIGN.md 8). Chunks of 16 images are 65 536 rows: 256 strips / row tiles, one full round of the chip per kernel.
-  static const int st_chunk = [] { const char* e = getenv("CYCLEDIFF_ST_CHUNK"); return e ? atoi(e) : 0; }();
   c.arena->release(mk);
-  if (!dup && !ctrl_ && st_chunk > 0 && T >= 4096 && B >= 2 * st_chunk) {
-    for (int b0 = 0; b0 < B; b0 += st_chunk) {
-      const int n = std::min(st_chunk, B - b0);
-      auto view = [&](const Act& a) {
-        Act v = a; v.B = n;
-        v.p = a.p + (int64_t)b0 * T * a.ld;
-        if (a.stats) v.stats = a.stats + ((int64_t)b0 * T / 32) * 2 * a.C;
-        if (a.stats_buf) v.stats_buf = a.stats_buf + ((int64_t)b0 * T / 32) * 2 * a.C;
-        return v;
-      };
-      Act xv = view(x_in), ov = view(out);
-      st_core16(c, s, xv, xv, ov, b0, 0);
-    }
-  } else {
-    st_core16(c, s, x_in, x, out, 0, dup_tail);
-  }
+  st_core16(c, s, x_in, x, out, dup_tail);  // 16-bit path
   out.stats = out.stats_buf;
   return out;
 }
 
-void UNetOpenAI::st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x, Act& out, int b0, int dup_tail) {
+void UNetOpenAI::st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x, Act& out, int dup_tail) {
   const bool dup = dup_tail > 0;
   int B = x_in.B;
   const int T = x_in.H * x_in.W, C = s.C;
   const size_t mk = c.arena->mark();
   ConvOpts p0; p0.pad = 0;
   const float scale = 1.0f / sqrtf((float)s.dh);
-  const bf16_t* k2c = s.k2c + (int64_t)b0 * ctx_L_ * C;
-  const bf16_t* v2c = s.v2c + (int64_t)b0 * ctx_L_ * C;
   const int entry_stages = x_in.rows() >= kStEntryNetMinRows ? st_entry_stages() : 0;
   Act h;
   if (s.qkv1) {
@@ -591,17 +568,17 @@ void UNetOpenAI::st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x, Act& o
     }
     Act a;
     if (!ctrl_) {
-      a = attention_fwd(c, q.p, q.ld, k2c, C, v2c, C, B, s.heads, T, ctx_L_, s.dh, scale, x.H, x.W, /*q_log2=*/true);
+      a = attention_fwd(c, q.p, q.ld, s.k2c, C, s.v2c, C, B, s.heads, T, ctx_L_, s.dh, scale, x.H, x.W, /*q_log2=*/true);
     } else {
       // cross-attention control: the uncontrolled rows [0, row0) run the same launch as above, the controlled rows - the tail of
       // the batch - k_cross_attention_ctrl; both write into one output tensor
       const int Bu = ctrl_->row0;
-      CD_CHECK(b0 == 0 && Bu + ctrl_->rows == B, "cross-attention control: rows %d + %d of a batch of %d", Bu, ctrl_->rows, B);
+      CD_CHECK(Bu + ctrl_->rows == B, "cross-attention control: rows %d + %d of a batch of %d", Bu, ctrl_->rows, B);
       const size_t bi = (size_t)(&s - st_.data());
       CD_CHECK(bi < ctrl_->va.size(), "cross-attention control: no values for transformer block %d", (int)bi);
       a = alloc_act(c, B, x.H, x.W, C);
       AttnParams pu;
-      pu.q = q.p; pu.k = k2c; pu.v = v2c; pu.o = a.p;
+      pu.q = q.p; pu.k = s.k2c; pu.v = s.v2c; pu.o = a.p;
       pu.B = Bu; pu.H = s.heads; pu.Tq = T; pu.Tk = ctx_L_; pu.D = s.dh;
       pu.ldq = q.ld; pu.ldk = C; pu.ldv = C; pu.ldo = a.ld;
       pu.q_bs = (int64_t)T * q.ld; pu.k_bs = (int64_t)ctx_L_ * C; pu.v_bs = (int64_t)ctx_L_ * C; pu.o_bs = (int64_t)T * a.ld;
@@ -609,7 +586,7 @@ void UNetOpenAI::st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x, Act& o
       launch_attention(c.st, pu);
       CtrlAttnParams p;
       p.q_own = q.p + (int64_t)Bu * pu.q_bs; p.q_src = q.p + (int64_t)ctrl_->src_b0 * pu.q_bs;
-      p.k_own = k2c + (int64_t)Bu * pu.k_bs; p.k_src = k2c + (int64_t)ctrl_->src_b0 * pu.k_bs;
+      p.k_own = s.k2c + (int64_t)Bu * pu.k_bs; p.k_src = s.k2c + (int64_t)ctrl_->src_b0 * pu.k_bs;
       p.va = ctrl_->va[bi]; p.vb = ctrl_->vb[bi]; p.o = a.p + (int64_t)Bu * pu.o_bs;
       p.B = ctrl_->rows; p.B_src = ctrl_->B_src; p.H = s.heads; p.Tq = T; p.L = ctx_L_; p.D = s.dh;
       p.ldq = q.ld; p.ldk = C; p.ldv = C; p.ldo = a.ld;

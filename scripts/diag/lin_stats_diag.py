@@ -37,6 +37,6 @@ for (B, H, W, has_res) in ((1, 32, 16, False), (2, 32, 32, True)):
                 B * H * W, has_res, tile, want, d.max().item(), len(rows), rows[:12].tolist(), len(cols), cols[:12].tolist())
             if want:
                 blocks = ref.permute(0, 2, 3, 1).reshape(-1, 32, N)
-                wantst = torch.stack([blocks.sum(1), (blocks * blocks).sum(1)], 1)
-                msg += "; stats rel err %.2e" % ((st - wantst).abs().max() / wantst.abs().max()).item()
+                want_st = torch.stack([blocks.sum(1), (blocks * blocks).sum(1)], 1)
+                msg += "; stats rel err %.2e" % ((st - want_st).abs().max() / want_st.abs().max()).item()
             print(msg, flush=True)

@@ -386,3 +386,19 @@ def test_main_fold_look_ahead_is_invariant_to_fold_and_sharding():
                             (1, 2, 3), (16, 1, 4), (1, 1, 7)):
         assert torch.equal(run(fold, world, bs), base), (fold, world, bs)
     assert pads and all(torch.equal(img, base[sid]) for sid, img in pads)
+
+
+def test_every_environment_switch_of_the_library_is_documented():
+    """Every name the C++ sources pass to getenv() is in INTEGRATION.md's "Environment switches" table: a switch
+    nobody can look up is one nobody dares to remove."""
+    import glob
+    import re
+    names = set()
+    for path in glob.glob(os.path.join(ROOT, "cycle-diffusion_amd", "csrc", "*")):
+        with open(path, encoding="utf-8") as f:
+            names.update(re.findall(r'getenv\(\s*"([^"]+)"', f.read()))
+    assert names  # the pattern still matches how the sources read their switches
+    with open(os.path.join(ROOT, "INTEGRATION.md"), encoding="utf-8") as f:
+        doc = f.read()
+    missing = sorted(n for n in names if "`%s`" % n not in doc)
+    assert not missing, "not in INTEGRATION.md: %s" % ", ".join(missing)
