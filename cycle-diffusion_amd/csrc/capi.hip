@@ -2212,4 +2212,47 @@ int cd_op_vq_quantize(cd_handle h, const float* z, float in_mul, const float* co
   CD_API_END
 }
 
+// ---- the implicit-GEMM kernel as the batched plain GEMM of the V^T / S = QK^T / O = PV call sites, on the caller's bytes:
+// one launch_conv_gemm whose parameters are filled the way those sites fill them (the launcher's own checks refuse a bad call)
+int cd_op_gemm_batched(cd_handle h, const void* a, int lda, int64_t a_bs, const void* w, int ldw, int64_t w_bs, int M, int N,
+                       int K, int nbatch, float alpha, const float* bias, const void* resid, int resid_ld, float* stats, int act,
+                       int tile, void* out, int out_ld, int64_t o_bs, int out_f32) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && a && w && out && M > 0 && N > 0 && K > 0 && nbatch > 0 && lda > 0 && ldw > 0 && out_ld > 0, "bad argument");
+  Ctx c = h->ctx();
+  ConvGemmParams p;
+  p.src0 = (const bf16_t*)a; p.C0 = K; p.ld0 = lda;
+  p.B = 1; p.Hs = M; p.Ws = 1; p.Hin = M; p.Win = 1; p.Hout = M; p.Wout = 1;
+  p.M = M;
+  p.wgt = (const bf16_t*)w; p.Ktot = K; p.ldw = ldw; p.N = N;
+  p.nbatch = nbatch; p.a_bs = a_bs; p.w_bs = w_bs; p.o_bs = o_bs;
+  p.alpha = alpha; p.bias = bias; p.resid = (const bf16_t*)resid; p.resid_ld = resid_ld; p.stats = stats; p.act = act;
+  p.tile = tile;
+  p.out = out; p.out_ld = out_ld; p.out_f32 = out_f32; p.zeros = c.zeros;
+  launch_conv_gemm(h->st, p);
+  op_bare_done(h);
+  CD_API_END
+}
+
+// at_core (nets_ho_vae.hip) on the caller's q | k rows, normalised rows and output; vt_out (or NULL) receives V^T [B][C][Tpad]
+int cd_op_attn_block_core(cd_handle h, const void* qk, int ldqk, const void* n, int ldn, const void* packed_v,
+                          const float* v_bias, int B, int T, int C, void* o, int ldo, void* vt_out, int* branch) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && qk && n && packed_v && o && B > 0 && T > 0 && C > 0 && ldqk >= 2 * C && ldn >= C && ldo >= C, "bad argument");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  const ConvW& wv = *(const ConvW*)packed_v;
+  CD_CHECK(wv.N == C && wv.Cpad == C && wv.KH == 1 && wv.KW == 1, "packed weight does not match the call");
+  Act aqk; aqk.p = (bf16_t*)const_cast<void*>(qk); aqk.B = B; aqk.H = T; aqk.W = 1; aqk.C = 2 * C; aqk.ld = ldqk;
+  Act an; an.p = (bf16_t*)const_cast<void*>(n); an.B = B; an.H = T; an.W = 1; an.C = C; an.ld = ldn;
+  Act ao; ao.p = (bf16_t*)o; ao.B = B; ao.H = T; ao.W = 1; ao.C = C; ao.ld = ldo;
+  const AtCoreOut r = at_core(c, wv, v_bias, aqk, an, C, ao);
+  if (vt_out) HIP_CHECK(hipMemcpyAsync(vt_out, r.vt, (size_t)B * C * r.Tpad * 2, hipMemcpyDeviceToDevice, h->st));
+  if (branch) *branch = r.branch;
+  op_bare_done(h);
+  CD_API_END
+}
+
 }  // extern "C"

@@ -53,18 +53,6 @@ ConvW* mk_linear(ParamStore& ps, const std::string& pfx, int N, int K) {
   return c;
 }
 
-// V^T[b] = Wv . X[b]^T : weights as the A operand, tokens as the B operand -> [B][C][Tpad]
-void vt_gemm(Ctx& c, const ConvW& wv, const bf16_t* x, int ldx, int B, int T, int Tpad, bf16_t* vt) {
-  ConvGemmParams p;
-  p.src0 = wv.w; p.C0 = wv.Cpad; p.ld0 = wv.Cpad;
-  p.B = 1; p.Hs = wv.N; p.Ws = 1; p.Hin = wv.N; p.Win = 1; p.Hout = wv.N; p.Wout = 1;
-  p.M = wv.N;
-  p.wgt = x; p.Ktot = wv.Cpad; p.ldw = ldx; p.N = T;
-  p.nbatch = B; p.a_bs = 0; p.w_bs = (int64_t)T * ldx; p.o_bs = (int64_t)wv.N * Tpad;
-  p.out = vt; p.out_ld = Tpad; p.zeros = c.zeros;
-  launch_conv_gemm(c.st, p);
-}
-
 ClipLayer mk_layer_openai(ParamStore& ps, const std::string& lp, int D, int mlp) {
   ClipLayer L;
   L.ln1 = mk_ln(ps, lp + ".ln_1", D);
@@ -263,7 +251,7 @@ class ClipText : public TextEncoder {
       const size_t m2 = c.arena->mark();
       Act n1 = layernorm_fwd(c, Lw.ln1, h);
       Act qk = conv_fwd(c, *Lw.qk, n1, nullptr, p0);  // [B*L][2*inner]
-      vt_gemm(c, *Lw.v, n1.p, n1.ld, B, L, Tpad, vt);
+      vt_gemm_fwd(c, *Lw.v, n1.p, n1.ld, B, L, Tpad, vt);
       Act a = alloc_act(c, B, L, 1, I);
       AttnParams ap;
       ap.q = qk.p; ap.k = qk.p + I; ap.vt = vt; ap.o = a.p;

@@ -215,6 +215,11 @@ void st_entry_refresh(hipStream_t st, StEntryW& w);
 struct StEntryOut { Act h, qk; bf16_t* vt = nullptr; int Tpad = 0; int stages = 0; };  // stages: the bits that ran
 // V^T[b] = Wv . X[b]^T on the implicit-GEMM family: weights as the A operand, tokens as the B operand -> [B][C][Tpad]
 void vt_gemm_fwd(Ctx& c, const ConvW& wv, const bf16_t* x, int ldx, int B, int T, int Tpad, bf16_t* vt);
+// the single-head AttnBlock of the Ho-DDPM U-Net / the first stages between its q | k projection and proj_out (nets_ho_vae.hip):
+// qk [B*T][2C] and the normalised rows n [B*T][C] -> o = softmax(C^-1/2 q k^T) (Wv n) + vbias. o.p == nullptr: allocated from the
+// arena, as vt [B][C][Tpad] is. branch: 0 = the flash kernel (C <= 160), 1 = scores materialised once per image
+struct AtCoreOut { Act o; bf16_t* vt = nullptr; int Tpad = 0; int branch = 0; };
+AtCoreOut at_core(Ctx& c, const ConvW& wv, const float* vbias, const Act& qk, const Act& n, int C, Act o = Act());
 // h = proj_in(GroupNorm(x)) [B*T][C]; then qk = [q (log2 units) | k] of LayerNorm1(h) [B*T][2C], vt [B][C][Tpad]
 // (arena-allocated: the caller brackets the second call with the mark its attention releases); st_entry_fwd = both
 Act st_entry_proj_in(Ctx& c, const StEntryW& w, const Act& x, int stages);

@@ -496,8 +496,7 @@ void vt_gemm_fwd(Ctx& c, const ConvW& wv, const bf16_t* x, int ldx, int B, int T
   p.src0 = wv.w; p.C0 = wv.Cpad; p.ld0 = wv.Cpad;
   p.B = 1; p.Hs = wv.N; p.Ws = 1; p.Hin = wv.N; p.Win = 1; p.Hout = wv.N; p.Wout = 1;
   p.M = wv.N;
-  p.wgt = x; p.Ktot = wv.Cpad; p.N = T;
-  CD_CHECK(ldx == wv.Cpad, "vt_gemm: token row stride %d must equal K %d", ldx, wv.Cpad);
+  p.wgt = x; p.Ktot = wv.Cpad; p.ldw = ldx; p.N = T;
   p.nbatch = B; p.a_bs = 0; p.w_bs = (int64_t)T * ldx; p.o_bs = (int64_t)wv.N * Tpad;
   p.out = vt; p.out_ld = Tpad; p.zeros = c.zeros;
   launch_conv_gemm(c.st, p);

@@ -87,45 +87,26 @@ Act rn_fwd(Ctx& c, const RnW& r, const Act& x, const Act* x2, const float* proj,
   return out;
 }
 
-void vt_gemm2(Ctx& c, const ConvW& wv, const bf16_t* x, int ldx, int B, int T, int Tpad, bf16_t* vt) {
-  ConvGemmParams p;
-  p.src0 = wv.w; p.C0 = wv.Cpad; p.ld0 = wv.Cpad;
-  p.B = 1; p.Hs = wv.N; p.Ws = 1; p.Hin = wv.N; p.Win = 1; p.Hout = wv.N; p.Wout = 1;
-  p.M = wv.N;
-  p.wgt = x; p.Ktot = wv.Cpad; p.ldw = ldx; p.N = T;
-  p.nbatch = B; p.a_bs = 0; p.w_bs = (int64_t)T * ldx; p.o_bs = (int64_t)wv.N * Tpad;
-  p.out = vt; p.out_ld = Tpad; p.zeros = c.zeros;
-  launch_conv_gemm(c.st, p);
-}
+}  // namespace
 
-Act at_fwd(Ctx& c, const AtW& a, const Act& x) {
-  const int B = x.B, T = x.H * x.W, C = a.C;
-  Act out = alloc_act(c, B, x.H, x.W, C, /*with_stats=*/true);
-  const size_t mk = c.arena->mark();
-  ConvOpts p0; p0.pad = 0;
-  Act n = groupnorm_fwd(c, a.norm, x, nullptr, false);
-  Act qk = conv_fwd(c, *a.qk, n, nullptr, p0);  // [B*T][2C]
-  if (c.f32) {  // fp32 path (Ho-DDPM in CD_PREC_F32): single head of width C
-    Act v = conv_fwd(c, *a.v, n, nullptr, p0);
-    Act o = attention_f32_fwd(c, qk, v, 1, C, 1.0f / sqrtf((float)C), a.vbias);
-    ConvOpts po; po.pad = 0; po.resid = &x; po.out = out.p; po.out_ld = out.ld;
-    conv_fwd(c, *a.proj, o, nullptr, po);
-    c.arena->release(mk);
-    return out;
-  }
+// the AttnBlock between its q | k projection and proj_out (16-bit path): V^T from the normalised rows, then the flash kernel
+// (C <= 160) or the materialised scores. o.p == nullptr: o is allocated here, [B*T][C]
+AtCoreOut at_core(Ctx& c, const ConvW& wv, const float* vbias, const Act& qk, const Act& n, int C, Act o) {
+  const int B = n.B, T = n.H * n.W;
+  AtCoreOut r;
   const int Tpad = round_up(T, 64);
   bf16_t* vt = (bf16_t*)c.arena->alloc((size_t)B * C * Tpad * 2);
   if (Tpad != T) HIP_CHECK(hipMemsetAsync(vt, 0, (size_t)B * C * Tpad * 2, c.st));
-  vt_gemm2(c, *a.v, n.p, n.ld, B, T, Tpad, vt);
+  vt_gemm_fwd(c, wv, n.p, n.ld, B, T, Tpad, vt);
   const float scale = 1.0f / sqrtf((float)C);  // w_ * int(c)**(-0.5), model.py:192
-  Act o = alloc_act(c, B, x.H, x.W, C);
+  if (!o.p) o = alloc_act(c, B, n.H, n.W, C);
   if (C <= 160) {
     AttnParams p;
     p.q = qk.p; p.k = qk.p + C; p.vt = vt; p.o = o.p;
     p.B = B; p.H = 1; p.Tq = T; p.Tk = T; p.D = C;
     p.ldq = qk.ld; p.ldk = qk.ld; p.ldo = o.ld;
     p.q_bs = (int64_t)T * qk.ld; p.k_bs = (int64_t)T * qk.ld; p.o_bs = (int64_t)T * o.ld;
-    p.vt_dpad = C; p.vt_tpad = Tpad; p.scale = scale; p.obias = a.vbias;
+    p.vt_dpad = C; p.vt_tpad = Tpad; p.scale = scale; p.obias = vbias;
     launch_attention(c.st, p);
   } else {
     // wide single head (VAE mid block: 4096 tokens x 512 ch): scores materialised once per image,
@@ -145,10 +126,33 @@ Act at_fwd(Ctx& c, const AtW& a, const Act& x) {
     h.src0 = P; h.C0 = T; h.ld0 = T; h.B = 1; h.Hs = T; h.Ws = 1; h.Hin = T; h.Win = 1;
     h.Hout = T; h.Wout = 1; h.M = T;
     h.wgt = vt; h.Ktot = T; h.ldw = Tpad; h.N = C;
-    h.nbatch = B; h.a_bs = (int64_t)T * T; h.w_bs = (int64_t)C * Tpad; h.o_bs = (int64_t)T * C;
-    h.bias = a.vbias; h.out = o.p; h.out_ld = o.ld; h.zeros = c.zeros;
+    h.nbatch = B; h.a_bs = (int64_t)T * T; h.w_bs = (int64_t)C * Tpad; h.o_bs = (int64_t)T * o.ld;
+    h.bias = vbias; h.out = o.p; h.out_ld = o.ld; h.zeros = c.zeros;
     launch_conv_gemm(c.st, h);
+    r.branch = 1;
   }
+  r.o = o; r.vt = vt; r.Tpad = Tpad;
+  return r;
+}
+
+namespace {
+
+Act at_fwd(Ctx& c, const AtW& a, const Act& x) {
+  const int B = x.B, T = x.H * x.W, C = a.C;
+  Act out = alloc_act(c, B, x.H, x.W, C, /*with_stats=*/true);
+  const size_t mk = c.arena->mark();
+  ConvOpts p0; p0.pad = 0;
+  Act n = groupnorm_fwd(c, a.norm, x, nullptr, false);
+  Act qk = conv_fwd(c, *a.qk, n, nullptr, p0);  // [B*T][2C]
+  if (c.f32) {  // fp32 path (Ho-DDPM in CD_PREC_F32): single head of width C
+    Act v = conv_fwd(c, *a.v, n, nullptr, p0);
+    Act o = attention_f32_fwd(c, qk, v, 1, C, 1.0f / sqrtf((float)C), a.vbias);
+    ConvOpts po; po.pad = 0; po.resid = &x; po.out = out.p; po.out_ld = out.ld;
+    conv_fwd(c, *a.proj, o, nullptr, po);
+    c.arena->release(mk);
+    return out;
+  }
+  Act o = at_core(c, *a.v, a.vbias, qk, n, C).o;
   ConvOpts po; po.pad = 0; po.resid = &x; po.out = out.p; po.out_ld = out.ld; po.out_stats = out.stats_buf;
   conv_fwd(c, *a.proj, o, nullptr, po);
   out.stats = out.stats_buf;

@@ -500,6 +500,22 @@ int cd_op_posterior_sample(cd_handle h, const float* mom, int ld, const float* n
  * columns < zc, zero words behind; zc <= 8 and a codebook of at most 150 KB */
 int cd_op_vq_quantize(cd_handle h, const float* z, float in_mul, const float* codebook, int n_embed, int zc, int B, int HW,
                       void* out16, int Cpad);
+/* the implicit-GEMM kernel as a batched plain GEMM on the caller's device bytes (one launch, no staging):
+ * out[z][m][n] = act(alpha * sum_k a[z][m][k] w[z][n][k] + bias[n]) + resid[z][m][n], z < nbatch. a 16-bit [M][lda] at
+ * a + z * a_bs, w 16-bit [N][ldw] at w + z * w_bs (element strides; 0 = shared), K % 32 == 0; out 16-bit or fp32 (out_f32)
+ * [M][out_ld] at out + z * o_bs; resid 16-bit [M][resid_ld] at resid + z * o_bs, or NULL; stats fp32 [nbatch][ceil(M/32)][2][N]
+ * (sums and sums of squares of the final values over 32-row blocks) or NULL; bias fp32 [N] or NULL; act as cd_op_conv2d;
+ * tile = id | split << 8 | bk32 << 16, 0 = the launcher's choice (read back with cd_op_last_gemm_config) */
+int cd_op_gemm_batched(cd_handle h, const void* a, int lda, int64_t a_bs, const void* w, int ldw, int64_t w_bs, int M, int N,
+                       int K, int nbatch, float alpha, const float* bias, const void* resid, int resid_ld, float* stats, int act,
+                       int tile, void* out, int out_ld, int64_t o_bs, int out_f32);
+/* the single-head AttnBlock (Ho-DDPM U-Net, first stages) between its q | k projection and proj_out, on the caller's device
+ * bytes: qk 16-bit [B*T][ldqk] = q (C) | k (C), n 16-bit [B*T][ldn] the normalised rows, packed_v the [C][C] value weight from
+ * cd_op_pack_conv_weight, v_bias fp32 [C] -> o 16-bit [B*T][ldo] = softmax(C^-1/2 q k^T) (Wv n) + v_bias; vt_out (or NULL)
+ * 16-bit [B][C][round_up(T, 64)] = V^T, zero behind column T; *branch = 0: the flash kernel (C <= 160), 1: scores materialised
+ * per image (T % 32 == 0) */
+int cd_op_attn_block_core(cd_handle h, const void* qk, int ldqk, const void* n, int ldn, const void* packed_v,
+                          const float* v_bias, int B, int T, int C, void* o, int ldo, void* vt_out, int* branch);
 /* micro-benchmark of one conv / GEMM shape on synthetic data (scripts/bench_gemm.py): average ms per launch.
  * act: low byte = activation; | 0x100 = in-place residual update of the output; | 0x200 = fused GroupNorm statistics */
 int cd_op_bench_conv(cd_handle h, int B, int H, int W, int C0, int C1, int N, int k, int stride, int up,

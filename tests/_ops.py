@@ -452,3 +452,65 @@ def glue_vq_quantize(eng, z, in_mul, codebook, B, HW, Cpad, guard, sent, refusal
     rc = eng.lib.cd_op_vq_quantize(eng.h, ptr(zs), C.c_float(in_mul), ptr(cs), codebook.shape[0], codebook.shape[1], B, HW, ptr(y),
                                    Cpad)
     return _finish(eng, rc, y, refusal)
+
+
+# ------------------------------------------------------------------------------ the batched GEMM forms and the AttnBlock core
+# tests/_gemm_batched_ref.py: operands as int16 storage words, sentinels and guards; nothing is staged on the device.
+def _at(t, elems):
+    """device pointer `elems` elements into tensor t"""
+    return None if t is None else C.c_void_p(t.data_ptr() + elems * t.element_size())
+
+
+def gemm_batched(eng, o, tile, singles=False, guard=0, sent16=0, sent32=0.0):
+    """cd_op_gemm_batched on the operands of _gemm_batched_ref.gemm_build: one launch with nbatch = nb, or (singles) nb launches
+    with nbatch = 1 and every pointer advanced by its batch stride, into the same buffers. -> (out, statistics or None, the
+    read-back of every launch), the buffers with their guards"""
+    c = o["case"]
+    M, N, K, nb, out_ld = c["M"], c["N"], c["K"], c["nb"], c["out_ld"]
+    o_bs, nblk = M * out_ld, M // 32
+    A = _up(o["A"])
+    W = A if o["W"] is None else _up(o["W"])
+    bias, resid = _up(o["bias"]), _up(o["resid"])
+    out = _out32(nb * o_bs, guard, sent32) if c["out_f32"] else _out16(nb * o_bs, guard, sent16)
+    st = _out32(nb * nblk * 2 * N, guard, sent32) if c["stats"] else None
+    rbs = []
+    for z, n in ([(z, 1) for z in range(nb)] if singles else [(0, nb)]):
+        check(eng.lib.cd_op_gemm_batched(
+            eng.h, _at(A, o["a_off"] + z * c["a_bs"]), c["lda"], c["a_bs"], _at(W, o["w_off"] + z * c["w_bs"]), c["ldw"], c["w_bs"],
+            M, N, K, n, C.c_float(c["alpha"]), ptr(bias), _at(resid, z * o_bs), N if resid is not None else 0,
+            _at(st, z * nblk * 2 * N), 0, tile, _at(out, z * o_bs), out_ld, o_bs, c["out_f32"]))
+        rbs.append(last_gemm_config(eng))
+    return out.cpu(), (st.cpu() if st is not None else None), rbs
+
+
+def gemm_raw(eng, a, lda, a_bs, w, ldw, w_bs, M, N, K, nb, alpha, bias, out, out_ld, out_f32, tile=0):
+    """cd_op_gemm_batched on device pointers (ctypes) / tensors the caller laid out; out [nb][M][out_ld] on the device"""
+    as_ptr = lambda t: t if isinstance(t, C.c_void_p) else ptr(t)
+    check(eng.lib.cd_op_gemm_batched(eng.h, as_ptr(a), lda, a_bs, as_ptr(w), ldw, w_bs, M, N, K, nb, C.c_float(alpha), ptr(bias),
+                                     None, 0, None, 0, tile, ptr(out), out_ld, M * out_ld, out_f32))
+
+
+def attn_block_core(eng, o, guard, sent16, want_vt=True, refusal=False):
+    """cd_op_attn_block_core on the operands of _gemm_batched_ref.core_build -> (o words, V^T words or None, branch); with
+    refusal = True: (the error text, o words)"""
+    c = o["case"]
+    B, T, Cc = c["B"], c["T"], c["C"]
+    handle, _ = pack_conv(eng, o["wv"])
+    qk, n, vb = _up(o["qk"]), _up(o["n"]), _up(o["vbias"])
+    out = _out16(B * T * c["ldo"], guard, sent16)
+    vt = _out16(B * Cc * c["Tpad"], guard, sent16) if want_vt else None
+    branch = C.c_int(-1)
+    rc = eng.lib.cd_op_attn_block_core(eng.h, ptr(qk), c["ldqk"], ptr(n), c["ldn"], handle, ptr(vb), B, T, Cc, ptr(out), c["ldo"],
+                                       ptr(vt), C.byref(branch))
+    if refusal:
+        return _finish(eng, rc, out, True)
+    check(rc)
+    return out.cpu(), (vt.cpu() if vt is not None else None), branch.value
+
+
+def softmax_rows_dev(eng, s_dev):
+    """cd_op_softmax_rows on a device tensor fp32 [rows, cols] -> fp32 on the device (16-bit values, widened)"""
+    rows, cols = s_dev.shape
+    p = torch.empty_like(s_dev)
+    check(eng.lib.cd_op_softmax_rows(eng.h, ptr(s_dev), rows, cols, ptr(p)))
+    return p

@@ -110,6 +110,11 @@ CONV_CASES = [
     ("3x3_ragged_M_split8", 1, 64, 0, 10, 10, 64, 3, 1, 1, False, False, True, False, True, 0, 1 | (8 << 8)),
     ("3x3_concat_k32_split3", 2, 64, 32, 16, 16, 96, 3, 1, 1, False, False, True, False, False, 0, 2 | (3 << 8)),
     ("3x3_stride2_split2_silu", 2, 128, 0, 16, 16, 128, 3, 2, 1, False, False, True, False, False, 1, 3 | (2 << 8)),
+    # the two activations of the generic epilogue that only whole towers reached: quick-GELU x sigmoid(1.702 x) (CLIP), ReLU
+    # (Inception; zero-mean outputs: about half are clipped); the residual is added AFTER the activation
+    ("1x1_qgelu", 1, 64, 0, 8, 8, 96, 1, 1, 0, False, False, True, False, False, 4, 0),
+    ("3x3_relu", 2, 64, 0, 16, 16, 64, 3, 1, 1, False, False, True, False, False, 5, 0),
+    ("1x1_relu_resid_t22", 1, 64, 0, 16, 16, 256, 1, 1, 0, False, False, True, False, True, 5, 22),
 ]
 
 
@@ -135,6 +140,11 @@ def test_conv2d(engine, report, case):
         ref = F.silu(ref)
     elif act == 2:
         ref = F.gelu(ref)
+    elif act == 4:
+        ref = ref * torch.sigmoid(1.702 * ref)
+    elif act == 5:
+        ref = ref.clamp_min(0.0)
+        assert 0.3 < (ref == 0).float().mean() < 0.7  # the clip is exercised on both sides
     res = r16(torch.randn(ref.shape, generator=g)) if has_res else None
     if res is not None:
         ref = ref + res
@@ -473,6 +483,17 @@ def test_softmax_rows(engine, report):
     s = torch.randn(70, 1000, generator=g) * 4
     got = _ops.softmax_rows(engine, s)
     _check(report, "softmax_rows", got, torch.softmax(s, -1), rel=1e-2, mean=5e-3)
+    # the row lengths of the AttnBlock's materialised scores (96, 64, 4096), rows whose maximum stands 80 above the rest in the
+    # last column (the small terms underflow: exactly 0 / 1 must come out, finite), constant rows (1 / cols); float64 reference
+    # and the words that must be exact: tests/_gemm_batched_ref.py, the same bounds
+    import _gemm_batched_ref as G
+    fmt = "fp16" if engine.lib.cd_act_format() == 1 else "bf16"
+    for name in G.SM:
+        o = G.sm_build(name)
+        r = G.sm_verify(o, _ops.softmax_rows(engine, o["s"]), fmt)
+        report.add("softmax_rows/" + name[3:], **r)
+        print("softmax_rows/%s %s" % (name[3:], r))
+        assert r["finite"] and r["mismatch"] == 0 and r["rel_to_max"] < 1e-2 and r["mean_rel"] < 5e-3, (name, r)
 
 
 @pytest.mark.parametrize("mode", [0, 1])
