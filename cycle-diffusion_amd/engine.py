@@ -446,10 +446,25 @@ class Engine:
         forward per step over [encoder rows | decoder rows]. x0 [B, C, H, W]; dec_ctx_* [n_dec * B, L, Dc] (decoder row
         j * B + b decodes encoder sample b); dec_guidance one scale or n_dec * B of them (none 0 or 1).
         Returns (z [B, K+1, C, H, W], x [n_dec * B, C, H, W])."""
+        return self._cycle_translate(net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
+                                     dec_guidance, n_dec, noise, seed, last_uses_x0)
+
+    def _cycle_translate(self, net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
+                         dec_guidance, n_dec, noise, seed, last_uses_x0, mask=None, mask_x0=None, qcoef=None, mask_noise=None,
+                         mask_seed=0, mask_source="q_sample", ctrl=None):
+        """The marshalling of the three coupled entry points: cd_cycle_translate without a mask and without `ctrl`,
+        cd_cycle_translate_masked with a mask only, cd_cycle_translate_ctrl with `ctrl` = (mapper, alpha, weight, n_ctrl) - the
+        argument list of each is the one before it plus a tail, as cycle_translate_impl serves them from one body."""
         x0 = self._f32(x0)
         K = len(coef_dec)
         assert len(coef_enc) == K + 1
         B, Cc, H, W = x0.shape
+        Bm, src = 0, _ffi.CD_MASK_QSAMPLE
+        if mask is not None:
+            mask, mask_x0, Bm, src, qcoef, mask_noise = self._mask_args(mask, mask_x0, B, qcoef, mask_noise, mask_source, H, W,
+                                                                        Cc, K, b_noise=n_dec * B)
+        else:
+            mask_x0 = qcoef = mask_noise = None
         z = torch.empty((B, K + 1, Cc, H, W), device=x0.device, dtype=torch.float32)
         x = torch.empty((n_dec * B, Cc, H, W), device=x0.device, dtype=torch.float32)
         coef_enc, coef_dec = np.ascontiguousarray(coef_enc), np.ascontiguousarray(coef_dec)
@@ -457,20 +472,36 @@ class Engine:
         L = next((t.shape[1] for t in ctxs if t is not None), 0)
         for t, rows in zip(ctxs, (B, B, n_dec * B, n_dec * B)):
             assert t is None or t.shape[0] == rows, (t.shape, rows)
-        gvec, gscalar = None, 1.0
-        if isinstance(dec_guidance, (int, float)):
-            gscalar = float(dec_guidance)
-        else:
-            gvec = torch.as_tensor(dec_guidance, dtype=torch.float32).to(x0.device).contiguous()
-            if gvec.numel() != n_dec * B or bool(((gvec == 0) | (gvec == 1)).any()):
-                raise ValueError("per-sample guidance: n_dec * B scales, none of them 0 or 1")
+        fn, tail, ctl = self.lib.cd_cycle_translate, [], None
+        if mask is not None or ctrl is not None:
+            fn = self.lib.cd_cycle_translate_masked
+            tail = [ptr(mask), ptr(mask_x0), Bm, src, C.c_void_p(qcoef.ctypes.data) if qcoef is not None else None,
+                    ptr(mask_noise), C.c_uint64(mask_seed)]
+        if ctrl is not None:
+            ctl = [torch.as_tensor(t, dtype=torch.float32).to(x0.device).contiguous() for t in ctrl[:3]]
+            Bc = ctl[0].shape[0]
+            if tuple(ctl[0].shape) != (Bc, L, L) or tuple(ctl[1].shape) != (Bc, L) or tuple(ctl[2].shape) != (Bc, L):
+                raise ValueError("control tensors must be mapper [B_ctrl, %d, %d], alpha / weight [B_ctrl, %d], got %s"
+                                 % (L, L, L, [tuple(t.shape) for t in ctl]))
+            fn = self.lib.cd_cycle_translate_ctrl
+            tail += [ptr(ctl[0]), ptr(ctl[1]), ptr(ctl[2]), Bc, int(ctrl[3])]
+        gvec, gscalar = self._guidance(dec_guidance, n_dec * B, "n_dec * B", x0.device)
         nz = self._f32(noise) if noise is not None else None
-        check(self.lib.cd_cycle_translate(self.h, net, kind, ptr(x0), ptr(ctxs[0]), ptr(ctxs[1]), C.c_float(enc_guidance),
-                                          ptr(ctxs[2]), ptr(ctxs[3]), C.c_float(gscalar), ptr(gvec), L, B, n_dec, K,
-                                          C.c_void_p(coef_enc.ctypes.data), C.c_void_p(coef_dec.ctypes.data), ptr(nz),
-                                          C.c_uint64(seed), int(last_uses_x0), ptr(z), ptr(x)))
-        self._keep = (gvec, ctxs, nz)  # the launches read them asynchronously
+        check(fn(self.h, net, kind, ptr(x0), ptr(ctxs[0]), ptr(ctxs[1]), C.c_float(enc_guidance), ptr(ctxs[2]), ptr(ctxs[3]),
+                 C.c_float(gscalar), ptr(gvec), L, B, n_dec, K, C.c_void_p(coef_enc.ctypes.data), C.c_void_p(coef_dec.ctypes.data),
+                 ptr(nz), C.c_uint64(seed), int(last_uses_x0), *tail, ptr(z), ptr(x)))
+        self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise, ctl)  # the launches read them asynchronously
         return z, x
+
+    @staticmethod
+    def _guidance(guidance, rows, what, device):
+        """(gvec, gscalar) of a decoder guidance: one scale, or `rows` of them on the device when the samples differ in it"""
+        if isinstance(guidance, (int, float)):
+            return None, float(guidance)
+        gvec = torch.as_tensor(guidance, dtype=torch.float32).to(device).contiguous()
+        if gvec.numel() != rows or bool(((gvec == 0) | (gvec == 1)).any()):
+            raise ValueError("per-sample guidance: %s scales, none of them 0 or 1" % what)
+        return gvec, 1.0
 
     def _mask_args(self, mask, x0, B, qcoef, mask_noise, mask_source, H, W, Cc, K, b_noise=None):
         """checked (mask, x0, B_mask, source id, qcoef, noise) of the masked entry points; `b_noise`: the decoder's batch"""
@@ -518,13 +549,7 @@ class Engine:
         cc = self._f32(ctx_c) if ctx_c is not None else None
         cu = self._f32(ctx_uc) if ctx_uc is not None else None
         nt = self._f32(noise_tail) if noise_tail is not None else None
-        gvec, gscalar = None, 1.0
-        if isinstance(guidance, (int, float)):
-            gscalar = float(guidance)
-        else:
-            gvec = torch.as_tensor(guidance, dtype=torch.float32).to(z.device).contiguous()
-            if gvec.numel() != B or bool(((gvec == 0) | (gvec == 1)).any()):
-                raise ValueError("per-sample guidance: B scales, none of them 0 or 1")
+        gvec, gscalar = self._guidance(guidance, B, "B", z.device)
         check(self.lib.cd_ddim_decode_masked(self.h, net, kind, ptr(z), T, n_eps, ptr(cc), ptr(cu), L, C.c_float(gscalar),
                                              ptr(gvec), B, K, C.c_void_p(coef.ctypes.data), ptr(nt), C.c_uint64(seed),
                                              ptr(mask), ptr(x0), Bm, src, C.c_void_p(qcoef.ctypes.data), ptr(mask_noise),
@@ -539,34 +564,10 @@ class Engine:
         """cd_cycle_translate_masked: cycle_translate with the keep-mask on the decoder rows. mask [B_mask, 1, H, W], B_mask
         dividing B. "q_sample": mask_x0 [B_mask, C, H, W], qcoef = coef_qsample(skip), mask_noise [K, n_dec * B, C, H, W] or
         None; "encoder": the kept region follows the encoder's own x_t of every level, nothing else is passed or drawn."""
-        x0 = self._f32(x0)
-        K = len(coef_dec)
-        assert len(coef_enc) == K + 1
-        B, Cc, H, W = x0.shape
-        mask, mask_x0, Bm, src, qcoef, mask_noise = self._mask_args(mask, mask_x0, B, qcoef, mask_noise, mask_source, H, W, Cc,
-                                                                    K, b_noise=n_dec * B)
-        z = torch.empty((B, K + 1, Cc, H, W), device=x0.device, dtype=torch.float32)
-        x = torch.empty((n_dec * B, Cc, H, W), device=x0.device, dtype=torch.float32)
-        coef_enc, coef_dec = np.ascontiguousarray(coef_enc), np.ascontiguousarray(coef_dec)
-        ctxs = [self._f32(t) if t is not None else None for t in (enc_ctx_c, enc_ctx_uc, dec_ctx_c, dec_ctx_uc)]
-        L = next((t.shape[1] for t in ctxs if t is not None), 0)
-        for t, rows in zip(ctxs, (B, B, n_dec * B, n_dec * B)):
-            assert t is None or t.shape[0] == rows, (t.shape, rows)
-        gvec, gscalar = None, 1.0
-        if isinstance(dec_guidance, (int, float)):
-            gscalar = float(dec_guidance)
-        else:
-            gvec = torch.as_tensor(dec_guidance, dtype=torch.float32).to(x0.device).contiguous()
-            if gvec.numel() != n_dec * B or bool(((gvec == 0) | (gvec == 1)).any()):
-                raise ValueError("per-sample guidance: n_dec * B scales, none of them 0 or 1")
-        nz = self._f32(noise) if noise is not None else None
-        check(self.lib.cd_cycle_translate_masked(
-            self.h, net, kind, ptr(x0), ptr(ctxs[0]), ptr(ctxs[1]), C.c_float(enc_guidance), ptr(ctxs[2]), ptr(ctxs[3]),
-            C.c_float(gscalar), ptr(gvec), L, B, n_dec, K, C.c_void_p(coef_enc.ctypes.data), C.c_void_p(coef_dec.ctypes.data),
-            ptr(nz), C.c_uint64(seed), int(last_uses_x0), ptr(mask), ptr(mask_x0), Bm, src,
-            C.c_void_p(qcoef.ctypes.data) if qcoef is not None else None, ptr(mask_noise), C.c_uint64(mask_seed), ptr(z), ptr(x)))
-        self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise)  # the launches read them asynchronously
-        return z, x
+        # _f32(mask): the mask is not optional here - None is an error, never the unmasked loop
+        return self._cycle_translate(net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
+                                     dec_guidance, n_dec, noise, seed, last_uses_x0, self._f32(mask), mask_x0, qcoef, mask_noise,
+                                     mask_seed, mask_source)
 
     def cycle_translate_ctrl(self, net, kind, x0, coef_enc, coef_dec, mapper, alpha, weight, n_ctrl, mask=None, mask_x0=None,
                              qcoef=None, mask_noise=None, mask_seed=0, mask_source="q_sample", enc_ctx_c=None, enc_ctx_uc=None,
@@ -576,44 +577,9 @@ class Engine:
         first n_ctrl iterations. mapper [B_ctrl, L, L], alpha / weight [B_ctrl, L] (attn_control.build_control), B_ctrl
         dividing B; the decoder's conditional rows take P = w * (alpha * (P_src . M) + (1 - alpha) * P_own) in every text
         cross-attention, P_src from the encoder's conditional row of the same sample in the same forward."""
-        x0 = self._f32(x0)
-        K = len(coef_dec)
-        assert len(coef_enc) == K + 1
-        B, Cc, H, W = x0.shape
-        Bm, src = 0, _ffi.CD_MASK_QSAMPLE
-        if mask is not None:
-            mask, mask_x0, Bm, src, qcoef, mask_noise = self._mask_args(mask, mask_x0, B, qcoef, mask_noise, mask_source, H, W,
-                                                                        Cc, K, b_noise=n_dec * B)
-        else:
-            mask_x0 = qcoef = mask_noise = None
-        z = torch.empty((B, K + 1, Cc, H, W), device=x0.device, dtype=torch.float32)
-        x = torch.empty((n_dec * B, Cc, H, W), device=x0.device, dtype=torch.float32)
-        coef_enc, coef_dec = np.ascontiguousarray(coef_enc), np.ascontiguousarray(coef_dec)
-        ctxs = [self._f32(t) if t is not None else None for t in (enc_ctx_c, enc_ctx_uc, dec_ctx_c, dec_ctx_uc)]
-        L = next((t.shape[1] for t in ctxs if t is not None), 0)
-        for t, rows in zip(ctxs, (B, B, n_dec * B, n_dec * B)):
-            assert t is None or t.shape[0] == rows, (t.shape, rows)
-        ctl = [torch.as_tensor(t, dtype=torch.float32).to(x0.device).contiguous() for t in (mapper, alpha, weight)]
-        Bc = ctl[0].shape[0]
-        if tuple(ctl[0].shape) != (Bc, L, L) or tuple(ctl[1].shape) != (Bc, L) or tuple(ctl[2].shape) != (Bc, L):
-            raise ValueError("control tensors must be mapper [B_ctrl, %d, %d], alpha / weight [B_ctrl, %d], got %s"
-                             % (L, L, L, [tuple(t.shape) for t in ctl]))
-        gvec, gscalar = None, 1.0
-        if isinstance(dec_guidance, (int, float)):
-            gscalar = float(dec_guidance)
-        else:
-            gvec = torch.as_tensor(dec_guidance, dtype=torch.float32).to(x0.device).contiguous()
-            if gvec.numel() != n_dec * B or bool(((gvec == 0) | (gvec == 1)).any()):
-                raise ValueError("per-sample guidance: n_dec * B scales, none of them 0 or 1")
-        nz = self._f32(noise) if noise is not None else None
-        check(self.lib.cd_cycle_translate_ctrl(
-            self.h, net, kind, ptr(x0), ptr(ctxs[0]), ptr(ctxs[1]), C.c_float(enc_guidance), ptr(ctxs[2]), ptr(ctxs[3]),
-            C.c_float(gscalar), ptr(gvec), L, B, n_dec, K, C.c_void_p(coef_enc.ctypes.data), C.c_void_p(coef_dec.ctypes.data),
-            ptr(nz), C.c_uint64(seed), int(last_uses_x0), ptr(mask), ptr(mask_x0), Bm, src,
-            C.c_void_p(qcoef.ctypes.data) if qcoef is not None else None, ptr(mask_noise), C.c_uint64(mask_seed),
-            ptr(ctl[0]), ptr(ctl[1]), ptr(ctl[2]), Bc, int(n_ctrl), ptr(z), ptr(x)))
-        self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise, ctl)  # the launches read them asynchronously
-        return z, x
+        return self._cycle_translate(net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
+                                     dec_guidance, n_dec, noise, seed, last_uses_x0, mask, mask_x0, qcoef, mask_noise, mask_seed,
+                                     mask_source, ctrl=(mapper, alpha, weight, n_ctrl))
 
     def ilvr_decode(self, net, kind, z, coef, ref, down_n, qcoef, range_t=0, n_eps=0, noise_tail=None, seed=0, ref_noise=None,
                     ref_seed=0):

@@ -470,186 +470,72 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         both evaluates the same U-Net at the same timestep, and the decode step needs eps_k only after its forward, so each
         step is ONE forward over [encoder rows | decoder rows] (C2: 12 rows per step for a batch of 4 instead of 4, then 8).
         Same draws in the same order, same member order, same per-sample arithmetic as the two calls. Chains that leave part
-        of the decode to fresh noise (white_box_steps shorter than the chain) take the two calls.
-        `mask` (pixel-space [B, 1, R, R] in [0, 1], 1 = keep the source): the region-keeping edit, see _translate_masked;
-        without one every call below is the unmasked path's.
-        `attn_ctrl` (a prebuilt (M, alpha, w) of attn_control.build_control) or `[gan] cac_steps > 0`: cross-attention control,
-        see _translate_ctrl; with cac_steps = 0 and no attn_ctrl nothing below changes.
+        of the decode to fresh noise (white_box_steps shorter than the chain) take the two calls, and so does a forward of
+        more than COUPLE_MAX_TOKENS.
+        `mask` (pixel-space [B, 1, R, R] in [0, 1], 1 = keep the source; or a LatentMask): the region-keeping edit - ahead of
+        every forward the decoder's latent becomes src_k * m + (1 - m) * x, m the block mean of `mask` (ddim.py:427-430). x0 of
+        the blend is the first-stage encoding encode() works on (the sampled z0 for the SD family). mask_source 'q_sample':
+        src_k = q_sample(x0, tau[k]) with K fresh draws per candidate, made after the encoder's in the reference's order (every
+        member encoded, then member -> decoder scale) - coupled or as two calls, by the same rule as without a mask.
+        'encoder': src_k = the DPM-Encoder's own x_t of level k, which exists in the coupled loop only: ALWAYS the coupled loop
+        - past COUPLE_MAX_TOKENS it runs in chunks of samples. The decoded image is NOT pasted over in pixel space: the kept
+        region goes through the first stage like the rest. Without a mask every call below is the unmasked path's.
+        `attn_ctrl` (a prebuilt (M, alpha, w) of attn_control.build_control) or `[gan] cac_steps > 0`: cross-attention control -
+        in the first n_ctrl = int(cac_steps * K) iterations of a member's K-step loop the decoder's conditional rows take the
+        source prompt's attention maps on the source image - recomputed from the encoder's rows of the same forward - for the
+        tokens both prompts share (`attn_ctrl` replaces the built (M, alpha, w)). The source rows only exist in the coupled
+        loop, so this ALWAYS runs coupled too, in chunks of samples past COUPLE_MAX_TOKENS. Composes with a keep-mask of either
+        source; draw order and member order do not change. With cac_steps = 0 and no attn_ctrl nothing below changes.
         `[gan] auto_mask = diffedit` without a `mask`: the keep-mask is estimated from the two prompts on the x0 the masked
         path works on (auto_mask()) and that path runs with it; with auto_mask = none nothing below changes."""
         if mask is None and self._auto_mask_on():
-            mask = AUTO_MASK
-        if attn_ctrl is not None or self.cac_steps > 0:
-            return self._translate_ctrl(image, encode_text, decode_text, mask, attn_ctrl)
-        if mask is not None:
-            return self._translate_masked(image, encode_text, decode_text, mask)
+            mask = AUTO_MASK  # estimated below, once x0 exists
         sch = self._schedule()
+        bsz = image.shape[0]
         whole = all(self._white_box_loop(len(sch) - sk, sk) == len(sch) - sk for sk in self.skip_steps)
         dec_scales = [float(sc) for sc in self.decoder_unconditional_guidance_scales]
         n_dec = len(dec_scales)
         kinds = [self._kind(sc) for sc in dec_scales]
         main = "cfg" if "cfg" in kinds else kinds[0]  # the decoder scales that ride with the encoder (the others decode from z)
         ride = [j for j in range(n_dec) if kinds[j] == main and (main == "cfg" or dec_scales[j] == dec_scales[kinds.index(main)])]
-        bsz = image.shape[0]
-        enc_cfg = any(self._kind(float(sc)) == "cfg" for sc in self.encoder_unconditional_guidance_scales)
-        rows = bsz * ((2 if enc_cfg else 1) + len(ride) * (2 if main == "cfg" else 1))  # of one member's coupled forward
-        self.last_translate_coupled = bool(self.couple and whole and rows * self.image_size ** 2 <= self.couple_max_tokens)
-        if not self.last_translate_coupled:
-            z_ensemble = self.encode(image, encode_text)
-            return self.forward(z_ensemble, image, encode_text, decode_text)
-        x0, c_src, uc, members = self._encode_front(image, encode_text)
-        c_tgt, _ = self.get_condition(decode_text, bsz)
-        z_ensemble, latents = [None] * len(members), {}
-        per_call = max(1, min(self.MAX_FOLD // (bsz * (1 + len(ride))), self.couple_max_tokens // (rows * self.image_size ** 2)))
-        for grp in self._groups([(m[0], m[1]) for m in members]):
-            enc_scale, skip = members[grp[0]][0], members[grp[0]][1]
-            for idx in self._chunks(grp, per_call):
-                n, nr = len(idx), len(ride)
-                if main == "cfg" and len({dec_scales[j] for j in ride}) > 1:
-                    guidance = torch.tensor([dec_scales[j] for j in ride for _ in range(n * bsz)], dtype=torch.float32)
-                else:
-                    guidance = dec_scales[ride[0]]
-                z, x = self.engine.cycle_translate(
-                    self.unet, _ffi.CD_SCHED_DDIM, x0.repeat(n, 1, 1, 1), sch.coef_encode(skip), sch.coef_decode(skip),
-                    enc_ctx_c=c_src.repeat(n, 1, 1), enc_ctx_uc=uc.repeat(n, 1, 1), enc_guidance=enc_scale,
-                    dec_ctx_c=c_tgt.repeat(n * nr, 1, 1), dec_ctx_uc=uc.repeat(n * nr, 1, 1), dec_guidance=guidance, n_dec=nr,
-                    noise=torch.cat([members[i][2] for i in idx], dim=1), last_uses_x0=True)
-                for m, i in enumerate(idx):
-                    z_ensemble[i] = z[m * bsz:(m + 1) * bsz].reshape(bsz, -1)
-                    for jr, j in enumerate(ride):  # decoder row (jr * n + m) * bsz + b
-                        latents[i * n_dec + j] = x[(jr * n + m) * bsz:(jr * n + m + 1) * bsz]
-        img_ensemble = self.generate(z_ensemble, decode_text, latents=latents)
-        return self._select(img_ensemble, image, encode_text, decode_text)
-
-    def _translate_masked(self, image, encode_text, decode_text, mask):
-        """translate() with a keep-mask: ahead of every forward the decoder's latent becomes src_k * m + (1 - m) * x, m the
-        block mean of `mask` (ddim.py:427-430). x0 of the blend is the first-stage encoding encode() works on (the sampled z0
-        for the SD family). mask_source 'q_sample': src_k = q_sample(x0, tau[k]) with K fresh draws per candidate, made after
-        the encoder's in the reference's order - coupled or as two calls, by the same rule as the unmasked translate().
-        'encoder': src_k = the DPM-Encoder's own x_t of level k; ALWAYS the coupled loop - past COUPLE_MAX_TOKENS it runs in
-        chunks of samples. The decoded image is NOT pasted over in pixel space: the kept region goes through the first stage
-        like the rest."""
-        sch = self._schedule()
-        bsz = image.shape[0]
-        m = None if mask is AUTO_MASK else self._latent_mask(mask, bsz)  # AUTO_MASK: estimated below, once x0 exists
-        encoder = self.mask_source == "encoder"
-        whole = all(self._white_box_loop(len(sch) - sk, sk) == len(sch) - sk for sk in self.skip_steps)
-        dec_scales = [float(sc) for sc in self.decoder_unconditional_guidance_scales]
-        n_dec = len(dec_scales)
-        kinds = [self._kind(sc) for sc in dec_scales]
-        main = "cfg" if "cfg" in kinds else kinds[0]
-        ride = [j for j in range(n_dec) if kinds[j] == main and (main == "cfg" or dec_scales[j] == dec_scales[kinds.index(main)])]
-        enc_cfg = any(self._kind(float(sc)) == "cfg" for sc in self.encoder_unconditional_guidance_scales)
-        rows1 = (2 if enc_cfg else 1) + len(ride) * (2 if main == "cfg" else 1)  # rows of one sample of one member
+        enc_kinds = [self._kind(float(sc)) for sc in self.encoder_unconditional_guidance_scales]
+        rows1 = (2 if "cfg" in enc_kinds else 1) + len(ride) * (2 if main == "cfg" else 1)  # rows of one sample of one member
         tokens = self.image_size ** 2
         fits = bsz * rows1 * tokens <= self.couple_max_tokens
-        if encoder:
-            if not whole:
-                raise ValueError("mask_source = 'encoder' needs the DPM-Encoder over the whole chain (white_box_steps = "
-                                 "custom_steps + 1): a shorter prefix has no encoder trajectory for the remaining steps")
-            if len(ride) != n_dec:
-                raise ValueError("mask_source = 'encoder': every decoder scale must ride in the coupled loop (all guided, or "
-                                 "one unguided scale) - a candidate decoded from z afterwards has no encoder trajectory")
-            coupled = True
-        else:
-            coupled = bool(self.couple and whole and fits)
-        self.last_translate_coupled = coupled
-        x0, c_src, uc, members = self._encode_front(image, encode_text)
-        if m is None:
-            m = self._auto_mask_ctx(x0, c_src, self.get_condition(decode_text, bsz)[0])[0]
-        if not coupled:
-            z_ensemble = self._encode_members(x0, c_src, uc, members)
-            return self._select(self.generate(z_ensemble, decode_text, mask=m, x0=x0), image, encode_text, decode_text)
-        c_tgt, _ = self.get_condition(decode_text, bsz)
-        mask_noise = {}
-        if not encoder:  # the reference's order: every member encoded, then member -> decoder scale, K draws each
-            for i, mem in enumerate(members):
-                for j in range(n_dec):
-                    mask_noise[i * n_dec + j] = self._mask_draws(len(sch) - mem[1], bsz)[0]
-        bc = bsz if fits else max(1, self.couple_max_tokens // (rows1 * tokens))  # samples per coupled call
-        per_call = max(1, min(self.MAX_FOLD // (bc * (1 + len(ride))), self.couple_max_tokens // (bc * rows1 * tokens)))
-        z_parts, lat_parts = [[] for _ in members], {}
-        for s0 in range(0, bsz, bc):
-            sl = slice(s0, min(bsz, s0 + bc))
-            nb = sl.stop - sl.start
-            for grp in self._groups([(mm[0], mm[1]) for mm in members]):
-                enc_scale, skip = members[grp[0]][0], members[grp[0]][1]
-                for idx in self._chunks(grp, per_call):
-                    n, nr = len(idx), len(ride)
-                    if main == "cfg" and len({dec_scales[j] for j in ride}) > 1:
-                        guidance = torch.tensor([dec_scales[j] for j in ride for _ in range(n * nb)], dtype=torch.float32)
-                    else:
-                        guidance = dec_scales[ride[0]]
-                    kw = {}
-                    if not encoder:  # decoder row (jr * n + mi) * nb + b
-                        kw = dict(mask_x0=x0[sl].contiguous(), qcoef=sch.coef_qsample(skip),
-                                  mask_noise=torch.cat([mask_noise[i * n_dec + j][:, sl] for j in ride for i in idx],
-                                                       dim=1).contiguous())
-                    z, x = self.engine.cycle_translate_masked(
-                        self.unet, _ffi.CD_SCHED_DDIM, x0[sl].repeat(n, 1, 1, 1), sch.coef_encode(skip), sch.coef_decode(skip),
-                        m[sl].contiguous(), mask_source=self.mask_source, enc_ctx_c=c_src[sl].repeat(n, 1, 1),
-                        enc_ctx_uc=uc[sl].repeat(n, 1, 1), enc_guidance=enc_scale, dec_ctx_c=c_tgt[sl].repeat(n * nr, 1, 1),
-                        dec_ctx_uc=uc[sl].repeat(n * nr, 1, 1), dec_guidance=guidance, n_dec=nr,
-                        noise=torch.cat([members[i][2][:, sl] for i in idx], dim=1).contiguous(), last_uses_x0=True, **kw)
-                    for mi, i in enumerate(idx):
-                        z_parts[i].append(z[mi * nb:(mi + 1) * nb].reshape(nb, -1))
-                        for jr, j in enumerate(ride):
-                            lat_parts.setdefault(i * n_dec + j, []).append(x[(jr * n + mi) * nb:(jr * n + mi + 1) * nb])
-        z_ensemble = [torch.cat(p, 0) for p in z_parts]
-        latents = {k: torch.cat(v, 0) for k, v in lat_parts.items()}
-        img_ensemble = self.generate(z_ensemble, decode_text, latents=latents, mask=m, x0=x0, mask_noise=mask_noise)
-        return self._select(img_ensemble, image, encode_text, decode_text)
-
-    def _control_ids(self, texts):
-        """token ids [B, L] of the prompts and the id that ends a prompt, from the text encoder's own tokenizer; a conditioning
-        stage without one (a callable embedder) falls back to the whitespace hash tokenizer, padded to the context length"""
-        from .text_encoders import EOS, BertHashTokenizer, BertWordPieceTokenizer, HashTokenizer
-        tok = getattr(self.cond_stage, "tokenizer", None)
-        if tok is None:
-            tok = HashTokenizer(getattr(self.cond_stage, "length", 77))
-        eos = BertHashTokenizer.SEP if isinstance(tok, (BertHashTokenizer, BertWordPieceTokenizer)) else EOS
-        return np.asarray(tok(list(texts))), eos
-
-    def _translate_ctrl(self, image, encode_text, decode_text, mask=None, attn_ctrl=None):
-        """translate() with cross-attention control: in the first n_ctrl = int(cac_steps * K) iterations of a member's K-step
-        loop the decoder's conditional rows take the source prompt's attention maps on the source image - recomputed from the
-        encoder's rows of the same forward - for the tokens both prompts share (attn_control.build_control; `attn_ctrl` replaces
-        the built (M, alpha, w)). The source rows only exist in the coupled loop, so this ALWAYS runs coupled; past
-        COUPLE_MAX_TOKENS it runs in chunks of samples, as mask_source = encoder does. Composes with a keep-mask of either
-        source. Draw order and member order are translate()'s."""
-        sch = self._schedule()
-        bsz = image.shape[0]
-        whole = all(self._white_box_loop(len(sch) - sk, sk) == len(sch) - sk for sk in self.skip_steps)
-        dec_scales = [float(sc) for sc in self.decoder_unconditional_guidance_scales]
-        n_dec = len(dec_scales)
-        kinds = [self._kind(sc) for sc in dec_scales]
-        main = "cfg" if "cfg" in kinds else kinds[0]
-        ride = [j for j in range(n_dec) if kinds[j] == main and (main == "cfg" or dec_scales[j] == dec_scales[kinds.index(main)])]
-        if not whole:
+        ctrl = attn_ctrl is not None or self.cac_steps > 0
+        if ctrl and not whole:
             raise ValueError("cross-attention control needs the DPM-Encoder over the whole chain (white_box_steps = custom_steps "
                              "+ 1): the steps past a shorter prefix have no source rows")
-        if len(ride) != n_dec or main == "uncond" or any(self._kind(float(sc)) == "uncond"
-                                                           for sc in self.encoder_unconditional_guidance_scales):
+        if ctrl and (len(ride) != n_dec or main == "uncond" or "uncond" in enc_kinds):
             raise ValueError("cross-attention control: every decoder scale must ride in the coupled loop (all guided, or one "
                              "unguided scale) and no scale may be 0 - the control acts on conditional rows")
-        m = self._latent_mask(mask, bsz) if mask is not None and mask is not AUTO_MASK else None
+        m = None if mask is None or mask is AUTO_MASK else self._latent_mask(mask, bsz)
         encoder = mask is not None and self.mask_source == "encoder"
-        enc_cfg = any(self._kind(float(sc)) == "cfg" for sc in self.encoder_unconditional_guidance_scales)
-        rows1 = (2 if enc_cfg else 1) + len(ride) * (2 if main == "cfg" else 1)  # rows of one sample of one member
-        tokens = self.image_size ** 2
-        fits = bsz * rows1 * tokens <= self.couple_max_tokens
-        self.last_translate_coupled = True
-        if attn_ctrl is None:
-            src_ids, eos = self._control_ids(encode_text)
-            tgt_ids, _ = self._control_ids(decode_text)
-            attn_ctrl = attn_control.build_control(src_ids, tgt_ids, self.cac_mode, eos_id=eos)
-        ctl = [torch.as_tensor(t, dtype=torch.float32).to(self.device) for t in attn_ctrl]
-        if ctl[0].shape[0] != bsz:
-            raise ValueError("attn_ctrl must carry one control per sample (%d), got %d" % (bsz, ctl[0].shape[0]))
+        if encoder and not whole:
+            raise ValueError("mask_source = 'encoder' needs the DPM-Encoder over the whole chain (white_box_steps = "
+                             "custom_steps + 1): a shorter prefix has no encoder trajectory for the remaining steps")
+        if encoder and len(ride) != n_dec:
+            raise ValueError("mask_source = 'encoder': every decoder scale must ride in the coupled loop (all guided, or "
+                             "one unguided scale) - a candidate decoded from z afterwards has no encoder trajectory")
+        coupled = ctrl or encoder or bool(self.couple and whole and fits)
+        self.last_translate_coupled = coupled
+        ctl = None
+        if ctrl:
+            if attn_ctrl is None:
+                src_ids, eos = self._control_ids(encode_text)
+                tgt_ids, _ = self._control_ids(decode_text)
+                attn_ctrl = attn_control.build_control(src_ids, tgt_ids, self.cac_mode, eos_id=eos)
+            ctl = [torch.as_tensor(t, dtype=torch.float32).to(self.device) for t in attn_ctrl]
+            if ctl[0].shape[0] != bsz:
+                raise ValueError("attn_ctrl must carry one control per sample (%d), got %d" % (bsz, ctl[0].shape[0]))
         x0, c_src, uc, members = self._encode_front(image, encode_text)
-        c_tgt, _ = self.get_condition(decode_text, bsz)
+        c_tgt = self.get_condition(decode_text, bsz)[0] if coupled or mask is AUTO_MASK else None
         if mask is AUTO_MASK:
             m = self._auto_mask_ctx(x0, c_src, c_tgt)[0]
+        masked = {} if m is None else dict(mask=m, x0=x0)  # generate()'s share of the keep-mask
+        if not coupled:  # what encode() + forward() do
+            z_ensemble = self._encode_members(x0, c_src, uc, members)
+            return self._select(self.generate(z_ensemble, decode_text, **masked), image, encode_text, decode_text)
         mask_noise = {}
         if m is not None and not encoder:  # the reference's order: every member encoded, then member -> decoder scale, K draws
             for i, mem in enumerate(members):
@@ -663,38 +549,50 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
             nb = sl.stop - sl.start
             for grp in self._groups([(mm[0], mm[1]) for mm in members]):
                 enc_scale, skip = members[grp[0]][0], members[grp[0]][1]
-                n_ctrl = int(self.cac_steps * (len(sch) - skip))
                 for idx in self._chunks(grp, per_call):
                     n, nr = len(idx), len(ride)
                     if main == "cfg" and len({dec_scales[j] for j in ride}) > 1:
                         guidance = torch.tensor([dec_scales[j] for j in ride for _ in range(n * nb)], dtype=torch.float32)
                     else:
                         guidance = dec_scales[ride[0]]
-                    kw = {}
+                    args = (self.unet, _ffi.CD_SCHED_DDIM, x0[sl].repeat(n, 1, 1, 1), sch.coef_encode(skip), sch.coef_decode(skip))
+                    kw = dict(enc_ctx_c=c_src[sl].repeat(n, 1, 1), enc_ctx_uc=uc[sl].repeat(n, 1, 1), enc_guidance=enc_scale,
+                              dec_ctx_c=c_tgt[sl].repeat(n * nr, 1, 1), dec_ctx_uc=uc[sl].repeat(n * nr, 1, 1),
+                              dec_guidance=guidance, n_dec=nr, last_uses_x0=True,
+                              noise=torch.cat([members[i][2][:, sl] for i in idx], dim=1).contiguous())
                     if m is not None:
-                        kw = dict(mask=m[sl].contiguous(), mask_source=self.mask_source)
+                        kw["mask_source"] = self.mask_source
                         if not encoder:  # decoder row (jr * n + mi) * nb + b
-                            kw.update(mask_x0=x0[sl].contiguous(), qcoef=sch.coef_qsample(skip),
-                                      mask_noise=torch.cat([mask_noise[i * n_dec + j][:, sl] for j in ride for i in idx],
-                                                           dim=1).contiguous())
-                    z, x = self.engine.cycle_translate_ctrl(
-                        self.unet, _ffi.CD_SCHED_DDIM, x0[sl].repeat(n, 1, 1, 1), sch.coef_encode(skip), sch.coef_decode(skip),
-                        mapper=ctl[0][sl].contiguous(), alpha=ctl[1][sl].contiguous(), weight=ctl[2][sl].contiguous(),
-                        n_ctrl=n_ctrl, enc_ctx_c=c_src[sl].repeat(n, 1, 1), enc_ctx_uc=uc[sl].repeat(n, 1, 1),
-                        enc_guidance=enc_scale, dec_ctx_c=c_tgt[sl].repeat(n * nr, 1, 1), dec_ctx_uc=uc[sl].repeat(n * nr, 1, 1),
-                        dec_guidance=guidance, n_dec=nr, noise=torch.cat([members[i][2][:, sl] for i in idx], dim=1).contiguous(),
-                        last_uses_x0=True, **kw)
+                            kw.update(mask_x0=x0[sl].contiguous(), qcoef=sch.coef_qsample(skip), mask_noise=torch.cat(
+                                [mask_noise[i * n_dec + j][:, sl] for j in ride for i in idx], dim=1).contiguous())
+                    if ctl is not None:
+                        if m is not None:
+                            kw["mask"] = m[sl].contiguous()
+                        z, x = self.engine.cycle_translate_ctrl(
+                            *args, mapper=ctl[0][sl].contiguous(), alpha=ctl[1][sl].contiguous(), weight=ctl[2][sl].contiguous(),
+                            n_ctrl=int(self.cac_steps * (len(sch) - skip)), **kw)
+                    elif m is not None:
+                        z, x = self.engine.cycle_translate_masked(*args, m[sl].contiguous(), **kw)
+                    else:
+                        z, x = self.engine.cycle_translate(*args, **kw)
                     for mi, i in enumerate(idx):
                         z_parts[i].append(z[mi * nb:(mi + 1) * nb].reshape(nb, -1))
                         for jr, j in enumerate(ride):
                             lat_parts.setdefault(i * n_dec + j, []).append(x[(jr * n + mi) * nb:(jr * n + mi + 1) * nb])
-        z_ensemble = [torch.cat(p, 0) for p in z_parts]
-        latents = {k: torch.cat(v, 0) for k, v in lat_parts.items()}
-        if m is not None:
-            img_ensemble = self.generate(z_ensemble, decode_text, latents=latents, mask=m, x0=x0, mask_noise=mask_noise)
-        else:
-            img_ensemble = self.generate(z_ensemble, decode_text, latents=latents)
+        z_ensemble = [p[0] if len(p) == 1 else torch.cat(p, 0) for p in z_parts]  # one part: the whole batch fitted
+        latents = {k: v[0] if len(v) == 1 else torch.cat(v, 0) for k, v in lat_parts.items()}
+        img_ensemble = self.generate(z_ensemble, decode_text, latents=latents, mask_noise=mask_noise, **masked)
         return self._select(img_ensemble, image, encode_text, decode_text)
+
+    def _control_ids(self, texts):
+        """token ids [B, L] of the prompts and the id that ends a prompt, from the text encoder's own tokenizer; a conditioning
+        stage without one (a callable embedder) falls back to the whitespace hash tokenizer, padded to the context length"""
+        from .text_encoders import EOS, BertHashTokenizer, BertWordPieceTokenizer, HashTokenizer
+        tok = getattr(self.cond_stage, "tokenizer", None)
+        if tok is None:
+            tok = HashTokenizer(getattr(self.cond_stage, "length", 77))
+        eos = BertHashTokenizer.SEP if isinstance(tok, (BertHashTokenizer, BertWordPieceTokenizer)) else EOS
+        return np.asarray(tok(list(texts))), eos
 
     def forward(self, z_ensemble, original_img, encode_text, decode_text, mask=None):
         """`mask` (pixel-space [B, 1, R, R] in [0, 1], 1 = keep the source): the reference's sample_with_eps(mask=, x0=) decode.
