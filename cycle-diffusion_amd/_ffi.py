@@ -83,6 +83,7 @@ SIGNATURES = {
                                 _VP, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP, _VP, _I, _I, _VP, _VP],
     "cd_ilvr_decode": [_VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _U64, _VP, _I, _I, _I, _VP, _VP, _U64, _VP],
     "cd_automask": [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _F, _F, _VP, _U64, _I, _F, _F, _I, _VP, _VP],
+    "cd_word_maps": [_VP, _I, _VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _F, _F, _VP, _U64, _I, _I, _I, _VP, C.POINTER(_I)],
     "cd_pix_refine": [_VP, _I, _I, _VP, _I, _I, _VP, _VP, _U64],
     "cd_op_pack_conv_weight": [_VP, _VP, _I, _I, _I, _I, _I, C.POINTER(_VP), C.POINTER(_I), C.POINTER(_I)],
     "cd_op_free": [_VP, _VP],
@@ -106,6 +107,7 @@ SIGNATURES = {
     "cd_op_cross_attention_ctrl": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _VP],
     "cd_op_cross_attention_ctrl_ex": [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I,
                                       _VP],
+    "cd_op_cross_attention_maps": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _VP],
     "cd_op_attention_ex": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _VP, _I, _I, _VP],
     "cd_op_lowpass": [_VP, _VP, _I, _I, _I, _I, _VP],
     "cd_op_softmax_rows": [_VP, _VP, _I64, _I, _VP],

@@ -7,6 +7,9 @@ build_control() turns the token ids of a source and a target prompt into what cd
 It works on id arrays, not on strings: any tokenizer that pads to a fixed length and marks the end of the prompt with one id
 will do (the CLIP BPE, the BERT WordPiece and the hash stand-ins of gan_wrapper/text_encoders.py).
 
+word_selector() / edited_selector() build the key-position selectors of the per-word attention maps (cd_word_maps, DESIGN.md
+17) from the same id arrays, and blend_mask() turns such maps into a keep-mask by prompt-to-prompt's LocalBlend rule.
+
 The alignment is the global (Needleman-Wunsch) alignment of prompt-to-prompt's seq_aligner: match +1, gap 0, mismatch -1,
 ties resolved in its order (gap in the source, gap in the target, diagonal). With these scores a substituted token never
 aligns diagonally (two gaps score 0 > -1): it shows up as one source token left out and one target token inserted.
@@ -98,3 +101,62 @@ def build_control(src_ids, tgt_ids, mode="refine", reweight=None, eos_id=CLIP_EO
             else:
                 w[b, 1:nt][t[1:nt] == key] = float(scale)
     return M, alpha, w
+
+
+# ------------------------------------------------------------------------------------------------ per-word attention maps
+MAX_WORDS = 8  # selector rows of one cd_word_maps call (csrc/kernels.h kMapWords)
+
+
+def word_selector(ids, words, eos_id=CLIP_EOS):
+    """ids: one padded id row [L]; words: N token-id sequences (one word may be several tokens). Returns float32 [N, L]: row n
+    is 1 at every position of every occurrence of words[n] between the start token and the end token, 0 elsewhere."""
+    ids = np.asarray(ids)
+    if ids.ndim != 1:
+        raise ValueError("ids must be one id row [L], got %s" % (ids.shape,))
+    words = [[int(t) for t in np.atleast_1d(np.asarray(w))] for w in words]
+    if not 1 <= len(words) <= MAX_WORDS:
+        raise ValueError("a selector holds 1 to %d words, got %d" % (MAX_WORDS, len(words)))
+    end = prompt_length(ids, eos_id)
+    sel = np.zeros((len(words), len(ids)), dtype=np.float32)
+    for n, w in enumerate(words):
+        for at in range(1, end - len(w) + 1):
+            if len(w) and list(ids[at:at + len(w)]) == w:
+                sel[n, at:at + len(w)] = 1.0
+        if not sel[n].any():
+            raise ValueError("word %d (tokens %s) does not occur in the prompt" % (n, w))
+    return sel
+
+
+def edited_selector(src_ids, tgt_ids, eos_id=CLIP_EOS):
+    """src_ids, tgt_ids: one padded id row [L] each. Returns float32 [1, L]: 1 at the target positions align() does not pair
+    with an equal source token - the words the edit introduces."""
+    s, t = np.asarray(src_ids), np.asarray(tgt_ids)
+    if s.ndim != 1 or s.shape != t.shape:
+        raise ValueError("src_ids and tgt_ids must both be one id row [L], got %s and %s" % (s.shape, t.shape))
+    ns, nt = prompt_length(s, eos_id), prompt_length(t, eos_id)
+    sel = np.zeros((1, len(t)), dtype=np.float32)
+    for jj, ii in enumerate(align(list(s[1:ns]), list(t[1:nt]))):
+        if ii < 0 or s[1 + ii] != t[1 + jj]:
+            sel[0, 1 + jj] = 1.0
+    if not sel.any():
+        raise ValueError("the target prompt introduces no token: every one is aligned with an equal source token")
+    return sel
+
+
+def blend_mask(maps, threshold=0.3, pool=3, factor=1):
+    """prompt-to-prompt's LocalBlend rule on maps [B, N, h, w] (a torch tensor): sum over the words, max_pool2d(pool, 1,
+    pool // 2), divide by the image's own maximum (an all-zero image edits nothing), edit = value > threshold. Returns the
+    keep-mask 1 - edit as float32 [B, 1, h * factor, w * factor] by nearest replication: the orientation and form
+    translate(mask=) takes (1 = keep the source)."""
+    import torch
+    import torch.nn.functional as F
+    if maps.dim() != 4:
+        raise ValueError("maps must be [B, N, h, w], got %s" % (tuple(maps.shape),))
+    if pool < 1 or pool % 2 != 1 or int(factor) < 1:
+        raise ValueError("pool must be odd and >= 1, factor >= 1; got pool = %s, factor = %s" % (pool, factor))
+    m = maps.float().sum(1, keepdim=True)
+    m = F.max_pool2d(m, pool, 1, pool // 2)
+    mx = m.amax(dim=(1, 2, 3), keepdim=True)
+    m = torch.where(mx > 0, m / mx.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(m))
+    keep = 1.0 - (m > threshold).float()
+    return keep.repeat_interleave(int(factor), 2).repeat_interleave(int(factor), 3).contiguous()

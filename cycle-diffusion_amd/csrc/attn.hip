@@ -755,6 +755,134 @@ __global__ __launch_bounds__(256, DV <= 96 ? 2 : 1) void k_cross_attention_ctrl(
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Per-word cross-attention maps: the score / softmax half of k_cross_attention_ctrl for ONE source, with the
+// probabilities reduced in registers against a selector table instead of multiplied into V. A workgroup owns 128 queries of
+// one batch row and loops the heads itself (K of the head restaged between two barriers), so the head sum has one fixed
+// order and needs neither partial buffers nor atomics. Per head: K [96][DQK+8] in LDS (rows >= L, columns >= D zero), 96
+// scores per query in three accumulator blocks, keys >= L to -inf, maximum, exp2, row sum; then for every word n the lane
+// dots its 48 fp32 probabilities with selector row n - one 16-byte LDS read per four keys, the same address in all lanes of a
+// half-wave (a broadcast) - adds the partner half's 48 by __shfl_xor(., 32) and scales by 1 / l. Nothing is rounded to 16 bits.
+template <int DQK>
+__global__ __launch_bounds__(256) void k_cross_attention_maps(WordMapParams p) {
+  constexpr int NT = 256, CK = kCtrlKeys, NG = CK / 32;
+  constexpr int KLD = DQK + 8, NKS = DQK / 16, CPR = DQK / 8;
+  __shared__ __attribute__((aligned(16))) bf16_t Ks[CK * KLD];
+  __shared__ __attribute__((aligned(16))) float Ss[kMapWords * CK];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qi = lane & 31, half = lane >> 5;
+  const int b = blockIdx.z, bs = b % p.B_sel;
+  const int q = blockIdx.x * 128 + wave * 32 + qi;
+  const int D = p.D, L = p.L, N = p.N;
+
+  // ---- the selector rows of this batch row: zero beyond L and beyond N (visible after the first head's barriers)
+  for (int id = tid; id < kMapWords * CK; id += NT) {
+    const int n = id / CK, j = id % CK;
+    Ss[id] = (n < N && j < L) ? p.sel[((int64_t)bs * N + n) * L + j] : 0.f;
+  }
+
+  const float qsc = p.scale * 1.44269504088896340736f;
+  float macc[kMapWords];
+#pragma unroll
+  for (int n = 0; n < kMapWords; ++n) macc[n] = 0.f;
+
+  for (int h = 0; h < p.H; ++h) {
+    if (h) __syncthreads();  // everyone is done reading the previous head's K
+    {
+      const bf16_t* kb = p.k + (int64_t)b * p.k_bs + h * D;
+      for (int id = tid; id < CK * CPR; id += NT) {
+        const int row = id / CPR, ch = id % CPR;
+        uint4 raw = make_uint4(0, 0, 0, 0);
+        if (row < L && ch * 8 < D) raw = *(const uint4*)(kb + (int64_t)row * p.ldk + ch * 8);
+        *(uint4*)(&Ks[row * KLD + ch * 8]) = raw;
+      }
+    }
+    __syncthreads();
+    // Q fragments (B operand of S^T = K Q^T): lane holds Q[q][ks*16 + 8*half .. +7], in log2 score units
+    bf16x8 qf[NKS];
+    {
+      const bf16_t* qb = p.q + (int64_t)b * p.q_bs + h * D;
+#pragma unroll
+      for (int ks = 0; ks < NKS; ++ks) {
+        const int d0 = ks * 16 + 8 * half;
+        uint4 raw = make_uint4(0, 0, 0, 0);
+        if (q < p.Tq && d0 < D) raw = *(const uint4*)(qb + (int64_t)q * p.ldq + d0);
+        if (!p.q_log2) {
+          float f[8];
+          unpack8(raw, f);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) f[e] *= qsc;
+          raw = pack8(f);
+        }
+        qf[ks] = *(bf16x8*)&raw;
+      }
+    }
+    // ---- S^T = K Q^T over all 96 keys
+    f32x16 s[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) s[g][r] = 0.f;
+#pragma unroll
+      for (int ks = 0; ks < NKS; ++ks) {
+        const bf16x8 kf = *(const bf16x8*)(Ks + (g * 32 + qi) * KLD + ks * 16 + 8 * half);
+        s[g] = CD_MFMA_32x32x16(kf, qf[ks], s[g]);
+      }
+    }
+    // ---- keys beyond L out, maximum of the query (a lane holds 48 of its 96 scores, lane ^ 32 the others)
+    float mx = -INFINITY;
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = g * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+        s[g][r] = key < L ? s[g][r] : -INFINITY;
+        mx = fmaxf(mx, s[g][r]);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    // ---- exp2(s - max) (<= 1, a masked key gives exactly 0) and the row sum
+    float ps = 0.f;
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        s[g][r] = __builtin_amdgcn_exp2f(s[g][r] - mx);
+        ps += s[g][r];
+      }
+    ps += __shfl_xor(ps, 32);
+    const float inv = 1.0f / ps;  // ps >= 1: the maximum's own term
+    // ---- mass on the chosen keys: register r of group g is key g*32 + 8*(r>>2) + 4*half + (r&3)
+#pragma unroll
+    for (int n = 0; n < kMapWords; ++n) {
+      if (n < N) {
+        float d = 0.f;
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+          for (int rq = 0; rq < 4; ++rq) {
+            const float4 sv = *(const float4*)(&Ss[n * CK + g * 32 + 8 * rq + 4 * half]);
+            d = fmaf(sv.x, s[g][rq * 4 + 0], d);
+            d = fmaf(sv.y, s[g][rq * 4 + 1], d);
+            d = fmaf(sv.z, s[g][rq * 4 + 2], d);
+            d = fmaf(sv.w, s[g][rq * 4 + 3], d);
+          }
+        d += __shfl_xor(d, 32);
+        macc[n] = fmaf(d, inv, macc[n]);
+      }
+    }
+  }
+
+  // ---- store: both halves hold the query's sums; the lower one writes, queries contiguous per word
+  if (q < p.Tq && half == 0) {
+    const float invh = 1.0f / (float)p.H;
+    float* mb = p.maps + (int64_t)b * N * p.Tq + q;
+#pragma unroll
+    for (int n = 0; n < kMapWords; ++n)
+      if (n < N) mb[(int64_t)n * p.Tq] = macc[n] * invh;
+  }
+}
+
 // the step-invariant value tensors of the control: grid (L, rows), threads over the channels
 __global__ __launch_bounds__(256) void k_ctrl_values(const bf16_t* __restrict__ v, const float* __restrict__ M,
                                                      const float* __restrict__ alpha, const float* __restrict__ w, int B_ctrl,
@@ -798,6 +926,28 @@ void launch_cross_attention_ctrl(hipStream_t st, const CtrlAttnParams& p) {
     default: CD_CHECK(false, "cross-attention control: head dim %d unsupported (32, 40, 64, 80, 160)", p.D);
   }
 #undef CD_CTRL
+}
+
+void launch_cross_attention_maps(hipStream_t st, const WordMapParams& p) {
+  CD_CHECK(p.B > 0 && p.H > 0 && p.Tq > 0 && p.q && p.k && p.sel && p.maps, "cross-attention maps: empty launch");
+  CD_CHECK(p.B_sel > 0 && p.B % p.B_sel == 0, "cross-attention maps: %d selector entries for a batch of %d", p.B_sel, p.B);
+  CD_CHECK(p.N >= 1 && p.N <= kMapWords, "cross-attention maps: %d words outside [1, %d]", p.N, kMapWords);
+  CD_CHECK(p.L > 0 && p.L <= kCtrlKeys, "cross-attention maps: context length %d above the %d keys the kernel keeps resident",
+           p.L, kCtrlKeys);
+  CD_CHECK((p.ldq % 8) == 0 && (p.ldk % 8) == 0 && (p.q_bs % 8) == 0 && (p.k_bs % 8) == 0, "cross-attention maps: leading dims");
+  CD_CHECK((((uintptr_t)p.q | (uintptr_t)p.k) & 15) == 0 && (((uintptr_t)p.sel | (uintptr_t)p.maps) & 3) == 0,
+           "cross-attention maps: pointer alignment");
+  const dim3 grid(ceil_div(p.Tq, 128), 1, p.B);
+#define CD_MAPS(DQK) hipLaunchKernelGGL((k_cross_attention_maps<DQK>), grid, dim3(256), 0, st, p)
+  switch (p.D) {  // the control kernel's table
+    case 32: CD_MAPS(32); break;
+    case 40: CD_MAPS(48); break;
+    case 64: CD_MAPS(64); break;
+    case 80: CD_MAPS(80); break;
+    case 160: CD_MAPS(160); break;
+    default: CD_CHECK(false, "cross-attention maps: head dim %d unsupported (32, 40, 64, 80, 160)", p.D);
+  }
+#undef CD_MAPS
 }
 
 void launch_ctrl_values(hipStream_t st, const bf16_t* v, const float* M, const float* alpha, const float* w, int rows,

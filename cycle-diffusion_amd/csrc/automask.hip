@@ -10,6 +10,9 @@
 //                       then a halving tree in LDS; one partial per block
 //   k_automask_finish   mean[b] = (partials added in ascending block order) / HW, cl = ratio * mean, v = min(map, cl) / cl,
 //                       edit = v > thr, dilated by a (2 d + 1)^2 max through an LDS tile with a halo; keep = 1 - edit
+// The per-word attention maps reuse k_automask_qsample and keep their two sums here, in the same arithmetic:
+//   k_word_map_accumulate  one included layer of a forward into that forward's per-row sums, nearest replication to the latent grid
+//   k_word_map_fold        the draws of a forward into the call's sums, ascending; the scale after the last forward
 #include "common.h"
 #include "gauss.h"
 #include "kernels.h"
@@ -152,6 +155,28 @@ __global__ void __launch_bounds__(kThreads) k_automask_finish(AutoMaskArgs a) {
   if (a.map_out) a.map_out[at] = map_of(a, accb[y * W + x]);
 }
 
+// ---- per-word attention maps: the two sums around cd_word_maps' forwards, grid-stride, a thread owns its elements
+__global__ void __launch_bounds__(kThreads) k_word_map_accumulate(WordMapAccum a) {
+  const int f = a.h / a.s;
+  const int64_t hw = (int64_t)a.h * a.w, n = (int64_t)a.rows * a.N * hw;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t rn = e / hw;  // row * N + word
+    const int pix = (int)(e - rn * hw), y = pix / a.w, x = pix - y * a.w;
+    const float v = a.layer[rn * a.s * a.s + (y / f) * a.s + x / f];
+    a.acc[e] = a.first ? v : a.acc[e] + v;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) k_word_map_fold(WordMapFold a) {
+  const int64_t n = (int64_t)a.B * a.per;
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+    float t = a.first ? 0.f : a.total[e];
+    for (int i = 0; i < a.n_chunk; ++i) t += a.acc[(int64_t)i * n + e];  // draws ascending
+    a.total[e] = t;
+    if (a.out) a.out[e] = t * a.scale;
+  }
+}
+
 bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 void check_automask(const AutoMaskArgs& a) {
@@ -185,6 +210,19 @@ void launch_automask_finish(hipStream_t st, const AutoMaskArgs& a) {
   CD_CHECK(a.nblk == automask_sum_blocks(a.H * a.W) && a.partial && a.keep_out && a.n_total > 0, "bad keep-mask arguments");
   hipLaunchKernelGGL(k_automask_sum, dim3(a.nblk, a.B), dim3(kThreads), 0, st, a);
   hipLaunchKernelGGL(k_automask_finish, dim3(ceil_div(a.W, kTile), ceil_div(a.H, kTile), a.B), dim3(kThreads), 0, st, a);
+}
+
+void launch_word_map_accumulate(hipStream_t st, const WordMapAccum& a) {
+  CD_CHECK(a.layer && a.acc && a.rows > 0 && a.N > 0 && a.s > 0 && a.h > 0 && a.w == a.h, "word maps: empty accumulate");
+  CD_CHECK(a.h % a.s == 0, "word maps: a %d x %d token grid does not divide the %d x %d latent", a.s, a.s, a.h, a.w);
+  const int64_t nb = ((int64_t)a.rows * a.N * a.h * a.w + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(k_word_map_accumulate, dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(kThreads), 0, st, a);
+}
+
+void launch_word_map_fold(hipStream_t st, const WordMapFold& a) {
+  CD_CHECK(a.acc && a.total && a.n_chunk > 0 && a.B > 0 && a.per > 0, "word maps: empty fold");
+  const int64_t nb = ((int64_t)a.B * a.per + kThreads - 1) / kThreads;
+  hipLaunchKernelGGL(k_word_map_fold, dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(kThreads), 0, st, a);
 }
 
 }  // namespace cd

@@ -394,7 +394,7 @@ struct MaskArgs {
 // The generator's streams are banded by loop, 4096 streams to a band (tests/_philox_ref.py STREAMS):
 // 0 x_T and 1 + i the encoder, 0x1000 + i the decode, 0x2000 / 0x2001 + i the refinement, 0x3000 + j the inversion,
 // 0x4000 + slot the keep-mask's q-sample, 0x5000 + i ILVR's reference, 0x6000 + i the keep-mask estimate's draws, 0x7a65 the
-// VAE posterior. A loop that draws from the
+// VAE posterior, 0x8000 + i the per-word attention maps' draws. A loop that draws from the
 // generator (`noise` is NULL) may not walk into the next loop's numbers; a noise tensor has no such limit.
 constexpr int kStreamBandSteps = 0xFFF;
 void check_stream_band(const void* noise, int steps, const char* what) {
@@ -1200,6 +1200,85 @@ int cd_automask(cd_handle h, int net, const float* x0, const float* ctx_src, con
   CD_API_END
 }
 
+// Per-word cross-attention heat maps: n_draws noised copies of x0 at one level through the CONDITIONAL forward
+// only, every text cross-attention in the side window reduced by k_cross_attention_maps beside its own launch. A draw's layers
+// add up inside its forward (per-row sums), the draws of a forward are then added to the call's sums in ascending order, so
+// the result does not depend on how max_rows cuts the draws into forwards. The draws use the stream band 0x8000 + i: the
+// band at 0x7000 holds the VAE posterior's stream 0x7a65.
+int cd_word_maps(cd_handle h, int net, const float* x0, const float* ctx, int ctx_len, int B, const float* sel, int B_sel,
+                 int N, int n_draws, int t, float qa, float qb, const float* noise, uint64_t seed, int max_rows,
+                 int min_side, int max_side, float* maps_out, int* n_layers_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x0 && ctx && sel && maps_out && B > 0 && B_sel > 0 && ctx_len > 0, "bad argument");
+  UNet* u = get_unet(h, net);
+  CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer && u->desc.context_dim > 0,
+           "cd_word_maps: the maps are those of the text cross-attention; this network has no text context (a pixel network)");
+  CD_CHECK(!u->f32, "cd_word_maps is not built for fp32 / fp32x3 networks (their transformer blocks run the fp32 attention of "
+                    "st_f32.hip): use the 16-bit precision");
+  CD_CHECK(ctx_len <= kCtrlKeys, "cd_word_maps: context length %d above the %d keys the kernel keeps resident", ctx_len,
+           kCtrlKeys);
+  CD_CHECK(N >= 1 && N <= kMapWords, "cd_word_maps: N = %d words outside [1, %d]", N, kMapWords);
+  CD_CHECK(n_draws >= 1 && n_draws <= kStreamBandSteps, "cd_word_maps: n_draws must lie in [1, %d] (the width of its stream "
+                                                        "band), got %d", kStreamBandSteps, n_draws);
+  CD_CHECK(B % B_sel == 0, "cd_word_maps shape mismatch: %d selector entries for a batch of %d", B_sel, B);
+  CD_CHECK(max_rows >= B, "cd_word_maps: max_rows = %d holds no draw of a batch of %d", max_rows, B);
+  CD_CHECK(min_side >= 0 && min_side <= max_side, "cd_word_maps: side window [%d, %d] is empty (min_side > max_side)", min_side,
+           max_side);
+  const int n_layers = u->count_text_blocks(min_side, max_side);
+  CD_CHECK(n_layers > 0, "cd_word_maps: no transformer block has a token grid side in [%d, %d]", min_side, max_side);
+  const int C = u->desc.in_channels, R = u->image_size, HW = R * R, Co = u->out_channels, Dc = u->desc.context_dim;
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  const int64_t per_map = (int64_t)N * HW;
+  float* total = (float*)h->arena.alloc((size_t)B * per_map * 4);
+  const size_t buffers = h->arena.mark();
+  const int per_fwd = std::min(n_draws, std::max(1, max_rows / B));
+  const int64_t per_draw = (int64_t)B * C * HW;
+  AutoMaskNoised q;
+  q.x0 = x0; q.qa = qa; q.qb = qb; q.seed = seed; q.B = B; q.C = C; q.HW = HW;
+  WordMapCollect wm;
+  wm.sel = sel; wm.N = N; wm.B_sel = B_sel; wm.min_side = min_side; wm.max_side = max_side; wm.B = B;
+  bf16_t* xin = nullptr;
+  float *eh = nullptr, *tvec = nullptr;
+  int cur = 0;  // draws the buffers and the network's context are laid out for
+  for (int i0 = 0; i0 < n_draws; i0 += per_fwd) {
+    const int nc = std::min(per_fwd, n_draws - i0), rows = nc * B;
+    if (nc != cur) {  // the first forward, and a shorter last one
+      h->arena.release(buffers);
+      const size_t one = (size_t)B * ctx_len * Dc;
+      bf16_t* cx = (bf16_t*)h->arena.alloc((size_t)rows * ctx_len * Dc * 2);
+      for (int j = 0; j < nc; ++j)  // the context once per draw, converted as make_ctx converts it
+        launch_nchw_to_nhwc(h->st, ctx, cx + j * one, B * ctx_len, Dc, 1, Dc, 1.f, 0.f, 0);
+      u->set_context(c, cx, rows, ctx_len);
+      xin = (bf16_t*)h->arena.alloc((size_t)rows * HW * u->in_cpad * 2);
+      HIP_CHECK(hipMemsetAsync(xin, 0, (size_t)rows * HW * u->in_cpad * 2, h->st));  // the pad channels
+      eh = (float*)h->arena.alloc((size_t)rows * HW * Co * 4);
+      tvec = (float*)h->arena.alloc((size_t)rows * 4);
+      launch_fill_f32(h->st, tvec, (float)t, rows);
+      wm.acc = (float*)h->arena.alloc((size_t)rows * per_map * 4);
+      q.xin.xin = xin; q.xin.cpad = u->in_cpad; q.xin.dup = 0;
+      cur = nc;
+    }
+    q.n_draws = nc;
+    q.noise = noise ? noise + (int64_t)i0 * per_draw : nullptr;
+    q.stream0 = (uint32_t)(0x8000 + i0);
+    launch_automask_qsample(h->st, q);
+    wm.n_chunk = nc;
+    UNetIO io; io.xin = xin; io.B = rows; io.t_explicit = tvec; io.t_shared = false; io.out = eh; io.out_ld = Co;
+    io.maps = &wm;
+    u->forward(c, io);
+    CD_CHECK(wm.layers == n_layers, "cd_word_maps: the forward collected %d blocks of %d", wm.layers, n_layers);
+    WordMapFold f;
+    f.acc = wm.acc; f.total = total; f.n_chunk = nc; f.B = B; f.per = per_map; f.first = i0 == 0 ? 1 : 0;
+    if (i0 + nc == n_draws) { f.out = maps_out; f.scale = 1.0f / (float)(n_draws * n_layers); }
+    launch_word_map_fold(h->st, f);
+    h->pacer.tick(h->st);
+  }
+  if (n_layers_out) *n_layers_out = n_layers;
+  CD_API_END
+}
+
 // ------------------------------------------------------------------ single-kernel entry points
 int cd_op_pack_conv_weight(cd_handle h, const float* w_host, int N, int Cin, int KH, int KW, int geglu,
                            void** packed_dev, int* Npad, int* Cpad) {
@@ -1598,6 +1677,30 @@ int cd_op_cross_attention_ctrl_ex(cd_handle h, const float* q_own, const float* 
   enter_engine(h);
   op_cross_attention_ctrl(h, q_own, q_src, k_own, k_src, v_own, mapper, alpha, weight, B, B_src, B_ctrl, H, Tq, L, L_buf, D,
                           scale, q_log2, opad, o);
+  CD_API_END
+}
+
+// k_cross_attention_maps on caller-built operands: q [B, Tq, H*D], k [B, L_buf, H*D] (rows L .. L_buf-1 must not be read),
+// sel [B_sel, N, L] -> maps [B, N, Tq]
+int cd_op_cross_attention_maps(cd_handle h, const float* q, const float* k, const float* sel, int B, int B_sel, int H,
+                               int Tq, int L, int L_buf, int D, int N, float scale, int q_log2, float* maps) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && q && k && sel && maps, "bad argument");
+  CD_CHECK(B > 0 && B_sel > 0 && H > 0 && Tq > 0 && D > 0 && L > 0 && L_buf >= L, "bad argument");
+  ArenaScope arena_scope(h->arena);
+  const int C = H * D;
+  auto to16 = [&](const float* src, int64_t rows) {
+    bf16_t* d = (bf16_t*)h->arena.alloc((size_t)rows * C * 2);
+    launch_nchw_to_nhwc(h->st, src, d, (int)rows, C, 1, C, 1.f, 0.f, 0);
+    return d;
+  };
+  WordMapParams p;
+  p.q = to16(q, (int64_t)B * Tq); p.k = to16(k, (int64_t)B * L_buf); p.sel = sel; p.maps = maps;
+  p.B = B; p.B_sel = B_sel; p.H = H; p.Tq = Tq; p.L = L; p.D = D; p.N = N;
+  p.ldq = C; p.ldk = C; p.q_bs = (int64_t)Tq * C; p.k_bs = (int64_t)L_buf * C;
+  p.scale = scale; p.q_log2 = q_log2 != 0;
+  launch_cross_attention_maps(h->st, p);
   CD_API_END
 }
 

@@ -267,6 +267,19 @@ struct AttnCtrl {
   int src_b0 = 0, B_src = 0;
 };
 
+// Per-word attention maps of one forward (cd_word_maps): every text cross-attention whose token grid side lies
+// in the window also runs k_cross_attention_maps on its own q and cached keys and adds the result into the per-row sums `acc`.
+// The attention output itself is the launch it always was. Rows are (draw i, sample b) = i * B + b.
+struct WordMapCollect {
+  const float* sel = nullptr;  // [B_sel][N][L] device
+  int N = 0, B_sel = 0;
+  int min_side = 0, max_side = 0;  // 0, 0 = every block
+  float* acc = nullptr;            // [rows][N][h][w] sums over the included layers, in the forward's order
+  int B = 0, n_chunk = 0;          // rows = n_chunk * B: sample b of draw i uses selector entry b % B_sel
+  mutable int layers = 0;          // blocks included so far in this forward
+  bool takes(int side) const { return (min_side == 0 && max_side == 0) || (side >= min_side && side <= max_side); }
+};
+
 struct UNetIO {
   const bf16_t* xin = nullptr;   // NHWC bf16 [B][H][W][Cpad_in]
   int B = 0;
@@ -283,6 +296,7 @@ struct UNetIO {
   // with dup_tail = the decoder's sample count. cfg_dup is the case dup_tail = B / 2. 0 = no repeated rows.
   int dup_tail = 0;
   const AttnCtrl* ctrl = nullptr;     // cross-attention control of this forward, or null (16-bit path only)
+  const WordMapCollect* maps = nullptr;  // per-word attention maps collected beside this forward, or null (16-bit path only)
   float* out = nullptr;               // fp32 [B*H*W][out_ld]
   int out_ld = 0;
 };
@@ -298,6 +312,8 @@ class UNet : public Net {
   virtual void build_attn_control(Ctx&, const float*, const float*, const float*, int, AttnCtrl&) {
     CD_CHECK(false, "cross-attention control: the network has no text cross-attention");
   }
+  // text cross-attention blocks whose token grid side lies in [min_side, max_side] (0, 0 = all); 0 without a text context
+  virtual int count_text_blocks(int, int) const { return 0; }
   int in_cpad = 32;
   int out_channels = 0;
   int image_size = 0;

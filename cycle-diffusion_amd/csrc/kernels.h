@@ -155,6 +155,30 @@ void launch_automask_qsample(hipStream_t st, const AutoMaskNoised& a);
 void launch_automask_accum(hipStream_t st, const AutoMaskArgs& a);
 void launch_automask_finish(hipStream_t st, const AutoMaskArgs& a);  // the per-image sum, then threshold / dilation / output
 
+// ---------------------------------------------------------------- per-word attention maps (automask.hip)
+// One included layer of a forward into that forward's per-row sums: acc[r][n][y][x] (+)= layer[r][n][(y / f) * s + x / f],
+// f = h / s. A row is (draw i, sample b) = i * B + b, so a draw's layers add up in the forward's order whichever forward
+// the draw runs in.
+struct WordMapAccum {
+  const float* layer = nullptr;  // [rows][N][s * s]
+  float* acc = nullptr;          // [rows][N][h][w]
+  int rows = 0, N = 0, s = 0, h = 0, w = 0;
+  int first = 0;                 // 1: acc starts from 0, else from what lies there
+};
+void launch_word_map_accumulate(hipStream_t st, const WordMapAccum& a);
+// The draws of one forward into the call's sums, ascending: total[b][e] (+)= acc[0 * B + b][e] + ... ; with `out`,
+// out = total * scale afterwards (the last forward of a call).
+struct WordMapFold {
+  const float* acc = nullptr;  // [n_chunk * B][per]
+  float* total = nullptr;      // [B][per]
+  float* out = nullptr;        // [B][per] or null
+  int n_chunk = 0, B = 0;
+  int64_t per = 0;             // N * h * w
+  int first = 0;               // 1: total starts from 0
+  float scale = 1.f;
+};
+void launch_word_map_fold(hipStream_t st, const WordMapFold& a);
+
 // ---------------------------------------------------------------- implicit-GEMM conv / GEMM (conv_gemm.hip)
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_GEGLU = 3, ACT_QGELU = 4, ACT_RELU = 5 };  // QGELU: x*sigmoid(1.702x) (CLIP)
 // RELU: max(x, 0) (the BasicConv2d units of the FID Inception-v3, inception.hip)
@@ -398,6 +422,22 @@ void launch_cross_attention_ctrl(hipStream_t st, const CtrlAttnParams& p);
 // s = r % B_ctrl; fp32 accumulation, one rounding. v / va / vb [rows][L][C] dense; M [B_ctrl][L][L], alpha / w [B_ctrl][L] fp32
 void launch_ctrl_values(hipStream_t st, const bf16_t* v, const float* M, const float* alpha, const float* w, int rows,
                         int B_ctrl, int L, int C, bf16_t* va, bf16_t* vb);
+// Per-word cross-attention maps: the score and softmax half of the control kernel, reduced in the same pass to
+//   maps[r][n][q] = (1/H) * sum_hd ( sum_j sel[r % B_sel][n][j] * P_hd[q][j] ),   P = softmax over the L keys, hd ascending
+// No probability is stored; fp32 from the scores on.
+constexpr int kMapWords = 8;  // selector rows (words) of one launch
+struct WordMapParams {
+  const bf16_t* q = nullptr;   // [B][Tq][ldq], head h at column h*D
+  const bf16_t* k = nullptr;   // [B][L][ldk]
+  const float* sel = nullptr;  // [B_sel][N][L] weights over the key positions
+  float* maps = nullptr;       // [B][N][Tq]
+  int B = 0, B_sel = 0, H = 0, Tq = 0, L = 0, D = 0, N = 0;
+  int ldq = 0, ldk = 0;
+  int64_t q_bs = 0, k_bs = 0;
+  float scale = 1.0f;  // softmax scale; ignored when q_log2 is set
+  int q_log2 = 0;
+};
+void launch_cross_attention_maps(hipStream_t st, const WordMapParams& p);
 // V [B][Tk][ldv] (head h at column h*D) -> Vt [B][H][Dpad][Tpad], zero padded
 void launch_transpose_v(hipStream_t st, const bf16_t* v, int ldv, int64_t v_bs, bf16_t* vt, int B,
                         int H, int Tk, int D, int Dpad, int Tpad);

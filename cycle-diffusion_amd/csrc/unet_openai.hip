@@ -39,6 +39,7 @@ struct STW {  // SpatialTransformer with one BasicTransformerBlock
   // d_head = 40: the block's entry (norm -> proj_in -> norm1 -> q | k -> V^T) with its derived q | k | v weights, rebuilt
   // with the LayerNorm folds (engine.h st_entry_fwd)
   StEntryW entry;
+  int side = 0;  // token grid side of the block
   // context cache (step invariant)
   bf16_t* k2c = nullptr;  // [B*L][C]
   bf16_t* v2c = nullptr;  // [B*L][C] (token-major: k_attention transposes V tiles with LDS transpose reads)
@@ -66,6 +67,7 @@ class UNetOpenAI : public UNet {
   void set_context(Ctx& c, const bf16_t* ctx, int B, int L) override;
   void build_attn_control(Ctx& c, const float* mapper, const float* alpha, const float* weight, int B_ctrl,
                           AttnCtrl& ctrl) override;
+  int count_text_blocks(int min_side, int max_side) const override;
   size_t workspace_hint(int B) const override;
 
  private:
@@ -81,6 +83,7 @@ class UNetOpenAI : public UNet {
   int ctx_B_ = 0, ctx_L_ = 0;
   std::vector<void*> ctx_allocs_;
   const AttnCtrl* ctrl_ = nullptr;  // the control of the running forward (UNetIO::ctrl), else null
+  const WordMapCollect* maps_ = nullptr;  // the map collection of the running forward (UNetIO::maps), else null
 
   int add_res(const std::string& pfx, int cin, int cout, bool up, bool down);
   int add_st(const std::string& pfx, int C, int heads, int dh);
@@ -220,6 +223,7 @@ UNetOpenAI::UNetOpenAI(const cd_net_desc& d) {
     if (d.num_head_channels == -1) { heads = d.num_heads; dh = ch / heads; }
     else { heads = ch / d.num_head_channels; dh = d.num_head_channels; }
   };
+  int ds = 1;  // downsampling factor of the level under construction
   std::vector<std::string> res_pfx;
   auto add_res_named = [&](const std::string& pfx, int cin, int cout, bool up, bool down) {
     res_pfx.push_back(pfx);
@@ -228,7 +232,7 @@ UNetOpenAI::UNetOpenAI(const cd_net_desc& d) {
   auto add_attn = [&](Block& blk, const std::string& pfx, int ch) {
     int heads, dh; heads_for(ch, heads, dh);
     Layer l;
-    if (use_st) { l.kind = Layer::ST; l.idx = add_st(pfx, ch, heads, dh); }
+    if (use_st) { l.kind = Layer::ST; l.idx = add_st(pfx, ch, heads, dh); st_[l.idx].side = d.image_size / ds; }
     else { l.kind = Layer::AB; l.idx = add_ab(pfx, ch, heads); }
     blk.layers.push_back(l);
   };
@@ -240,7 +244,7 @@ UNetOpenAI::UNetOpenAI(const cd_net_desc& d) {
     b.layers.push_back(l); in_blocks_.push_back(b);
   }
   std::vector<int> chans{mc_};
-  int ch = mc_, ds = 1, bi = 1;
+  int ch = mc_, bi = 1;
   for (int level = 0; level < d.n_mult; ++level) {
     const int mult = d.channel_mult[level];
     for (int r = 0; r < d.num_res_blocks; ++r) {
@@ -416,6 +420,13 @@ void UNetOpenAI::build_attn_control(Ctx& c, const float* mapper, const float* al
                        va, vb);
     ctrl.va.push_back(va); ctrl.vb.push_back(vb);
   }
+}
+
+int UNetOpenAI::count_text_blocks(int min_side, int max_side) const {
+  WordMapCollect w; w.min_side = min_side; w.max_side = max_side;
+  int n = 0;
+  for (const STW& s : st_) n += w.takes(s.side) ? 1 : 0;
+  return n;
 }
 
 // rows [0, n) of src -> rows [0, n) of dst, and its last `tail` rows again -> rows [n, n + tail) (dense, `cols` 16-bit
@@ -594,6 +605,21 @@ void UNetOpenAI::st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x, Act& o
       p.scale = scale; p.q_log2 = 1;
       launch_cross_attention_ctrl(c.st, p);
     }
+    if (maps_ && maps_->takes(x.H)) {  // the same q and keys once more, reduced to the mass on the chosen words
+      CD_CHECK(x.H == x.W && x.H == s.side && B == maps_->n_chunk * maps_->B, "word maps: block of side %d, %d rows", x.H, B);
+      WordMapParams mp;
+      mp.q = q.p; mp.k = s.k2c; mp.sel = maps_->sel;
+      mp.maps = (float*)c.arena->alloc((size_t)B * maps_->N * T * 4);
+      mp.B = B; mp.B_sel = maps_->B_sel; mp.H = s.heads; mp.Tq = T; mp.L = ctx_L_; mp.D = s.dh; mp.N = maps_->N;
+      mp.ldq = q.ld; mp.ldk = C; mp.q_bs = (int64_t)T * q.ld; mp.k_bs = (int64_t)ctx_L_ * C;
+      mp.scale = scale; mp.q_log2 = 1;
+      launch_cross_attention_maps(c.st, mp);
+      WordMapAccum ma;
+      ma.layer = mp.maps; ma.acc = maps_->acc; ma.rows = B; ma.N = maps_->N; ma.s = x.H; ma.h = image_size; ma.w = image_size;
+      ma.first = maps_->layers == 0 ? 1 : 0;
+      launch_word_map_accumulate(c.st, ma);
+      ++maps_->layers;
+    }
     ConvOpts o; o.pad = 0; o.resid = &h; o.out = h.p; o.out_ld = h.ld;  // in-place residual update
     conv_fwd(c, *s.o2, a, nullptr, o);
     c.arena->release(m2);
@@ -695,7 +721,13 @@ void UNetOpenAI::forward(Ctx& c, const UNetIO& io) {
   c.f32 = f32; c.x3 = x3;
   refresh_ln_folds(c);
   CD_CHECK(!io.ctrl || (!f32 && io.ctrl->va.size() == st_.size()), "U-Net: cross-attention control on a network it was not built for");
+  CD_CHECK(!io.maps || !f32, "U-Net: per-word attention maps are not built for fp32 / fp32x3 networks (their transformer blocks "
+           "run the fp32 attention of st_f32.hip): use the 16-bit precision");
+  CD_CHECK(!(io.maps && io.ctrl), "U-Net: a forward collects per-word attention maps or runs cross-attention control, not both");
+  CD_CHECK(!io.maps || (io.dup_tail == 0 && !io.cfg_dup), "U-Net: per-word attention maps on a batch with repeated rows");
   ctrl_ = io.ctrl;
+  maps_ = io.maps;
+  if (maps_) maps_->layers = 0;
   const int B = io.B, R = image_size;
   // ---- time embedding: sinusoid -> Linear -> SiLU -> Linear, then every ResBlock's
   //      emb_layers (SiLU -> Linear) in one launch (openaimodel.py:506-511,723-724,263)
@@ -760,6 +792,7 @@ void UNetOpenAI::forward(Ctx& c, const UNetIO& io) {
   c.arena->release(mk0);
   c.f32 = false; c.x3 = false;
   ctrl_ = nullptr;
+  maps_ = nullptr;
 }
 
 }  // namespace

@@ -648,6 +648,48 @@ class Engine:
         self._keep = (x0, cs, ct, noise)  # the launches read them asynchronously
         return keep, mp
 
+    def word_maps(self, net, x0, ctx, sel, t, qa, qb, n_draws=4, noise=None, seed=0, max_rows=None, sides=(0, 0)):
+        """cd_word_maps: per-word heat maps of the text cross-attention. x0 [B, C, h, w] noised n_draws times to the level
+        (t, qa, qb), one conditional forward under ctx [B, L, Dc]; in every transformer block whose token grid side lies in
+        sides = (min, max) ((0, 0): all) the softmax mass on the key positions sel [B_sel, N, L] marks, averaged over heads,
+        blocks and draws -> (maps [B, N, h, w], number of blocks included). noise [n_draws, B, C, h, w] or None (Philox(seed),
+        stream 0x8000 + i); max_rows: rows of one forward (default: all n_draws * B)."""
+        x0 = self._f32(x0)
+        B, Cc, H, W = x0.shape
+        cx, sel = self._f32(ctx), self._f32(sel)
+        if cx.dim() != 3 or cx.shape[0] != B:
+            raise ValueError("the context must be [%d, L, Dc], got %s" % (B, tuple(cx.shape)))
+        if sel.dim() != 3 or sel.shape[2] != cx.shape[1]:
+            raise ValueError("the selector must be [B_sel, N, %d], got %s" % (cx.shape[1], tuple(sel.shape)))
+        if noise is not None:
+            noise = self._f32(noise)
+            if tuple(noise.shape) != (int(n_draws), B, Cc, H, W):
+                raise ValueError("noise must be %s, got %s" % ((int(n_draws), B, Cc, H, W), tuple(noise.shape)))
+        N = sel.shape[1]
+        maps = torch.empty((B, N, H, W), device=x0.device, dtype=torch.float32)
+        max_rows = int(n_draws) * B if max_rows is None else int(max_rows)
+        n_layers = C.c_int(0)
+        check(self.lib.cd_word_maps(self.h, net, ptr(x0), ptr(cx), cx.shape[1], B, ptr(sel), sel.shape[0], N, int(n_draws),
+                                    int(t), C.c_float(qa), C.c_float(qb), ptr(noise), C.c_uint64(seed), max_rows,
+                                    int(sides[0]), int(sides[1]), ptr(maps), C.byref(n_layers)))
+        self._keep = (x0, cx, sel, noise)  # the launches read them asynchronously
+        return maps, n_layers.value
+
+    def cross_attention_maps(self, q, k, sel, H, L=None, scale=None, q_log2=False):
+        """cd_op_cross_attention_maps: one launch of the map kernel. q [B, Tq, H*D], k [B, L_buf, H*D] (the first L rows are the
+        keys), sel [B_sel, N, L] -> maps [B, N, Tq] = head mean of sum_j sel[b % B_sel, n, j] softmax(q k^T scale)[q, j]."""
+        q, k, sel = self._f32(q), self._f32(k), self._f32(sel)
+        B, Tq, Cq = q.shape
+        D = Cq // H
+        L = k.shape[1] if L is None else int(L)
+        if sel.dim() != 3 or sel.shape[2] != L or k.shape[0] != B or k.shape[2] != Cq:
+            raise ValueError("q %s, k %s, sel %s with L = %d" % (tuple(q.shape), tuple(k.shape), tuple(sel.shape), L))
+        scale = D ** -0.5 if scale is None else float(scale)
+        maps = torch.empty((B, sel.shape[1], Tq), device=q.device, dtype=torch.float32)
+        check(self.lib.cd_op_cross_attention_maps(self.h, ptr(q), ptr(k), ptr(sel), B, sel.shape[0], H, Tq, L, k.shape[1], D,
+                                                  sel.shape[1], C.c_float(scale), int(bool(q_log2)), ptr(maps)))
+        return maps
+
     def op_automask_reduce(self, eps_src, eps_tgt, ratio=3.0, thr=0.5, dilate=0):
         """cd_op_automask_reduce: the reduction of automask() on fp32 [n, B, C, H, W] predictions -> (keep, map [B, 1, H, W],
         mean [B])"""

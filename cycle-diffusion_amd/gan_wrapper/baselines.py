@@ -42,6 +42,10 @@ class _LatentBaseline(_NoCoupledLoop):
     share their rows and batch structure fold into one cd_ddim_decode(_v) call, as the CycleDiffusion wrapper folds its
     ensemble; then the first stage and the post-process (x + 1) / 2."""
 
+    @property
+    def word_maps(self):  # the per-word attention maps belong to the CycleDiffusion text wrappers, like translate
+        raise AttributeError("word_maps")
+
     def forward(self, z_ensemble, original_img, encode_text, decode_text, mask=None):
         if mask is not None:
             raise ValueError("%s takes no keep-mask: the region-keeping decode is CycleDiffusion's (SDStochasticText / "

@@ -364,6 +364,42 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         self.last_auto_mask, self.last_auto_map = torch.cat(keeps, 0), torch.cat(maps, 0)
         return self.last_auto_mask, self.last_auto_map
 
+    # ---- per-word cross-attention heat maps
+    def word_maps(self, x0, text, words=None, other_text=None, strength=0.5, draws=4, seed=0, sides=None):
+        """maps [B, N, h, w] of the latent x0 [B, C, h, w] under the prompts `text`: the softmax mass the text cross-attentions
+        put on chosen words, averaged over heads, transformer blocks and `draws` noised copies of x0 at the level
+        auto_mask.level_index(strength, S) of this wrapper's own schedule. `words`: N strings, each tokenised by the text
+        encoder's tokenizer and marked wherever it occurs in a sample's prompt; or `other_text`: the one map (N = 1) of the
+        tokens `text` introduces against `other_text` (attn_control.edited_selector). sides = (min, max) keeps the blocks
+        whose token grid side lies in that window (None: all). The draws come from the counter-based generator (seed)."""
+        if (words is None) == (other_text is None):
+            raise ValueError("word_maps takes either words= or other_text=")
+        bsz = x0.shape[0]
+        c, _ = self.get_condition(text, bsz)
+        ids, eos = self._control_ids(text)
+        if other_text is not None:
+            oids, _ = self._control_ids(other_text)
+            sel = [attn_control.edited_selector(oids[b], ids[b], eos) for b in range(bsz)]
+        else:
+            wids, _ = self._control_ids(list(words))
+            toks = [list(r[1:attn_control.prompt_length(r, eos)]) for r in wids]
+            sel = [attn_control.word_selector(ids[b], toks, eos) for b in range(bsz)]
+        sel = torch.from_numpy(np.stack(sel, 0)).to(self.device)
+        sch = self._schedule()
+        k = am.level_index(strength, len(sch))
+        qa, qb = sch.coef_qsample(0)[k]
+        t = int(sch.coef_decode(0)["t"][k])
+        # rows of one forward as the other calls bound them: MAX_FOLD samples, COUPLE_MAX_TOKENS tokens
+        max_rows = max(1, min(self.MAX_FOLD, self.couple_max_tokens // self.image_size ** 2))
+        x0 = x0.to(self.device, torch.float32)
+        out = []
+        for i in range(0, bsz, max_rows):  # a sample's draw index is its place in its call
+            m, _ = self.engine.word_maps(self.unet, x0[i:i + max_rows].contiguous(), c[i:i + max_rows].contiguous(),
+                                         sel[i:i + max_rows].contiguous(), t, float(qa), float(qb), n_draws=int(draws),
+                                         seed=int(seed), max_rows=max_rows, sides=sides or (0, 0))
+            out.append(m)
+        return torch.cat(out, 0)
+
     def _mask_draws(self, K, bsz, n_eps=None):
         """the K q_sample draws of ONE sample_with_eps(mask=) call in its own order (randn_like(x0) at the top of every step,
         ddim.py:429), and - interleaved as the reference draws them - the fresh noise of the steps past the white-box prefix

@@ -321,6 +321,27 @@ int cd_automask(cd_handle h, int net, const float* x0, const float* ctx_src, con
                 int n_draws, int t, float qa, float qb, const float* noise, uint64_t seed, int max_rows, float ratio, float thr,
                 int dilate, float* map_out, float* keep_out);
 
+/* Per-word cross-attention heat maps (DAAM, Tang et al. 2022; the maps prompt-to-prompt's local blend thresholds; no counterpart
+ * in the reference tree): how much softmax mass do the text cross-attentions put on chosen words, per pixel?
+ *     x_i = qa*x0 + qb*n_i (fp32, in that order), i < n_draws; rows [draw i, sample b] through ONE conditional forward per
+ *     chunk at timestep t - no unconditional rows. In every transformer block whose token grid side s has
+ *     min_side <= s <= max_side (0, 0: every block), for the block's text cross-attention (attn2), row r, query q:
+ *         P = softmax(Q K^T * scale) over the L keys
+ *         m_layer[r, n, q] = (1/H) * sum_hd sum_j sel[b % B_sel, n, j] * P_hd[q, j]                (hd ascending)
+ *     maps_out[b, n, y, x] = (1 / (n_draws * n_layers)) * sum_i sum_layer m_layer[i*B + b, n, (y / f)*s + (x / f)],  f = h / s
+ *     (nearest replication onto the latent grid; fp32 throughout; per draw the layers are added in the forward's order, then the
+ *     draws in ascending order). n_layers_out (or NULL): the number of blocks included.
+ *   x0 [B,C,h,w]; ctx [B,L,Dc]; sel [B_sel,N,L] fp32 weights over the key positions, N words, sample b uses entry b % B_sel;
+ *   (t, qa, qb): the level, as cd_automask takes it; noise [n_draws,B,C,h,w] or NULL -> Philox(seed), stream 0x8000 + i, element
+ *   = the flat index in [B,C,h,w] (the band at 0x7000 holds the VAE posterior's 0x7a65). max_rows: the most rows a forward may
+ *   have; max(1, max_rows / B) draws run per forward, and the result does not depend on that cut, bit for bit. The collection
+ *   changes no bit of the network's own output, and a forward without it runs the launches it always ran.
+ * Refused (error text, nothing launched): networks without a text context, fp32 / fp32x3 precision, ctx_len > 96, N outside
+ * [1, 8], n_draws outside [1, 4095], B % B_sel != 0, max_rows < B, min_side > max_side, a side window that matches no block. */
+int cd_word_maps(cd_handle h, int net, const float* x0, const float* ctx, int ctx_len, int B, const float* sel, int B_sel,
+                 int N, int n_draws, int t, float qa, float qb, const float* noise, uint64_t seed, int max_rows,
+                 int min_side, int max_side, float* maps_out /* [B,N,h,w] */, int* n_layers_out);
+
 /* Stochastic refinement (ddpm_ddim_wrapper.py:431-453): x_t = sa*x + s1a*n (row R of coef_host),
  * then R random-noise steps rows R-1..0. noise [R+1,B,C,H,W] or NULL. In/out x [B,C,H,W]. */
 int cd_pix_refine(cd_handle h, int net, int sched_kind, float* x, int B, int R,
@@ -433,6 +454,11 @@ int cd_op_cross_attention_ctrl_ex(cd_handle h, const float* q_own, const float* 
                                   const float* v_own, const float* mapper, const float* alpha, const float* weight, int B,
                                   int B_src, int B_ctrl, int H, int Tq, int L, int L_buf, int D, float scale, int q_log2,
                                   int opad, float* o);
+/* one launch of the per-word map kernel (k_cross_attention_maps) on caller tensors, fp32 device: q [B,Tq,H*D], k [B,L_buf,H*D]
+   (rows L..L_buf-1 of each sample are never used), sel [B_sel,N,L] -> maps [B,N,Tq] = (1/H) sum_hd sum_j sel[b % B_sel,n,j]
+   P_hd[q,j]. q_log2: q already carries scale * log2 e (scale is then ignored). L <= 96, N <= 8, D in {32, 40, 64, 80, 160}. */
+int cd_op_cross_attention_maps(cd_handle h, const float* q, const float* k, const float* sel, int B, int B_sel, int H,
+                               int Tq, int L, int L_buf, int D, int N, float scale, int q_log2, float* maps /* [B,N,Tq] */);
 /* launch_attention in the operand forms the networks use. q [B,Tq,H*D], k, v [B,Tk,H*D] fp32 as cd_op_attention takes them,
  * staged as 16-bit tensors by `layout`: 0 = three tensors, each padded: row strides H*D + pad (q), H*D + 2 pad (k),
  * H*D + 3 pad (v), so that no two are equal; 1 = q | k as column blocks of one

@@ -89,6 +89,22 @@ def folded_calls(model, batches, fold, seed, device):
         yield batch, orig, img
 
 
+def word_map_images(wrapper, orig, text, other_text, seed):
+    """--word_maps: uint8 [B, R, R] heat maps of the words `text` introduces against `other_text`, taken on the source images
+    `orig` (in [0, 1]) encoded with the posterior mean, as forward(mask=) encodes them; every image divided by its own
+    maximum and nearest-upsampled to the image size"""
+    img = ((orig - 0.5) * 2.0).to(wrapper.device, torch.float32)
+    per = wrapper._vae_batch()
+    with torch.no_grad():
+        x0 = torch.cat([wrapper.engine.vae_encode(wrapper.vae, img[i:i + per], sample=False, scale=wrapper.SCALE_FACTOR)
+                        for i in range(0, img.shape[0], per)], 0)
+        m = wrapper.word_maps(x0, list(text), other_text=list(other_text), seed=seed)[:, 0]
+    m = m / m.amax(dim=(1, 2), keepdim=True).clamp_min(torch.finfo(torch.float32).tiny)
+    f = wrapper.vae_factor
+    m = m.repeat_interleave(f, 1).repeat_interleave(f, 2)
+    return (m * 255 + 0.5).clamp(0, 255).to(torch.uint8).cpu()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg", required=True)
@@ -121,6 +137,9 @@ def main(argv=None):
     ap.add_argument("--text_metrics", action="store_true",
                     help="text tasks: per-sample CLIP and directional CLIP (evaluation/translate_text.py) on the unclamped "
                          "outputs; ViT-B/32 weights from CYCLEDIFF_CLIP_RANKER")
+    ap.add_argument("--word_maps", action="store_true",
+                    help="text tasks: also write every sample's cross-attention heat map of the words its target prompt "
+                         "introduces (against the source prompt), on the source image, as word_maps/<id>.png")
     a = ap.parse_args(argv)
     if a.synthetic_weights:
         os.environ["CYCLEDIFF_SYNTHETIC_WEIGHTS"] = "1"
@@ -180,6 +199,10 @@ def main(argv=None):
             grid_pairs.append((orig.detach().clamp(0, 1).cpu(), img.detach().clamp(0, 1).cpu()))
         keep = [j for j in range(img.shape[0]) if not batch["is_padding"][j]]
         feats = fid.features(engine, fid_net, img[keep]) if fid_net is not None and keep else None
+        heat = None
+        if a.word_maps and "encode_text" in batch and hasattr(wrapper, "word_maps"):
+            heat = word_map_images(wrapper, orig, batch["decode_text"], batch["encode_text"], a.seed)
+            os.makedirs(os.path.join(a.output_dir, "word_maps"), exist_ok=True)
         scores = None
         if ranker is not None and "encode_text" in batch:
             scores = text_metrics.text_scores(ranker, img, orig, batch["encode_text"], batch["decode_text"])
@@ -215,6 +238,8 @@ def main(argv=None):
                 row["_inception"] = feats[keep.index(j)]  # travels with the row to rank 0, dropped before writing
             rows.append(row)
             from PIL import Image
+            if heat is not None:
+                Image.fromarray(heat[j].numpy()).save(os.path.join(a.output_dir, "word_maps", "%06d.png" % sid))
             Image.fromarray((g.permute(1, 2, 0).numpy() * 255 + 0.5).astype("uint8")).save(
                 os.path.join(a.output_dir, "%06d.png" % sid))
     torch.cuda.synchronize(dev)
