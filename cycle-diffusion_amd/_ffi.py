@@ -125,6 +125,10 @@ SIGNATURES = {
     "cd_op_vq_quantize": [_VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _I],
     "cd_op_gemm_batched": [_VP, _VP, _I, _I64, _VP, _I, _I64, _I, _I, _I, _I, _F, _VP, _VP, _I, _VP, _I, _I, _VP, _I, _I64, _I],
     "cd_op_attn_block_core": [_VP, _VP, _I, _VP, _I, _VP, _VP, _I, _I, _I, _VP, _I, _VP, C.POINTER(_I)],
+    "cd_op_pool3x3": [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP],
+    "cd_op_global_avg": [_VP, _VP, _I, _I, _I, _I, _VP],
+    "cd_op_basic_conv": [_VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP,
+                         _VP],
     "cd_op_bench_conv": [_VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float)],
     "cd_op_bench_mfma_sustained": [_VP, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)],
     "cd_op_probe": [_VP, _I, _VP, _VP, _SZ],

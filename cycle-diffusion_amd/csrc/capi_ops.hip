@@ -87,12 +87,13 @@ Act op_upload_nhwc(cd_engine* h, const float* x, int B, int C, int Czero, int ld
   launch_nchw_to_nhwc_f32(h->st, op_nchw_guarded(h, x, B, C, Czero, ld, HW), a.pf(), B, ld, HW, ld, 1.f, 0.f);
   return a;
 }
-// fp32 NCHW -> 16-bit NHWC with row stride ld: channels [C, ld) NaN
-Act op_upload_nhwc16(cd_engine* h, const float* x, int B, int C, int ld, int H, int W) {
+// fp32 NCHW -> 16-bit NHWC with row stride ld: channels [C, ld) NaN; with Czero > C, [C, Czero) hold 0 and [Czero, ld) NaN
+Act op_upload_nhwc16(cd_engine* h, const float* x, int B, int C, int ld, int H, int W, int Czero = 0) {
   const int HW = H * W;
+  if (Czero < C) Czero = C;
   Act a; a.B = B; a.H = H; a.W = W; a.C = C; a.ld = ld;
   a.p = (bf16_t*)h->arena.alloc((size_t)B * HW * ld * sizeof(bf16_t));
-  launch_nchw_to_nhwc(h->st, op_nchw_guarded(h, x, B, C, C, ld, HW), a.p, B, ld, HW, ld, 1.f, 0.f, 0);
+  launch_nchw_to_nhwc(h->st, op_nchw_guarded(h, x, B, C, Czero, ld, HW), a.p, B, ld, HW, ld, 1.f, 0.f, 0);
   return a;
 }
 // the split form straight from NCHW (k_nchw_to_nhwc_split, as the U-Net input is uploaded): [pixel][hi(Cpad) | lo(Cpad)]
@@ -1085,6 +1086,69 @@ int cd_op_attn_block_core(cd_handle h, const void* qk, int ldqk, const void* n, 
   if (vt_out) HIP_CHECK(hipMemcpyAsync(vt_out, r.vt, (size_t)B * C * r.Tpad * 2, hipMemcpyDeviceToDevice, h->st));
   if (branch) *branch = r.branch;
   op_bare_done(h);
+  CD_API_END
+}
+
+// ---- the FID Inception-v3's own kernels and launch forms (inception.hip), through the launchers the network calls
+int cd_op_pool3x3(cd_handle h, const float* x, int B, int C, int H, int W, int in_pad, int max, int stride, int pad,
+                  int out_off, int out_ld, float* y) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && y && B > 0 && C > 0 && H > 0 && W > 0 && stride > 0 && pad >= 0 && in_pad >= 0 && out_off >= 0, "bad argument");
+  CD_CHECK(C % 8 == 0 && in_pad % 8 == 0 && out_off % 8 == 0 && out_ld % 8 == 0, "C, in_pad, out_off, out_ld: multiples of 8 elements");
+  CD_CHECK(out_off + C <= out_ld, "the slice [%d, %d) does not fit a row of %d", out_off, out_off + C, out_ld);
+  CD_CHECK(H + 2 * pad >= 3 && W + 2 * pad >= 3, "bad argument (image smaller than the window)");
+  ArenaScope arena_scope(h->arena);
+  const Act a = op_upload_nhwc16(h, x, B, C, C + in_pad, H, W);
+  const int Ho = (H + 2 * pad - 3) / stride + 1, Wo = (W + 2 * pad - 3) / stride + 1;
+  const int64_t rows = (int64_t)B * Ho * Wo;
+  bf16_t* ob = op_nan_rows16(h, rows, out_ld);
+  launch_pool3x3(h->st, a.p, a.ld, B, H, W, C, max != 0, stride, pad, ob + out_off, out_ld);
+  op_download_nchw(h, ob, false, out_ld, y, (int)rows + 64, out_ld, 1);
+  CD_API_END
+}
+
+int cd_op_global_avg(cd_handle h, const float* x, int B, int HW, int C, int in_pad, float* y) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && y && B > 0 && HW > 0 && C > 0 && in_pad >= 0, "bad argument");
+  CD_CHECK(C % 8 == 0 && in_pad % 8 == 0, "C, in_pad: multiples of 8 elements");
+  ArenaScope arena_scope(h->arena);
+  const Act a = op_upload_nhwc16(h, x, B, C, C + in_pad, HW, 1);
+  launch_global_avg(h->st, a.p, a.ld, B, HW, C, y);
+  CD_API_END
+}
+
+int cd_op_basic_conv(cd_handle h, const float* x, int B, int Cin, int H, int W, int in_ld, const float* w, const float* gamma,
+                     const float* beta, const float* mean, const float* var, int N, int KH, int KW, int stride, int pad_t,
+                     int pad_l, int out_off, int out_ld, int tile, float* y, float* w_packed, float* bias_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && w && gamma && beta && mean && var && y, "bad argument");
+  CD_CHECK(B > 0 && Cin > 0 && H > 0 && W > 0 && N > 0 && KH > 0 && KW > 0 && stride > 0 && pad_t >= 0 && pad_l >= 0 &&
+               out_off >= 0, "bad argument");
+  CD_CHECK(H + 2 * pad_t >= KH && W + 2 * pad_l >= KW, "bad argument (image smaller than the filter)");
+  const int Cpad = round_up(Cin, 32), Nrun = round_up(N, 32);
+  CD_CHECK(in_ld % 8 == 0 && in_ld >= Cpad, "in_ld: a multiple of 8 elements, at least round_up(Cin, 32) = %d", Cpad);
+  CD_CHECK(out_off % 8 == 0 && out_ld % 8 == 0, "out_off, out_ld: multiples of 8 elements");
+  CD_CHECK(out_off + Nrun <= out_ld, "the slice [%d, %d) does not fit a row of %d", out_off, out_off + Nrun, out_ld);
+  ConvW* cw = h->op_params.new_conv(N, Cin, KH, KW, true);  // as InceptionFID::unit: zeroed [Npad][KH][KW][Cpad] and bias [Npad]
+  CD_CHECK(cw->Cpad == Cpad, "basic_conv: channel padding");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  launch_fold_bn(h->st, w, gamma, beta, mean, var, N, Cin, KH, KW, Cpad, cw->w, cw->b);
+  const Act a = op_upload_nhwc16(h, x, B, Cin, in_ld, H, W, Cpad);
+  const int Ho = (H + 2 * pad_t - KH) / stride + 1, Wo = (W + 2 * pad_l - KW) / stride + 1;
+  const int64_t rows = (int64_t)B * Ho * Wo;
+  bf16_t* ob = op_nan_rows16(h, rows, out_ld);
+  ConvGemmParams p = basic_conv_params(a.p, a.ld, B, H, W, Cpad, cw->w, cw->b, N, KH, KW, stride, pad_t, pad_l, ob + out_off,
+                                       out_ld, c.zeros);
+  CD_CHECK(p.M == rows && p.N == Nrun, "basic_conv: geometry");
+  p.tile = tile;
+  launch_conv_gemm(h->st, p);
+  op_download_nchw(h, ob, false, out_ld, y, (int)rows + 64, out_ld, 1);
+  if (w_packed) op_download_nchw(h, cw->w, false, cw->Ktot(), w_packed, cw->Npad, cw->Ktot(), 1);
+  if (bias_out) HIP_CHECK(hipMemcpyAsync(bias_out, cw->b, (size_t)cw->Npad * sizeof(float), hipMemcpyDeviceToDevice, h->st));
   CD_API_END
 }
 

@@ -110,6 +110,50 @@ __global__ void k_fold_bn(const float* __restrict__ raw, const float* __restrict
   }
 }
 
+}  // namespace
+
+void launch_pool3x3(hipStream_t st, const bf16_t* x, int ldx, int B, int H, int W, int C, bool max, int stride, int pad,
+                    bf16_t* y, int ldy) {
+  CD_CHECK(C % 8 == 0 && ldx % 8 == 0 && ldy % 8 == 0, "inception_fid: pool channels");
+  const int Ho = (H + 2 * pad - 3) / stride + 1, Wo = (W + 2 * pad - 3) / stride + 1;
+  const int64_t n = (int64_t)B * Ho * Wo * (C / 8);
+  if (max)
+    hipLaunchKernelGGL(k_pool3x3<true>, dim3(grid_for(n)), dim3(256), 0, st, x, ldx, B, H, W, C, stride, pad, y, ldy, Ho, Wo);
+  else
+    hipLaunchKernelGGL(k_pool3x3<false>, dim3(grid_for(n)), dim3(256), 0, st, x, ldx, B, H, W, C, stride, pad, y, ldy, Ho, Wo);
+}
+
+void launch_global_avg(hipStream_t st, const bf16_t* x, int ldx, int B, int HW, int C, float* y) {
+  CD_CHECK(C % 8 == 0 && ldx % 8 == 0, "inception_fid: global average pool channels");
+  const int n = B * (C / 8);
+  hipLaunchKernelGGL(k_global_avg, dim3((n + 255) / 256), dim3(256), 0, st, x, ldx, B, HW, C, y);
+}
+
+void launch_fold_bn(hipStream_t st, const float* raw, const float* gamma, const float* beta, const float* mean, const float* var,
+                    int N, int Cin, int KH, int KW, int Cpad, bf16_t* w, float* bias) {
+  const int64_t n = (int64_t)N * KH * KW * Cpad;
+  hipLaunchKernelGGL(k_fold_bn, dim3(grid_for(n)), dim3(256), 0, st, raw, gamma, beta, mean, var, kBnEps, N, Cin, KH, KW, Cpad,
+                     w, bias);
+}
+
+ConvGemmParams basic_conv_params(const bf16_t* x, int ldx, int B, int H, int W, int Cpad, const bf16_t* wgt, const float* bias,
+                                 int N, int KH, int KW, int stride, int pad_t, int pad_l, void* out, int out_ld,
+                                 const bf16_t* zeros) {
+  ConvGemmParams p;
+  p.src0 = x; p.C0 = Cpad; p.ld0 = ldx;
+  p.B = B; p.Hs = H; p.Ws = W; p.Hin = H; p.Win = W;
+  p.KH = KH; p.KW = KW; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
+  p.Hout = (H + 2 * pad_t - KH) / stride + 1;
+  p.Wout = (W + 2 * pad_l - KW) / stride + 1;
+  p.M = B * p.Hout * p.Wout;
+  p.wgt = wgt; p.Ktot = KH * KW * Cpad; p.N = round_up(N, 32);
+  p.bias = bias; p.act = ACT_RELU;
+  p.out = out; p.out_ld = out_ld; p.zeros = zeros;
+  return p;
+}
+
+namespace {
+
 // one BasicConv2d
 struct Unit {
   ConvW* w = nullptr;
@@ -248,8 +292,7 @@ class InceptionFID : public Net {
       if (emit(h)) return done(c, mk);
     }
     CD_CHECK(h.C == 2048 && h.H == 8 && h.W == 8 && (h.ld % 8) == 0, "inception_fid: pool3 input shape");
-    const int n = B * (2048 / 8);
-    hipLaunchKernelGGL(k_global_avg, dim3((n + 255) / 256), dim3(256), 0, c.st, h.p, h.ld, B, 64, 2048, out);
+    launch_global_avg(c.st, h.p, h.ld, B, 64, 2048, out);
     done(c, mk);
   }
   // stem convs and pools (7), Mixed_5b..5d (3), 6a, 6b..6e (4), 7a, 7b, 7c
@@ -292,11 +335,8 @@ class InceptionFID : public Net {
     std::string first;
     const int miss = params.missing(&first);
     CD_CHECK(miss == 0, "inception_fid: %d parameters not loaded (first: %s)", miss, first.c_str());
-    for (const Unit& u : units_) {
-      const int64_t n = (int64_t)u.N * u.KH * u.KW * u.w->Cpad;
-      hipLaunchKernelGGL(k_fold_bn, dim3(grid_for(n)), dim3(256), 0, c.st, u.raw, u.gamma, u.beta, u.mean, u.var, kBnEps,
-                         u.N, u.Cin, u.KH, u.KW, u.w->Cpad, u.w->w, u.w->b);
-    }
+    for (const Unit& u : units_)
+      launch_fold_bn(c.st, u.raw, u.gamma, u.beta, u.mean, u.var, u.N, u.Cin, u.KH, u.KW, u.w->Cpad, u.w->w, u.w->b);
     folded_version_ = params.version;
   }
 
@@ -304,16 +344,8 @@ class InceptionFID : public Net {
   Act conv(Ctx& c, const Unit& u, const Act& x, bf16_t* out, int out_ld) {
     const int Cpad = u.w->Cpad, Nrun = round_up(u.N, 32);
     CD_CHECK(x.C == u.Cin && x.ld >= Cpad && out_ld >= Nrun, "inception_fid: conv operand shapes (C %d / Cin %d)", x.C, u.Cin);
-    ConvGemmParams p;
-    p.src0 = x.p; p.C0 = Cpad; p.ld0 = x.ld;
-    p.B = x.B; p.Hs = x.H; p.Ws = x.W; p.Hin = x.H; p.Win = x.W;
-    p.KH = u.KH; p.KW = u.KW; p.stride = u.stride; p.pad_t = u.pad_t; p.pad_l = u.pad_l;
-    p.Hout = (x.H + 2 * u.pad_t - u.KH) / u.stride + 1;
-    p.Wout = (x.W + 2 * u.pad_l - u.KW) / u.stride + 1;
-    p.M = x.B * p.Hout * p.Wout;
-    p.wgt = u.w->w; p.Ktot = u.w->Ktot(); p.N = Nrun;
-    p.bias = u.w->b; p.act = ACT_RELU;
-    p.out = out; p.out_ld = out_ld; p.zeros = c.zeros;
+    const ConvGemmParams p = basic_conv_params(x.p, x.ld, x.B, x.H, x.W, Cpad, u.w->w, u.w->b, u.N, u.KH, u.KW, u.stride, u.pad_t,
+                                               u.pad_l, out, out_ld, c.zeros);
     launch_conv_gemm(c.st, p);
     Act y; y.p = out; y.B = x.B; y.H = p.Hout; y.W = p.Wout; y.C = u.N; y.ld = out_ld;
     return y;
@@ -324,15 +356,8 @@ class InceptionFID : public Net {
     return conv(c, u, x, y.p, y.ld);
   }
   Act pool(Ctx& c, const Act& x, bool max, int stride, int pad, bf16_t* out, int out_ld) {
-    CD_CHECK(x.C % 8 == 0 && x.ld % 8 == 0 && out_ld % 8 == 0, "inception_fid: pool channels");
     const int Ho = (x.H + 2 * pad - 3) / stride + 1, Wo = (x.W + 2 * pad - 3) / stride + 1;
-    const int64_t n = (int64_t)x.B * Ho * Wo * (x.C / 8);
-    if (max)
-      hipLaunchKernelGGL(k_pool3x3<true>, dim3(grid_for(n)), dim3(256), 0, c.st, x.p, x.ld, x.B, x.H, x.W, x.C, stride, pad,
-                         out, out_ld, Ho, Wo);
-    else
-      hipLaunchKernelGGL(k_pool3x3<false>, dim3(grid_for(n)), dim3(256), 0, c.st, x.p, x.ld, x.B, x.H, x.W, x.C, stride, pad,
-                         out, out_ld, Ho, Wo);
+    launch_pool3x3(c.st, x.p, x.ld, x.B, x.H, x.W, x.C, max, stride, pad, out, out_ld);
     Act y; y.p = out; y.B = x.B; y.H = Ho; y.W = Wo; y.C = x.C; y.ld = out_ld;
     return y;
   }

@@ -527,4 +527,22 @@ void launch_avgpool2_split(hipStream_t st, const bf16_t* x, bf16_t* y, int B, in
 void launch_copy_strided_bf16(hipStream_t st, const bf16_t* src, int lds, bf16_t* dst, int ldd,
                               int64_t rows, int cols);
 
+// ---------------------------------------------------------------- FID Inception-v3 (inception.hip)
+// 3 x 3 pool over 16-bit NHWC: x [B][H][W] pixels of stride ldx -> y [B][Ho][Wo] pixels of stride ldy, Ho = (H + 2 pad - 3) /
+// stride + 1. max: the maximum of the in-image taps, else their mean (count_include_pad = False). C, ldx, ldy multiples of 8.
+void launch_pool3x3(hipStream_t st, const bf16_t* x, int ldx, int B, int H, int W, int C, bool max, int stride, int pad,
+                    bf16_t* y, int ldy);
+// global average pool: x [B][HW] pixels of stride ldx, C channels (C, ldx multiples of 8) -> y fp32 [B][C]
+void launch_global_avg(hipStream_t st, const bf16_t* x, int ldx, int B, int HW, int C, float* y);
+// BatchNorm (eps 1e-3, torchvision BasicConv2d) folded into a conv: raw fp32 [N][Cin][KH][KW] -> rows n < N of the packed
+// 16-bit [Npad][KH][KW][Cpad], w' = w * gamma / sqrt(var + eps) (channels Cin.. zero), bias[n] = beta - mean * gamma / sqrt(var + eps)
+void launch_fold_bn(hipStream_t st, const float* raw, const float* gamma, const float* beta, const float* mean, const float* var,
+                    int N, int Cin, int KH, int KW, int Cpad, bf16_t* w, float* bias);
+// the implicit-GEMM launch of one BasicConv2d (conv + folded BatchNorm + ReLU): x [B][H][W] pixels of stride ldx, Cpad channels
+// read; wgt / bias as launch_fold_bn leaves them; N rounded up to 32 columns (the extra weight rows and bias entries are zero, so
+// the GEMM writes the zero padding channels the next layer reads); out [B * Hout * Wout] rows of stride out_ld
+ConvGemmParams basic_conv_params(const bf16_t* x, int ldx, int B, int H, int W, int Cpad, const bf16_t* wgt, const float* bias,
+                                 int N, int KH, int KW, int stride, int pad_t, int pad_l, void* out, int out_ld,
+                                 const bf16_t* zeros);
+
 }  // namespace cd

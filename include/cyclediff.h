@@ -542,6 +542,29 @@ int cd_op_gemm_batched(cd_handle h, const void* a, int lda, int64_t a_bs, const 
  * per image (T % 32 == 0) */
 int cd_op_attn_block_core(cd_handle h, const void* qk, int ldqk, const void* n, int ldn, const void* packed_v,
                           const float* v_bias, int B, int T, int C, void* o, int ldo, void* vt_out, int* branch);
+/* ---- the kernels and launch forms of the FID Inception-v3 (csrc/inception.hip), one at a time, test-only ----
+ * Every 16-bit buffer a kernel reads past or writes into starts as 0xFF bytes (NaN in fp16 and bf16) and has one more 64-row
+ * block of them behind its last row. */
+/* the 3 x 3 pool (max != 0: maximum, else the mean over the in-image taps) as the network launches it: x fp32 NCHW [B,C,H,W],
+ * stored NHWC with row stride C + in_pad (pad columns NaN); the output rows [B*Ho*Wo] (Ho = (H + 2 pad - 3) / stride + 1) go
+ * to columns [out_off, out_off + C) of a buffer of row stride out_ld. y: the whole buffer, guard rows included, as fp32
+ * [B*Ho*Wo + 64][out_ld]. Refused: C % 8, in_pad % 8, out_off % 8, out_ld % 8, out_off + C > out_ld. */
+int cd_op_pool3x3(cd_handle h, const float* x, int B, int C, int H, int W, int in_pad, int max, int stride, int pad,
+                  int out_off, int out_ld, float* y);
+/* the global average pool behind Mixed_7c: x fp32 NCHW [B,C,HW], stored with row stride C + in_pad (pad columns NaN) -> y fp32
+ * [B][C]. Refused: C % 8, in_pad % 8. */
+int cd_op_global_avg(cd_handle h, const float* x, int B, int HW, int C, int in_pad, float* y);
+/* one BasicConv2d (conv without bias, BatchNorm eps 1e-3, ReLU) as the network runs it: the raw fp32 weight w [N][Cin][KH][KW]
+ * and the BatchNorm vectors [N] (all fp32 device) are folded by the network's own fold kernel into a packed weight allocated as
+ * the network allocates it; x fp32 NCHW [B,Cin,H,W] is stored NHWC with row stride in_ld (>= Cpad = round_up(Cin, 32); channels
+ * [Cin, Cpad) zero, [Cpad, in_ld) NaN); the implicit GEMM, filled in by the network's own function with N rounded up to 32, writes
+ * columns [out_off, out_off + round_up(N, 32)) of a buffer of row stride out_ld. tile as cd_op_gemm_batched (read back with
+ * cd_op_last_gemm_config). y: the whole output buffer, guard rows included, fp32 [B*Ho*Wo + 64][out_ld]; w_packed (or NULL): the
+ * packed 16-bit weights as fp32 [round_up(N, 128)][KH][KW][Cpad]; bias_out (or NULL): fp32 [round_up(N, 128)].
+ * Refused: in_ld % 8, in_ld < Cpad, out_off % 8, out_ld % 8, out_off + round_up(N, 32) > out_ld. */
+int cd_op_basic_conv(cd_handle h, const float* x, int B, int Cin, int H, int W, int in_ld, const float* w, const float* gamma,
+                     const float* beta, const float* mean, const float* var, int N, int KH, int KW, int stride, int pad_t,
+                     int pad_l, int out_off, int out_ld, int tile, float* y, float* w_packed, float* bias_out);
 /* micro-benchmark of one conv / GEMM shape on synthetic data (scripts/bench_gemm.py): average ms per launch.
  * act: low byte = activation; | 0x100 = in-place residual update of the output; | 0x200 = fused GroupNorm statistics */
 int cd_op_bench_conv(cd_handle h, int B, int H, int W, int C0, int C1, int N, int k, int stride, int up,

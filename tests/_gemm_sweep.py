@@ -213,6 +213,8 @@ def chm_battery():
         (_case("chm/3x3_s1_5x7", 3, 64, 5, 7, 200, 3), 1, 1),
         (_case("chm/3x3_s2_pad1", 2, 128, 9, 11, 200, 3, stride=2), 1, 1),
         (_case("chm/3x3_s2_asym", 2, 128, 9, 11, 200, 3, stride=2, pad=0, asym=True), 1, 1),
+        (_case("chm/3x3_valid_s1_9x11", 2, 64, 9, 11, 200, 3, pad=0), 1, 1),   # the Inception stem's forms: no padding at all,
+        (_case("chm/3x3_valid_s2_11x9", 3, 64, 11, 9, 200, 3, stride=2, pad=0), 1, 1),  # odd sizes at stride 2 (last tap row in-image)
         (_case("chm/5x5_pad2_5x7", 2, 64, 5, 7, 200, 5), 1, 1),
         (_case("chm/5x5_pad2_10x10", 1, 64, 10, 10, 200, 5), 1, 1),
         (_case("chm/8x8_s8", 2, 64, 24, 16, 200, 8, stride=8, pad=0), 1, 1),

@@ -514,3 +514,49 @@ def softmax_rows_dev(eng, s_dev):
     p = torch.empty_like(s_dev)
     check(eng.lib.cd_op_softmax_rows(eng.h, ptr(s_dev), rows, cols, ptr(p)))
     return p
+
+
+# ------------------------------------------------------------------------------ the FID Inception-v3's kernels and launch forms
+# tests/_inception_ops_ref.py. Every output comes back whole: [rows + GUARD_ROWS, out_ld] with NaN wherever nothing was written.
+GUARD_ROWS = 64
+
+
+def pool3x3(eng, x, max_pool, stride, pad, in_pad=0, out_off=0, out_ld=None):
+    """cd_op_pool3x3: x [B, C, H, W] -> the whole output buffer [B Ho Wo + 64, out_ld] (NaN outside the slice)"""
+    B, Cc, H, W = x.shape
+    out_ld = Cc if out_ld is None else out_ld
+    Ho, Wo = (H + 2 * pad - 3) // stride + 1, (W + 2 * pad - 3) // stride + 1
+    y = torch.zeros((B * Ho * Wo + GUARD_ROWS, out_ld), device="cuda", dtype=torch.float32)
+    xs = dev(x)
+    check(eng.lib.cd_op_pool3x3(eng.h, ptr(xs), B, Cc, H, W, in_pad, int(max_pool), stride, pad, out_off, out_ld, ptr(y)))
+    torch.cuda.synchronize()
+    return y.cpu()
+
+
+def global_avg(eng, x, in_pad=0):
+    """cd_op_global_avg: x [B, C, HW] -> fp32 [B, C]"""
+    B, Cc, HW = x.shape
+    y = torch.full((B, Cc), float("nan"), device="cuda", dtype=torch.float32)
+    xs = dev(x)
+    check(eng.lib.cd_op_global_avg(eng.h, ptr(xs), B, HW, Cc, in_pad, ptr(y)))
+    torch.cuda.synchronize()
+    return y.cpu()
+
+
+def basic_conv(eng, x, w, gamma, beta, mean, var, stride=1, pad=(0, 0), in_ld=None, out_off=0, out_ld=None, tile=0):
+    """cd_op_basic_conv: x [B, Cin, H, W], raw weight w [N, Cin, KH, KW] and the BatchNorm vectors [N] -> (the whole output buffer
+    [B Ho Wo + 64, out_ld], the packed weights [Npad, KH, KW, Cpad], the bias [Npad], the read-back of what ran)"""
+    B, Cin, H, W = x.shape
+    N, _, KH, KW = w.shape
+    Cpad, Npad, Nrun = -(-Cin // 32) * 32, -(-N // 128) * 128, -(-N // 32) * 32
+    in_ld = Cpad if in_ld is None else in_ld
+    out_ld = Nrun if out_ld is None else out_ld
+    Ho, Wo = (H + 2 * pad[0] - KH) // stride + 1, (W + 2 * pad[1] - KW) // stride + 1
+    y = torch.zeros((B * Ho * Wo + GUARD_ROWS, out_ld), device="cuda", dtype=torch.float32)
+    wp = torch.full((Npad, KH, KW, Cpad), float("nan"), device="cuda", dtype=torch.float32)
+    bo = torch.full((Npad,), float("nan"), device="cuda", dtype=torch.float32)
+    t = [dev(v) for v in (x, w, gamma, beta, mean, var)]
+    check(eng.lib.cd_op_basic_conv(eng.h, ptr(t[0]), B, Cin, H, W, in_ld, ptr(t[1]), ptr(t[2]), ptr(t[3]), ptr(t[4]), ptr(t[5]),
+                                   N, KH, KW, stride, pad[0], pad[1], out_off, out_ld, tile, ptr(y), ptr(wp), ptr(bo)))
+    torch.cuda.synchronize()
+    return y.cpu(), wp.cpu(), bo.cpu(), last_gemm_config(eng)

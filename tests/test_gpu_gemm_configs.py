@@ -13,7 +13,9 @@ nothing is missing). Every case
      epilogue arithmetic on every tile), and - without split-K - the other K-step depth as well.
 
 Channel-major K order and the grouped tile walk are process-wide settings (read once): they run in child processes
-(tests/_gemm_env_child.py), one at a time; nothing more is started on the GPU after a child that failed.
+(tests/_gemm_env_child.py), one at a time; nothing more is started on the GPU after a child that failed. A third child runs
+the launch forms of the FID Inception-v3's BasicConv2d units that meet the channel-major order at its production batch (valid
+3 x 3 at stride 1 and 2 on odd sizes, 3 channels padded to 32, 1 x 7 and 7 x 1) through cd_op_basic_conv, under the same rule.
 """
 import os
 import subprocess
@@ -24,6 +26,7 @@ import pytest
 import torch
 
 import _gemm_sweep as gs
+import _inception_ops_ref as ir
 import _ops
 from _ops import bf16_round as r16
 
@@ -212,4 +215,46 @@ def test_grouped_tile_walk(engine, report, group_child, tile):
         report.add("gemm_group/" + c["name"], bit_identical=same, rel_to_max=es["rel_to_max"], mean_rel=es["mean_rel"])
         if not same:
             failures.append((c["name"], "grouped walk differs from the row-major walk"))
+    assert not failures, failures
+
+
+# ------------------------------------------------------------------------------------------------ Inception forms, channel-major
+@pytest.fixture(scope="module")
+def inception_chm_child(tmp_path_factory, engine, chm_child, group_child):  # after the two others, one child at a time
+    return _run_child("inception_chm", {"CYCLEDIFF_KORDER": "2"}, tmp_path_factory.mktemp("gemm_inception_chm"), 600)
+
+
+@pytest.mark.parametrize("name", ir.CONV_CHM)
+def test_inception_forms_channel_major(engine, report, inception_chm_child, name):
+    """test_channel_major_order's acceptance on the BasicConv2d forms (tests/_inception_ops_ref.py): chm == 1 in the read-back,
+    the float64 bounds, max|err| at most CHM_ERR_FACTOR x the tap-major run's + one fp32 ulp of max|ref|; and nothing written
+    outside the slice."""
+    fmt = ir.lib_fmt()
+    c = ir.CONV[name]
+    o = ir.conv_operands(c, fmt)
+    run = _ops.basic_conv(engine, o["x"], o["w"], o["gamma"], o["beta"], o["mean"], o["var"], stride=c["stride"], pad=c["pad"],
+                          in_ld=c["in_ld"], out_off=c["off"], out_ld=c["ld"], tile=gs.ANCHOR_TILE)
+    assert run[3]["chm"] == 0 and run[3]["tile"] == gs.ANCHOR_TILE, run[3]
+    fails_tap, fig_tap = ir.check_basic_conv(c, o, run[0], run[1], run[2], fmt)
+    assert not fails_tap, fails_tap
+    failures = []
+    for tile in ir.CONV_TILES:
+        key = "%s|tile%d" % (name, tile)
+        buf, wp, bo = (torch.from_numpy(child_arr(inception_chm_child, key + s)) for s in ("|y", "|w", "|b"))
+        rb = child_arr(inception_chm_child, key + "|rb").tolist()  # tile, bk, split, chm, tile_group
+        assert rb[3] == 1 and rb[4] == 0 and (tile == 0 or rb[0] == tile), (key, rb)
+        assert torch.equal(wp, run[1]) and torch.equal(bo, run[2]), key  # the same fold in both processes
+        fails, fig = ir.check_basic_conv(c, o, buf, wp, bo, fmt)
+        failures += [(key,) + f for f in fails]
+        if "max_abs" not in fig:
+            continue
+        ref_max = float(ir.conv_ref(c, o, wp, bo)[0].abs().max())
+        ulp = float(np.spacing(np.float32(ref_max)))
+        ratio = fig["max_abs"] / max(fig_tap["max_abs"], 1e-30)
+        report.add("inception_ops/chm/" + key, tile_ran=rb[0], bk=rb[1], rel_to_max=fig["rel_to_max"], mean_rel=fig["mean_rel"],
+                   max_abs=fig["max_abs"], max_abs_tap_major=fig_tap["max_abs"], ratio=ratio, chm=rb[3])
+        print("%-40s chm %d tile %2d max_abs %.3e tap-major %.3e ratio %.3f" % (key, rb[3], rb[0], fig["max_abs"],
+                                                                                fig_tap["max_abs"], ratio))
+        if not fig["max_abs"] <= CHM_ERR_FACTOR * fig_tap["max_abs"] + ulp:
+            failures.append((key, "error vs tap-major", fig["max_abs"], fig_tap["max_abs"]))
     assert not failures, failures

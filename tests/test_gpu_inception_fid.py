@@ -16,6 +16,7 @@ from cycle_diffusion_amd import _ffi
 from cycle_diffusion_amd.engine import INCEPTION_BLOCKS
 from cycle_diffusion_amd.utils import fid
 
+import _ops
 from _inception_ref import inception_fid_forward
 
 pytestmark = pytest.mark.gpu
@@ -91,6 +92,54 @@ def test_block_by_block_parity(eng):
     assert float(ref_pool3.abs().mean()) > 1e-2  # the synthetic weights keep the activations at scale
     bad = [(n, v) for n, v in errs if v > _tol()]
     assert not bad, bad
+
+
+# The smallest batch at which all four 3 x 3 stem convs take the channel-major K order (conv_gemm.hip takes_channel_major: at
+# least 64 x 64 stored pixels and 32 MiB of activation): Conv2d_1a (299 x 299 x 32 channels) from 6 images, Conv2d_2a / 2b
+# (149 / 147 squared x 32) from 24 / 25, Conv2d_4a (73 x 73 x 96) from 33 - at 32 images its activation is 31.2 MiB.
+# utils/fid.py feeds 64 images at a time.
+STEM_CHM_BATCH = 33
+STEM_3X3_BLOCKS = (0, 1, 2, 5)  # Conv2d_1a, 2a, 2b, 4a in the block list
+
+
+def test_stem_convs_at_the_production_k_order(eng, report):
+    """The block-by-block test runs 3 images, which is tap-major everywhere. Here every 3 x 3 stem conv runs channel-major
+    (asserted through the launcher's read-back) and is held to test_channel_major_order's rule against the same images fed one
+    at a time (tap-major, asserted): max|err| against the float64 restatement at most 2 x the tap-major run's + one fp32 ulp
+    of max|ref|."""
+    e, net, sd = eng
+    n = STEM_CHM_BATCH
+    x = _lowpass(n, 3).cuda()
+    sd64 = {k: v.double().cuda() for k, v in sd.items()}
+    failures = []
+    for k in STEM_3X3_BLOCKS:
+        with torch.no_grad():
+            ref = inception_fid_forward(sd64, x.double(), stop_block=k)
+        big = e.inception_features(net, x, stop_block=k)
+        torch.cuda.synchronize()
+        rb = _ops.last_gemm_config(e)
+        assert rb["chm"] == 1, (INCEPTION_BLOCKS[k], rb)
+        assert big.shape == ref.shape
+        err_big = float((big.double() - ref).abs().max())
+        err_one = 0.0
+        for i in range(n):
+            one = e.inception_features(net, x[i:i + 1], stop_block=k)
+            torch.cuda.synchronize()
+            rb1 = _ops.last_gemm_config(e)
+            assert rb1["chm"] == 0, (INCEPTION_BLOCKS[k], i, rb1)
+            err_one = max(err_one, float((one.double() - ref[i:i + 1]).abs().max()))
+        ref_max = float(ref.abs().max())
+        ulp = float(np.spacing(np.float32(ref_max)))
+        ratio = err_big / max(err_one, 1e-30)
+        print("inception stem %s at %d images: channel-major (tile %d) max_abs %.3e, one image at a time (tap-major) %.3e, "
+              "ratio %.3f, max|ref| %.3f" % (INCEPTION_BLOCKS[k], n, rb["tile"], err_big, err_one, ratio, ref_max))
+        report.add("inception_stem_chm/" + INCEPTION_BLOCKS[k], batch=n, tile_ran=rb["tile"], bk=rb["bk"], max_abs=err_big,
+                   max_abs_tap_major=err_one, ratio=ratio, rel_l2=_rel(big, ref))
+        if not (np.isfinite(err_big) and err_big <= 2.0 * err_one + ulp):
+            failures.append((INCEPTION_BLOCKS[k], err_big, err_one))
+        if not _rel(big, ref) <= _tol():
+            failures.append((INCEPTION_BLOCKS[k], "relative L2", _rel(big, ref)))
+    assert not failures, failures
 
 
 def test_batch_splits_agree(eng):
