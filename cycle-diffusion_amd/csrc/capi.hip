@@ -178,20 +178,30 @@ int cd_net_missing_params(cd_handle h, int net, int* n_missing, char* first_name
 // ------------------------------------------------------------------ helpers for the forward paths
 namespace {
 
-// ctx fp32 [B][L][Dc] -> bf16, optionally [uncond | cond] stacking for classifier-free guidance
-bf16_t* make_ctx(cd_engine* h, const float* a, const float* b, int B, int L, int Dc, bool f32 = false) {
-  const int nb = b ? 2 * B : B;
-  if (f32) {  // fp32 networks (CD_PREC_F32 / F32X3 with transformer blocks) take the context as it is
-    float* out = (float*)h->arena.alloc((size_t)nb * L * Dc * 4);
-    const size_t half = (size_t)B * L * Dc;
-    HIP_CHECK(hipMemcpyAsync(out, a, half * 4, hipMemcpyDeviceToDevice, h->st));
-    if (b) HIP_CHECK(hipMemcpyAsync(out + half, b, half * 4, hipMemcpyDeviceToDevice, h->st));
-    return (bf16_t*)out;
-  }
-  bf16_t* out = (bf16_t*)h->arena.alloc((size_t)nb * L * Dc * 2);
-  launch_nchw_to_nhwc(h->st, a, out, B * L, Dc, 1, Dc, 1.f, 0.f, 0);
-  if (b) launch_nchw_to_nhwc(h->st, b, out + (size_t)B * L * Dc, B * L, Dc, 1, Dc, 1.f, 0.f, 0);
-  return out;
+// context rows fp32 [rows][L][Dc] -> rows [row0, row0 + rows) of the context tensor `dst` in the network's format: 16-bit, or -
+// fp32 networks (CD_PREC_F32 / F32X3 with transformer blocks) - as they are
+void put_ctx(cd_engine* h, const Net* n, const float* src, void* dst, size_t row0, int rows, int L, int Dc) {
+  const size_t per = (size_t)L * Dc;
+  if (n->f32) HIP_CHECK(hipMemcpyAsync((float*)dst + row0 * per, src, (size_t)rows * per * 4, hipMemcpyDeviceToDevice, h->st));
+  else launch_nchw_to_nhwc(h->st, src, (bf16_t*)dst + row0 * per, rows * L, Dc, 1, Dc, 1.f, 0.f, 0);
+}
+
+// the context of a forward of B (or, with b, 2 B) rows, optionally [uncond | cond] stacking for classifier-free guidance
+bf16_t* make_ctx(cd_engine* h, const Net* n, const float* a, const float* b, int B, int L, int Dc) {
+  void* out = h->arena.alloc((size_t)(b ? 2 * B : B) * L * Dc * (n->f32 ? 4 : 2));
+  put_ctx(h, n, a, out, 0, B, L, Dc);
+  if (b) put_ctx(h, n, b, out, B, B, L, Dc);
+  return (bf16_t*)out;
+}
+
+// image rows fp32 NCHW [B][C][HW] times `mul` -> the network's input rows [B][HW][cpad]: 16-bit, fp32, or - a split-mode
+// network - fp16 pairs; dup: the B samples once more behind themselves (a classifier-free-guidance batch built from one x_t,
+// ddim.py:553-559)
+void put_net_input(cd_engine* h, const Net* n, const float* src, void* dst, int B, int C, int HW, int cpad, float mul, bool dup) {
+  if (!n->f32) { launch_nchw_to_nhwc(h->st, src, (bf16_t*)dst, B, C, HW, cpad, mul, 0.f, dup ? 1 : 0); return; }
+  for (int r = 0; r < (dup ? 2 : 1); ++r)
+    launch_nchw_to_nhwc_f32(h->st, src, (float*)dst + (size_t)r * B * HW * cpad, B, C, HW, cpad, mul, 0.f, n->x3 ? 1 : 0,
+                            h->overflow_dev);
 }
 
 struct Guidance {
@@ -330,7 +340,7 @@ SamplerState setup_sampler(cd_engine* h, int net, const float* ctx_c, const floa
   if (ctx_c || ctx_uc) {
     const int Dc = s.u->desc.context_dim;
     CD_CHECK(Dc > 0 && ctx_len > 0, "network has no cross-attention but a context was given");
-    bf16_t* cx = s.cfg ? make_ctx(h, ctx_uc, ctx_c, B, ctx_len, Dc, s.u->f32) : make_ctx(h, gd.ctx_single, nullptr, B, ctx_len, Dc, s.u->f32);
+    bf16_t* cx = s.cfg ? make_ctx(h, s.u, ctx_uc, ctx_c, B, ctx_len, Dc) : make_ctx(h, s.u, gd.ctx_single, nullptr, B, ctx_len, Dc);
     s.u->set_context(c, cx, s.Bn, ctx_len);
   } else {
     CD_CHECK(s.u->desc.context_dim <= 0 || !s.u->desc.use_spatial_transformer,
@@ -353,12 +363,7 @@ SamplerState setup_sampler(cd_engine* h, int net, const float* ctx_c, const floa
 
 void run_unet(cd_engine* h, SamplerState& s, int step) {
   Ctx c = h->ctx();
-  if (s.f32) {
-    launch_nchw_to_nhwc_f32(h->st, s.xt, (float*)s.xin, s.B, s.C, s.HW, s.cpad, 1.f, 0.f, s.u->x3 ? 1 : 0, h->overflow_dev);
-    if (s.cfg)  // the classifier-free-guidance batch [uncond | cond] is built from one x_t (ddim.py:553-559)
-      launch_nchw_to_nhwc_f32(h->st, s.xt, (float*)s.xin + (size_t)s.B * s.HW * s.cpad, s.B, s.C, s.HW, s.cpad, 1.f, 0.f,
-                              s.u->x3 ? 1 : 0, h->overflow_dev);
-  }
+  if (s.f32) put_net_input(h, s.u, s.xt, s.xin, s.B, s.C, s.HW, s.cpad, 1.f, s.cfg);  // (the 16-bit rows: the step kernels)
   UNetIO io;
   io.xin = s.xin; io.B = s.Bn; io.tab = s.args.geom.tab; io.step = step; io.t_shared = true;
   io.cfg_dup = s.cfg;
@@ -382,12 +387,11 @@ int cd_unet_forward(cd_handle h, int net, const float* x, const float* t, const 
   if (ctx) {
     const int Dc = u->desc.context_dim;
     CD_CHECK(Dc > 0, "network has no cross-attention");
-    bf16_t* cx = make_ctx(h, ctx, nullptr, B, ctx_len, Dc, u->f32);
+    bf16_t* cx = make_ctx(h, u, ctx, nullptr, B, ctx_len, Dc);
     u->set_context(c, cx, B, ctx_len);
   }
   bf16_t* xin = (bf16_t*)h->arena.alloc((size_t)B * HW * u->in_cpad * (u->f32 ? 4 : 2));
-  if (u->f32) launch_nchw_to_nhwc_f32(h->st, x, (float*)xin, B, C, HW, u->in_cpad, 1.f, 0.f, u->x3 ? 1 : 0, h->overflow_dev);
-  else launch_nchw_to_nhwc(h->st, x, xin, B, C, HW, u->in_cpad, 1.f, 0.f, 0);
+  put_net_input(h, u, x, xin, B, C, HW, u->in_cpad, 1.f, false);
   float* eh = (float*)h->arena.alloc((size_t)B * HW * Co * 4);
   UNetIO io; io.xin = xin; io.B = B; io.t_explicit = t; io.t_shared = false; io.out = eh; io.out_ld = Co;
   u->forward(c, io);
@@ -459,8 +463,7 @@ int cd_vae_encode(cd_handle h, int net, const float* img, const float* noise, ui
   const int cin = v->desc.in_channels, cp = round_up(cin, 32), hl = R / v->factor;
   // 16-bit rows, or - first stage in fp32 / in the split mode - fp32 rows / fp16 pairs (the same bytes)
   bf16_t* xin = (bf16_t*)h->arena.alloc((size_t)B * R * R * cp * (v->f32 ? 4 : 2));
-  if (v->f32) launch_nchw_to_nhwc_f32(h->st, img, (float*)xin, B, cin, R * R, cp, 1.f, 0.f, v->x3 ? 1 : 0, h->overflow_dev);
-  else launch_nchw_to_nhwc(h->st, img, xin, B, cin, R * R, cp, 1.f, 0.f, 0);
+  put_net_input(h, v, img, xin, B, cin, R * R, cp, 1.f, false);
   const int mch = v->moments_channels;
   float* mom = (float*)h->arena.alloc((size_t)B * hl * hl * mch * 4);
   v->encode_moments(c, xin, B, R, mom);
@@ -482,10 +485,8 @@ int cd_vae_decode(cd_handle h, int net, const float* z0, int B, int hlat, float 
   bf16_t* zin = (bf16_t*)h->arena.alloc((size_t)B * hlat * hlat * cp * (v->f32 ? 4 : 2));
   if (v->codebook)  // VQModelInterface.decode: quantise to the codebook first (autoencoder.py:274-280)
     launch_vq_quantize(h->st, z0, 1.0f / scale, v->codebook, v->n_embed, zc, B, hlat * hlat, zin, cp);
-  else if (v->f32)
-    launch_nchw_to_nhwc_f32(h->st, z0, (float*)zin, B, zc, hlat * hlat, cp, 1.0f / scale, 0.f, v->x3 ? 1 : 0, h->overflow_dev);
   else
-    launch_nchw_to_nhwc(h->st, z0, zin, B, zc, hlat * hlat, cp, 1.0f / scale, 0.f, 0);  // z = 1/scale * z (ddpm.py:705)
+    put_net_input(h, v, z0, zin, B, zc, hlat * hlat, cp, 1.0f / scale, false);  // z = 1/scale * z (ddpm.py:705)
   float* o = (float*)h->arena.alloc((size_t)B * R * R * co * 4);
   v->decode(c, zin, B, hlat, o);
   launch_nhwc_to_nchw(h->st, o, 1, co, img, B, co, R * R, out_mul, out_add);
@@ -700,12 +701,8 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     const int Dc = u->desc.context_dim;
     CD_CHECK(Dc > 0 && ctx_len > 0, "network has no cross-attention but a context was given");
     // one context tensor in batch-row order: [enc (uncond | cond) | dec (uncond | cond)]
-    const size_t esz = f32 ? 4 : 2, per = (size_t)ctx_len * Dc;
-    char* cx = (char*)h->arena.alloc((size_t)Bn * per * esz);
-    auto put = [&](const float* src, int rows, size_t row0) {
-      if (f32) HIP_CHECK(hipMemcpyAsync(cx + row0 * per * 4, src, (size_t)rows * per * 4, hipMemcpyDeviceToDevice, h->st));
-      else launch_nchw_to_nhwc(h->st, src, (bf16_t*)cx + row0 * per, rows * ctx_len, Dc, 1, Dc, 1.f, 0.f, 0);
-    };
+    void* cx = h->arena.alloc((size_t)Bn * ctx_len * Dc * (f32 ? 4 : 2));
+    auto put = [&](const float* src, int rows, size_t row0) { put_ctx(h, u, src, cx, row0, rows, ctx_len, Dc); };
     if (ge.cfg) { put(enc_ctx_uc, B, 0); put(enc_ctx_c, B, B); } else put(ge.ctx_single, B, 0);
     if (gd.cfg) { put(dec_ctx_uc, Bd, Ben); put(dec_ctx_c, Bd, Ben + Bd); } else put(gd.ctx_single, Bd, Ben);
     u->set_context(c, (const bf16_t*)cx, Bn, ctx_len);
@@ -768,12 +765,8 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
   for (int i = 0; i < K; ++i) {
     const int k = K - 1 - i;
     if (f32) {
-      float* xf = (float*)xin;
-      launch_nchw_to_nhwc_f32(h->st, xt_e, xf, B, C, HW, cpad, 1.f, 0.f, u->x3 ? 1 : 0, h->overflow_dev);
-      if (ge.cfg) launch_nchw_to_nhwc_f32(h->st, xt_e, xf + (size_t)B * HW * cpad, B, C, HW, cpad, 1.f, 0.f, u->x3 ? 1 : 0, h->overflow_dev);
-      float* xd = xf + (size_t)Ben * HW * cpad;
-      launch_nchw_to_nhwc_f32(h->st, xt_d, xd, Bd, C, HW, cpad, 1.f, 0.f, u->x3 ? 1 : 0, h->overflow_dev);
-      if (gd.cfg) launch_nchw_to_nhwc_f32(h->st, xt_d, xd + (size_t)Bd * HW * cpad, Bd, C, HW, cpad, 1.f, 0.f, u->x3 ? 1 : 0, h->overflow_dev);
+      put_net_input(h, u, xt_e, xin, B, C, HW, cpad, 1.f, ge.cfg);
+      put_net_input(h, u, xt_d, xin + (size_t)Ben * row_in, Bd, C, HW, cpad, 1.f, gd.cfg);
     }
     UNetIO io;
     io.xin = (const bf16_t*)xin; io.B = Bn; io.tab = tab_d; io.step = k; io.t_shared = true;  // rows k of both tables carry the same t
@@ -1017,13 +1010,9 @@ int cd_automask(cd_handle h, int net, const float* x0, const float* ctx_src, con
     const int nc = std::min(per_fwd, n_draws - i0), rows = 2 * nc * B;
     if (nc != cur) {  // the first forward, and a shorter last one
       h->arena.release(buffers);
-      const size_t half = (size_t)B * ctx_len * Dc;
       bf16_t* cx = (bf16_t*)h->arena.alloc((size_t)rows * ctx_len * Dc * esz);
-      for (int j = 0; j < 2 * nc; ++j) {  // [c_src x nc | c_tgt x nc], converted as make_ctx converts them
-        const float* from = j < nc ? ctx_src : ctx_tgt;
-        if (u->f32) HIP_CHECK(hipMemcpyAsync((float*)cx + j * half, from, half * 4, hipMemcpyDeviceToDevice, h->st));
-        else launch_nchw_to_nhwc(h->st, from, cx + j * half, B * ctx_len, Dc, 1, Dc, 1.f, 0.f, 0);
-      }
+      for (int j = 0; j < 2 * nc; ++j)  // [c_src x nc | c_tgt x nc]
+        put_ctx(h, u, j < nc ? ctx_src : ctx_tgt, cx, (size_t)j * B, B, ctx_len, Dc);
       u->set_context(c, cx, rows, ctx_len);
       xin = (bf16_t*)h->arena.alloc((size_t)rows * HW * u->in_cpad * esz);
       if (!u->f32) HIP_CHECK(hipMemsetAsync(xin, 0, (size_t)rows * HW * u->in_cpad * esz, h->st));  // the pad channels
@@ -1038,10 +1027,7 @@ int cd_automask(cd_handle h, int net, const float* x0, const float* ctx_src, con
     q.noise = noise ? noise + (int64_t)i0 * per_draw : nullptr;
     q.stream0 = (uint32_t)(0x6000 + i0);
     launch_automask_qsample(h->st, q);
-    if (u->f32)  // the fp32 networks' layout pass, once per half
-      for (int half = 0; half < 2; ++half)
-        launch_nchw_to_nhwc_f32(h->st, q.xq, (float*)xin + (size_t)half * nc * B * HW * u->in_cpad, nc * B, C, HW, u->in_cpad,
-                                1.f, 0.f, u->x3 ? 1 : 0, h->overflow_dev);
+    if (u->f32) put_net_input(h, u, q.xq, xin, nc * B, C, HW, u->in_cpad, 1.f, /*dup=*/true);  // the layout pass, once per half
     UNetIO io; io.xin = xin; io.B = rows; io.t_explicit = tvec; io.t_shared = false; io.out = eh; io.out_ld = Co;
     u->forward(c, io);
     m.e_src = eh; m.e_tgt = eh + (int64_t)nc * B * m.sb;
@@ -1099,10 +1085,8 @@ int cd_word_maps(cd_handle h, int net, const float* x0, const float* ctx, int ct
     const int nc = std::min(per_fwd, n_draws - i0), rows = nc * B;
     if (nc != cur) {  // the first forward, and a shorter last one
       h->arena.release(buffers);
-      const size_t one = (size_t)B * ctx_len * Dc;
       bf16_t* cx = (bf16_t*)h->arena.alloc((size_t)rows * ctx_len * Dc * 2);
-      for (int j = 0; j < nc; ++j)  // the context once per draw, converted as make_ctx converts it
-        launch_nchw_to_nhwc(h->st, ctx, cx + j * one, B * ctx_len, Dc, 1, Dc, 1.f, 0.f, 0);
+      for (int j = 0; j < nc; ++j) put_ctx(h, u, ctx, cx, (size_t)j * B, B, ctx_len, Dc);  // the context once per draw
       u->set_context(c, cx, rows, ctx_len);
       xin = (bf16_t*)h->arena.alloc((size_t)rows * HW * u->in_cpad * 2);
       HIP_CHECK(hipMemsetAsync(xin, 0, (size_t)rows * HW * u->in_cpad * 2, h->st));  // the pad channels

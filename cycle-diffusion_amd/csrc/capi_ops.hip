@@ -1071,7 +1071,8 @@ int cd_op_gemm_batched(cd_handle h, const void* a, int lda, int64_t a_bs, const 
   CD_API_END
 }
 
-// at_core (nets_ho_vae.hip) on the caller's q | k rows, normalised rows and output; vt_out (or NULL) receives V^T [B][C][Tpad]
+// at_core (engine.hip) with one head on the caller's q | k rows, normalised rows and output; vt_out (or NULL) receives V^T
+// [B][C][Tpad]
 int cd_op_attn_block_core(cd_handle h, const void* qk, int ldqk, const void* n, int ldn, const void* packed_v,
                           const float* v_bias, int B, int T, int C, void* o, int ldo, void* vt_out, int* branch) {
   CD_API_BEGIN
@@ -1082,7 +1083,7 @@ int cd_op_attn_block_core(cd_handle h, const void* qk, int ldqk, const void* n, 
   const ConvW& wv = *(const ConvW*)packed_v;
   CD_CHECK(wv.N == C && wv.Cpad == C && wv.KH == 1 && wv.KW == 1, "packed weight does not match the call");
   const AtCoreOut r = at_core(c, wv, v_bias, op_rows_view(qk, B, T, 2 * C, ldqk, false), op_rows_view(n, B, T, C, ldn, false), C,
-                              op_rows_view(o, B, T, C, ldo, false));
+                              /*heads=*/1, op_rows_view(o, B, T, C, ldo, false));
   if (vt_out) HIP_CHECK(hipMemcpyAsync(vt_out, r.vt, (size_t)B * C * r.Tpad * 2, hipMemcpyDeviceToDevice, h->st));
   if (branch) *branch = r.branch;
   op_bare_done(h);

@@ -39,13 +39,6 @@ struct ClipLayer {
   float* vbias = nullptr;
 };
 
-LNW mk_ln(ParamStore& ps, const std::string& pfx, int C) {
-  LNW g; g.C = C;
-  g.g = ps.new_vec(C, 1.f); g.b = ps.new_vec(C, 0.f);
-  ps.vec(pfx + ".weight", g.g, C);
-  ps.vec(pfx + ".bias", g.b, C);
-  return g;
-}
 ConvW* mk_linear(ParamStore& ps, const std::string& pfx, int N, int K) {
   ConvW* c = ps.new_conv(N, K, 1, 1, true);
   ps.conv_weight(pfx + ".weight", c, 2);
@@ -55,8 +48,8 @@ ConvW* mk_linear(ParamStore& ps, const std::string& pfx, int N, int K) {
 
 ClipLayer mk_layer_openai(ParamStore& ps, const std::string& lp, int D, int mlp) {
   ClipLayer L;
-  L.ln1 = mk_ln(ps, lp + ".ln_1", D);
-  L.ln2 = mk_ln(ps, lp + ".ln_2", D);
+  L.ln1 = make_ln(ps, lp + ".ln_1", D);
+  L.ln2 = make_ln(ps, lp + ".ln_2", D);
   // nn.MultiheadAttention: in_proj_weight [3D, D] = [Wq; Wk; Wv], in_proj_bias [3D]
   L.qk = ps.new_conv(2 * D, D, 1, 1, true);
   ps.conv_rows(lp + ".attn.in_proj_weight", {3 * D, D}, L.qk, 0, D, 0, D, 0);
@@ -99,8 +92,8 @@ class ClipText : public TextEncoder {
       for (int i = 0; i < layers_n_; ++i) {
         const std::string lp = root + "encoder.layers." + std::to_string(i);
         ClipLayer L;
-        L.ln1 = mk_ln(params, lp + ".layer_norm1", D);
-        L.ln2 = mk_ln(params, lp + ".layer_norm2", D);
+        L.ln1 = make_ln(params, lp + ".layer_norm1", D);
+        L.ln2 = make_ln(params, lp + ".layer_norm2", D);
         L.qk = params.new_conv(2 * D, D, 1, 1, true);
         params.conv_rows(lp + ".self_attn.q_proj.weight", {D, D}, L.qk, 0, D, 0, D, 0);
         params.conv_rows(lp + ".self_attn.k_proj.weight", {D, D}, L.qk, D, D, 0, D, 0);
@@ -115,7 +108,7 @@ class ClipText : public TextEncoder {
         L.fc2 = mk_linear(params, lp + ".mlp.fc2", D, mlp_);
         layers_.push_back(L);
       }
-      final_ = mk_ln(params, root + "final_layer_norm", D);
+      final_ = make_ln(params, root + "final_layer_norm", D);
     } else {
       params.mat_f32("token_emb.weight", tok_, vocab_, D);
       params.mat_f32("pos_emb.emb.weight", pos_, maxpos_, D);
@@ -123,8 +116,8 @@ class ClipText : public TextEncoder {
         const std::string la = "attn_layers.layers." + std::to_string(2 * i);      // (LayerNorm, Attention, Residual)
         const std::string lf = "attn_layers.layers." + std::to_string(2 * i + 1);  // (LayerNorm, FeedForward, Residual)
         ClipLayer L;
-        L.ln1 = mk_ln(params, la + ".0", D);
-        L.ln2 = mk_ln(params, lf + ".0", D);
+        L.ln1 = make_ln(params, la + ".0", D);
+        L.ln2 = make_ln(params, lf + ".0", D);
         L.qk = params.new_conv(2 * I, D, 1, 1, false);
         params.conv_rows(la + ".1.to_q.weight", {I, D}, L.qk, 0, I, 0, I, 0);
         params.conv_rows(la + ".1.to_k.weight", {I, D}, L.qk, I, I, 0, I, 0);
@@ -135,7 +128,7 @@ class ClipText : public TextEncoder {
         L.fc2 = mk_linear(params, lf + ".1.net.2", D, mlp_);
         layers_.push_back(L);
       }
-      final_ = mk_ln(params, "norm", D);
+      final_ = make_ln(params, "norm", D);
     }
   }
   void init_openai(const cd_net_desc& d) {
@@ -158,8 +151,8 @@ class ClipText : public TextEncoder {
       params.vec(root + "class_embedding", cls_, D);
       pos_ = params.new_vec(maxpos_ * D);
       params.mat_f32(root + "positional_embedding", pos_, maxpos_, D);
-      pre_ = mk_ln(params, root + "ln_pre", D);
-      final_ = mk_ln(params, root + "ln_post", D);
+      pre_ = make_ln(params, root + "ln_pre", D);
+      final_ = make_ln(params, root + "ln_post", D);
       proj_ = params.new_conv(embed_, D, 1, 1, false);
       params.conv_weight_t(root + "proj", proj_);
     } else {
@@ -168,7 +161,7 @@ class ClipText : public TextEncoder {
       pos_ = params.new_vec(maxpos_ * D);
       params.mat_f32("token_embedding.weight", tok_, vocab_, D);
       params.mat_f32("positional_embedding", pos_, maxpos_, D);
-      final_ = mk_ln(params, "ln_final", D);
+      final_ = make_ln(params, "ln_final", D);
       proj_ = params.new_conv(embed_, D, 1, 1, false);
       params.conv_weight_t("text_projection", proj_);
     }

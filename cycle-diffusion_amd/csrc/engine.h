@@ -140,6 +140,18 @@ struct Ctx {
   bool x3 = false;              // ... with its GroupNorm-fed convolutions as three-term fp16 GEMMs (Net::x3)
   int* overflow = nullptr;      // host-visible word the split kernels set on a value outside the fp16 range
 };
+// A network's precision flags on the context for the length of one forward (or of its context projections); the previous
+// ones are back on exit, also when a CD_CHECK throws
+class PrecisionScope {
+ public:
+  PrecisionScope(Ctx& c, bool f32, bool x3) : c_(c), f32_(c.f32), x3_(c.x3) { c.f32 = f32; c.x3 = x3; }
+  ~PrecisionScope() { c_.f32 = f32_; c_.x3 = x3_; }
+  PrecisionScope(const PrecisionScope&) = delete;
+  PrecisionScope& operator=(const PrecisionScope&) = delete;
+ private:
+  Ctx& c_;
+  const bool f32_, x3_;
+};
 
 // shared building blocks -------------------------------------------------------------------
 struct ConvOpts {
@@ -185,6 +197,38 @@ Act layernorm_fwd(Ctx& c, const LNW& w, const Act& x);
 // 16-bit path, single source, no SiLU / FiLM: the statistics passes of groupnorm_fwd without the apply pass. Returns the
 // per-image multiply-add coefficients [B][2][C] (al | be), valid until the next GroupNorm of this engine is launched
 const float* groupnorm_coef_fwd(Ctx& c, const GNW& w, const Act& x);
+// declarations under the reference's state_dict prefix `pfx`: the gain and bias of a norm, the weight (and bias) of a k x k
+// conv or linear layer. ref_ndim: rank of the reference weight tensor (2 = nn.Linear, 3 = Conv1d, 4 = Conv2d)
+GNW make_gn(ParamStore& ps, const std::string& pfx, int C, float eps);
+LNW make_ln(ParamStore& ps, const std::string& pfx, int C);
+ConvW* make_conv(ParamStore& ps, const std::string& pfx, int N, int Cin, int k, bool bias = true, bool geglu = false,
+                 int ref_ndim = 4, float wscale = 1.f);
+// the network's input rows [B][H][W][C] as the caller laid them out: 16-bit, fp32, or - a split-mode network - fp16 pairs
+Act net_input_act(const void* p, int B, int H, int W, int C, bool f32, bool x3);
+
+// Residual block of the four conv nets: GroupNorm -> SiLU -> conv3x3 (+ the block's row of the time embedding) -> GroupNorm
+// (FiLM: scaled and shifted by that row instead) -> SiLU -> conv3x3, plus the input, through a 1 x 1 projection when the
+// channels change; up / down: resblock_updown (improved_ddpm/unet.py:104-135). The networks declare the weights under
+// their own state_dict names and assign emb_off.
+struct ResW {
+  int cin = 0, cout = 0;
+  bool up = false, down = false, film = false;
+  GNW gn1, gn2;
+  ConvW *conv1 = nullptr, *conv2 = nullptr, *skip = nullptr;
+  int emb_off = -1;  // offset into the fused time-embedding projection; -1 = no embedding row (the first stage)
+};
+// x2: second source of a channel concat, or null; proj [1 or B][proj_ld]: time_emb_fwd's rows
+Act res_fwd(Ctx& c, const ResW& r, const Act& x, const Act* x2, const float* proj, int proj_ld, bool t_shared);
+
+// Attention block on image tokens: GroupNorm -> q | k and v projections -> softmax(D^-1/2 q k^T) v + vbias per head of
+// width D = C / heads -> proj_out, plus the input
+struct AttnW {
+  int C = 0, heads = 1;
+  GNW norm;
+  ConvW *qk = nullptr, *v = nullptr, *proj = nullptr;  // [Wq; Wk] with bias, Wv without (vbias is added to the output)
+  float* vbias = nullptr;
+};
+Act attn_block_fwd(Ctx& c, const AttnW& a, const Act& x);
 
 // Entry of a SpatialTransformer block of the 320-channel level with d_head = 40 (16-bit path): GroupNorm -> proj_in ->
 // LayerNorm1 -> to_q | to_k -> V^T. On whole images of a multiple of 256 tokens and enough rows for the streaming kernel
@@ -215,11 +259,11 @@ void st_entry_refresh(hipStream_t st, StEntryW& w);
 struct StEntryOut { Act h, qk; bf16_t* vt = nullptr; int Tpad = 0; int stages = 0; };  // stages: the bits that ran
 // V^T[b] = Wv . X[b]^T on the implicit-GEMM family: weights as the A operand, tokens as the B operand -> [B][C][Tpad]
 void vt_gemm_fwd(Ctx& c, const ConvW& wv, const bf16_t* x, int ldx, int B, int T, int Tpad, bf16_t* vt);
-// the single-head AttnBlock of the Ho-DDPM U-Net / the first stages between its q | k projection and proj_out (nets_ho_vae.hip):
-// qk [B*T][2C] and the normalised rows n [B*T][C] -> o = softmax(C^-1/2 q k^T) (Wv n) + vbias. o.p == nullptr: allocated from the
-// arena, as vt [B][C][Tpad] is. branch: 0 = the flash kernel (C <= 160), 1 = scores materialised once per image
+// attn_block_fwd between its q | k projection and proj_out (16-bit path): qk [B*T][2C] and the normalised rows n [B*T][C] ->
+// o = softmax(D^-1/2 q k^T) (Wv n) + vbias per head, D = C / heads. o.p == nullptr: allocated from the arena, as vt [B][C][Tpad]
+// is. branch: 0 = the flash kernel (D <= 160), 1 = scores materialised once per image (the wide single head of the first stage)
 struct AtCoreOut { Act o; bf16_t* vt = nullptr; int Tpad = 0; int branch = 0; };
-AtCoreOut at_core(Ctx& c, const ConvW& wv, const float* vbias, const Act& qk, const Act& n, int C, Act o = Act());
+AtCoreOut at_core(Ctx& c, const ConvW& wv, const float* vbias, const Act& qk, const Act& n, int C, int heads, Act o = Act());
 // h = proj_in(GroupNorm(x)) [B*T][C]; then qk = [q (log2 units) | k] of LayerNorm1(h) [B*T][2C], vt [B][C][Tpad]
 // (arena-allocated: the caller brackets the second call with the mark its attention releases); st_entry_fwd = both
 Act st_entry_proj_in(Ctx& c, const StEntryW& w, const Act& x, int stages);
@@ -233,12 +277,15 @@ Act upsample2_fwd(Ctx& c, const Act& x);
 Act attention_f32_fwd(Ctx& c, const Act& qk, const Act& v, int H, int D, float scale, const float* obias);
 
 // multi-head attention on token-major activations: q [B][Tq][ldq], k [B][Tk][ldk], v [B][Tk][ldv] (head h at column
-// h*D of each). q_log2: q already carries scale * log2(e) (folded into its projection weights); `scale` is then unused
+// h*D of each). q_log2: q already carries scale * log2(e) (folded into its projection weights); `scale` is then unused.
+// rows >= 0: the output holds all B samples and only the first `rows` are computed (the caller's own launch writes the rest)
 Act attention_fwd(Ctx& c, const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, int B,
-                  int H, int Tq, int Tk, int D, float scale, int Himg, int Wimg, bool q_log2 = false);
-// the same with V pre-transposed: vt [B][H*D][Tpad] (keys contiguous, zero padded to Tpad % 64 == 0)
+                  int H, int Tq, int Tk, int D, float scale, int Himg, int Wimg, bool q_log2 = false, int rows = -1);
+// the same with V pre-transposed: vt [B][H*D][Tpad] (keys contiguous, zero padded to Tpad % 64 == 0). obias [H*D] is added to
+// the output (a value bias); o.p != nullptr: the caller's output rows instead of an arena allocation
 Act attention_vt_fwd(Ctx& c, const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* vt, int B,
-                     int H, int Tq, int Tk, int Tpad, int D, float scale, int Himg, int Wimg, bool q_log2 = false);
+                     int H, int Tq, int Tk, int Tpad, int D, float scale, int Himg, int Wimg, bool q_log2 = false,
+                     const float* obias = nullptr, Act o = Act());
 
 // ------------------------------------------------------------------ networks
 class Net {
@@ -248,6 +295,12 @@ class Net {
   cd_net_desc desc;
   bool f32 = false;  // desc.precision is CD_PREC_F32 or CD_PREC_F32X3
   bool x3 = false;   // desc.precision == CD_PREC_F32X3
+  // the flags above and those of the parameter store, ahead of the first declaration
+  void set_precision(const cd_net_desc& d) {
+    f32 = d.precision == CD_PREC_F32 || d.precision == CD_PREC_F32X3;
+    x3 = d.precision == CD_PREC_F32X3;
+    params.f32 = f32; params.x3 = x3;
+  }
   virtual int kind() const = 0;
 };
 
@@ -300,6 +353,9 @@ struct UNetIO {
   float* out = nullptr;               // fp32 [B*H*W][out_ld]
   int out_ld = 0;
 };
+// sinusoid -> Linear -> SiLU -> Linear, then every ResBlock's SiLU -> Linear in one launch: the fused projection rows
+// [1 or io.B][te.proj_total] fp32 (one row when the samples share the timestep), from the arena
+float* time_emb_fwd(Ctx& c, const TimeEmb& te, const UNetIO& io);
 
 class UNet : public Net {
  public:

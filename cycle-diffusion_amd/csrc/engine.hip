@@ -1,4 +1,5 @@
 // Arena, parameter store and the shared building blocks (conv / norm / attention wrappers).
+#include <limits.h>
 #include <stdlib.h>
 
 #include "engine.h"
@@ -612,12 +613,13 @@ Act layernorm_fwd(Ctx& c, const LNW& w, const Act& x) {
 }
 
 Act attention_fwd(Ctx& c, const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, int B,
-                  int H, int Tq, int Tk, int D, float scale, int Himg, int Wimg, bool q_log2) {
+                  int H, int Tq, int Tk, int D, float scale, int Himg, int Wimg, bool q_log2, int rows) {
   CD_CHECK(!c.f32, "attention: 16-bit kernel called on the fp32 path");
+  CD_CHECK(rows <= B, "attention: %d rows of a batch of %d", rows, B);
   Act o = alloc_act(c, B, Himg, Wimg, H * D);
   AttnParams p;
   p.q = q; p.k = k; p.v = v; p.o = o.p;
-  p.B = B; p.H = H; p.Tq = Tq; p.Tk = Tk; p.D = D;
+  p.B = rows >= 0 ? rows : B; p.H = H; p.Tq = Tq; p.Tk = Tk; p.D = D;
   p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = o.ld;
   p.q_bs = (int64_t)Tq * ldq; p.k_bs = (int64_t)Tk * ldk; p.v_bs = (int64_t)Tk * ldv; p.o_bs = (int64_t)Tq * o.ld;
   p.scale = scale; p.q_log2 = q_log2 ? 1 : 0;
@@ -626,16 +628,17 @@ Act attention_fwd(Ctx& c, const bf16_t* q, int ldq, const bf16_t* k, int ldk, co
 }
 
 Act attention_vt_fwd(Ctx& c, const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* vt, int B,
-                     int H, int Tq, int Tk, int Tpad, int D, float scale, int Himg, int Wimg, bool q_log2) {
+                     int H, int Tq, int Tk, int Tpad, int D, float scale, int Himg, int Wimg, bool q_log2,
+                     const float* obias, Act o) {
   CD_CHECK(!c.f32, "attention: 16-bit kernel called on the fp32 path");
-  Act o = alloc_act(c, B, Himg, Wimg, H * D);
+  if (!o.p) o = alloc_act(c, B, Himg, Wimg, H * D);
   AttnParams p;
   p.q = q; p.k = k; p.vt = vt; p.o = o.p;
   p.B = B; p.H = H; p.Tq = Tq; p.Tk = Tk; p.D = D;
   p.ldq = ldq; p.ldk = ldk; p.ldo = o.ld;
   p.q_bs = (int64_t)Tq * ldq; p.k_bs = (int64_t)Tk * ldk; p.o_bs = (int64_t)Tq * o.ld;
   p.vt_dpad = D; p.vt_tpad = Tpad;
-  p.scale = scale; p.q_log2 = q_log2 ? 1 : 0;
+  p.scale = scale; p.q_log2 = q_log2 ? 1 : 0; p.obias = obias;
   launch_attention(c.st, p);
   return o;
 }
@@ -668,6 +671,159 @@ Act split_rows_f32_fwd(Ctx& c, const Act& x, const Act* x2) {
                         c.overflow);
   y.split = true; y.ld = 2 * C;
   return y;
+}
+
+
+// ------------------------------------------------------------------ blocks shared by the conv nets
+GNW make_gn(ParamStore& ps, const std::string& pfx, int C, float eps) {
+  GNW g; g.C = C; g.eps = eps;
+  g.g = ps.new_vec(C, 1.f); g.b = ps.new_vec(C, 0.f);
+  ps.vec(pfx + ".weight", g.g, C);
+  ps.vec(pfx + ".bias", g.b, C);
+  return g;
+}
+LNW make_ln(ParamStore& ps, const std::string& pfx, int C) {
+  LNW g; g.C = C;
+  g.g = ps.new_vec(C, 1.f); g.b = ps.new_vec(C, 0.f);
+  ps.vec(pfx + ".weight", g.g, C);
+  ps.vec(pfx + ".bias", g.b, C);
+  return g;
+}
+ConvW* make_conv(ParamStore& ps, const std::string& pfx, int N, int Cin, int k, bool bias, bool geglu, int ref_ndim,
+                 float wscale) {
+  CD_CHECK(!(bias && wscale != 1.f), "a folded weight scale needs the bias scaled too");
+  ConvW* c = ps.new_conv(N, Cin, k, k, bias, geglu);
+  ps.conv_weight(pfx + ".weight", c, ref_ndim, wscale);
+  if (bias) ps.conv_bias(pfx + ".bias", c);
+  return c;
+}
+
+Act net_input_act(const void* p, int B, int H, int W, int C, bool f32, bool x3) {
+  Act x; x.p = (bf16_t*)p; x.B = B; x.H = H; x.W = W; x.C = C; x.ld = C; x.f32 = f32;
+  if (x3) { x.split = true; x.ld = 2 * C; }  // the caller hands a split-mode network its input as fp16 pairs
+  return x;
+}
+
+float* time_emb_fwd(Ctx& c, const TimeEmb& te, const UNetIO& io) {
+  const int tB = io.t_shared ? 1 : io.B;
+  float* sinu = (float*)c.arena->alloc((size_t)tB * te.dim * 4);
+  float* e1 = (float*)c.arena->alloc((size_t)tB * te.hidden * 4);
+  float* emb = (float*)c.arena->alloc((size_t)tB * te.hidden * 4);
+  float* proj = (float*)c.arena->alloc((size_t)tB * te.proj_total * 4);
+  launch_timestep_embedding(c.st, io.tab, io.step, io.t_explicit, sinu, tB, te.dim, te.mode);
+  launch_vec_linear(c.st, sinu, te.dim, te.w0, te.b0, e1, te.hidden, tB, te.dim, te.hidden, 0, 1);
+  launch_vec_linear(c.st, e1, te.hidden, te.w1, te.b1, emb, te.hidden, tB, te.hidden, te.hidden, 0, 0);
+  launch_vec_linear(c.st, emb, te.hidden, te.proj_w, te.proj_b, proj, te.proj_total, tB, te.hidden, te.proj_total, 1, 0);
+  return proj;
+}
+
+Act res_fwd(Ctx& c, const ResW& r, const Act& x, const Act* x2, const float* proj, int proj_ld, bool t_shared) {
+  // output first (it outlives the block's temporaries)
+  const int Ho = r.up ? x.H * 2 : (r.down ? x.H / 2 : x.H);
+  const int Wo = r.up ? x.W * 2 : (r.down ? x.W / 2 : x.W);
+  Act out = alloc_act(c, x.B, Ho, Wo, r.cout, /*with_stats=*/true);
+  const int rpv = t_shared ? INT_MAX : Ho * Wo;  // output rows sharing one time-embedding vector
+  const size_t mk = c.arena->mark();
+  Act h = groupnorm_fwd(c, r.gn1, x, x2, /*silu=*/true);
+  Act xs = x;           // skip-path input (identity path needs a single dense tensor)
+  const Act* xs2 = x2;
+  bool up_in_conv = false;
+  if (r.down) {
+    CD_CHECK(!x2, "resblock_updown with concat input is not produced by the reference");
+    h = avgpool2_fwd(c, h);
+    xs = avgpool2_fwd(c, x); xs2 = nullptr;
+  } else if (r.up) {
+    CD_CHECK(!x2, "resblock_updown with concat input is not produced by the reference");
+    up_in_conv = true;
+    xs = upsample2_fwd(c, x); xs2 = nullptr;
+  }
+  CD_CHECK(r.emb_off >= 0 || !r.film, "ResBlock: FiLM without a time-embedding row");
+  ConvOpts o1; o1.up = up_in_conv; o1.want_stats = true;
+  const float* pr = r.emb_off >= 0 ? proj + r.emb_off : nullptr;
+  if (pr && !r.film) { o1.rowvec = pr; o1.rowvec_ld = proj_ld; o1.rows_per_vec = rpv; }
+  Act h2 = conv_fwd(c, *r.conv1, h, nullptr, o1);
+  Act h3;
+  if (r.film) h3 = groupnorm_fwd(c, r.gn2, h2, nullptr, true, pr, t_shared ? 0 : proj_ld);
+  else h3 = groupnorm_fwd(c, r.gn2, h2, nullptr, true);
+  Act skip;
+  if (r.skip) {
+    ConvOpts os; os.pad = 0;
+    // (Round 4 measured the split form of this projection - its unnormalised input, or the concat of two, first written as
+    // fp16 pairs by split_rows_f32_fwd: on config 5 the conversion pass over the 256 x 256 tensors costs more than k_conv_f32
+    // saves - 2.93 -> 2.82 images/s same box, profiles/r4_c5r_split_skip_projection_ab.txt - so it stays on the fp32 matrix
+    // instructions.)
+    skip = conv_fwd(c, *r.skip, xs, xs2, os);
+  } else {
+    CD_CHECK(!xs2, "identity skip with concat input");
+    skip = xs;
+  }
+  ConvOpts o2; o2.resid = &skip; o2.out = out.p; o2.out_ld = out.ld; o2.out_stats = out.stats_buf;
+  conv_fwd(c, *r.conv2, h3, nullptr, o2);
+  out.stats = out.stats_buf;
+  c.arena->release(mk);
+  return out;
+}
+
+AtCoreOut at_core(Ctx& c, const ConvW& wv, const float* vbias, const Act& qk, const Act& n, int C, int heads, Act o) {
+  const int B = n.B, T = n.H * n.W, D = C / heads;
+  AtCoreOut r;
+  const int Tpad = round_up(T, 64);
+  bf16_t* vt = (bf16_t*)c.arena->alloc((size_t)B * C * Tpad * 2);
+  if (Tpad != T) HIP_CHECK(hipMemsetAsync(vt, 0, (size_t)B * C * Tpad * 2, c.st));
+  vt_gemm_fwd(c, wv, n.p, n.ld, B, T, Tpad, vt);
+  const float scale = 1.0f / sqrtf((float)D);  // w_ * int(c)**(-0.5), model.py:192 (one head: D = C)
+  if (!o.p) o = alloc_act(c, B, n.H, n.W, C);
+  if (D <= 160) {
+    attention_vt_fwd(c, qk.p, qk.ld, qk.p + C, qk.ld, vt, B, heads, T, T, Tpad, D, scale, n.H, n.W, /*q_log2=*/false, vbias, o);
+  } else {
+    // wide single head (VAE mid block: 4096 tokens x 512 ch): scores materialised once per image,
+    // S = QK^T and O = PV on the MFMA GEMM kernel, fp32 row softmax in between
+    CD_CHECK(heads == 1, "AttnBlock: heads of %d channels (above 160) are only built for the single-head blocks of the first "
+             "stage and the Ho-DDPM U-Net, got %d heads", D, heads);
+    CD_CHECK(T % 32 == 0, "AttnBlock: token count %d must be a multiple of 32", T);
+    float* S = (float*)c.arena->alloc((size_t)B * T * T * 4);
+    bf16_t* P = (bf16_t*)c.arena->alloc((size_t)B * T * T * 2);
+    ConvGemmParams g;
+    g.src0 = qk.p; g.C0 = C; g.ld0 = qk.ld; g.B = 1; g.Hs = T; g.Ws = 1; g.Hin = T; g.Win = 1;
+    g.Hout = T; g.Wout = 1; g.M = T;
+    g.wgt = qk.p + C; g.Ktot = C; g.ldw = qk.ld; g.N = T;
+    g.nbatch = B; g.a_bs = (int64_t)T * qk.ld; g.w_bs = (int64_t)T * qk.ld; g.o_bs = (int64_t)T * T;
+    g.alpha = scale; g.out = S; g.out_ld = T; g.out_f32 = 1; g.zeros = c.zeros;
+    launch_conv_gemm(c.st, g);
+    launch_softmax_rows(c.st, S, T, P, T, (int64_t)B * T, T);
+    ConvGemmParams h;
+    h.src0 = P; h.C0 = T; h.ld0 = T; h.B = 1; h.Hs = T; h.Ws = 1; h.Hin = T; h.Win = 1;
+    h.Hout = T; h.Wout = 1; h.M = T;
+    h.wgt = vt; h.Ktot = T; h.ldw = Tpad; h.N = C;
+    h.nbatch = B; h.a_bs = (int64_t)T * T; h.w_bs = (int64_t)C * Tpad; h.o_bs = (int64_t)T * o.ld;
+    h.bias = vbias; h.out = o.p; h.out_ld = o.ld; h.zeros = c.zeros;
+    launch_conv_gemm(c.st, h);
+    r.branch = 1;
+  }
+  r.o = o; r.vt = vt; r.Tpad = Tpad;
+  return r;
+}
+
+Act attn_block_fwd(Ctx& c, const AttnW& a, const Act& x) {
+  const int C = a.C, D = C / a.heads;
+  Act out = alloc_act(c, x.B, x.H, x.W, C, /*with_stats=*/true);
+  const size_t mk = c.arena->mark();
+  ConvOpts p0; p0.pad = 0;
+  Act n = groupnorm_fwd(c, a.norm, x, nullptr, false);
+  Act qk = conv_fwd(c, *a.qk, n, nullptr, p0);  // [B*T][2C]
+  ConvOpts po; po.pad = 0; po.resid = &x; po.out = out.p; po.out_ld = out.ld;
+  if (c.f32) {  // fp32 path: V as ordinary tokens, its bias added to the output (rows of P sum to 1)
+    Act v = conv_fwd(c, *a.v, n, nullptr, p0);
+    Act o = attention_f32_fwd(c, qk, v, a.heads, D, 1.0f / sqrtf((float)D), a.vbias);
+    conv_fwd(c, *a.proj, o, nullptr, po);
+  } else {
+    Act o = at_core(c, *a.v, a.vbias, qk, n, C, a.heads).o;
+    po.out_stats = out.stats_buf;
+    conv_fwd(c, *a.proj, o, nullptr, po);
+    out.stats = out.stats_buf;
+  }
+  c.arena->release(mk);
+  return out;
 }
 
 }  // namespace cd

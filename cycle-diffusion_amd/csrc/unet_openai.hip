@@ -4,8 +4,6 @@
 //   * improved-DDPM AFHQ: UNetModel with resblock_updown, FiLM (scale-shift) norm and
 //     QKVAttentionLegacy (model/lib/ddpm_ddim/models/improved_ddpm/unet.py:401-668)
 // Parameter names are the reference's state_dict keys.
-#include <limits.h>
-
 #include <algorithm>
 
 #include "engine.h"
@@ -13,14 +11,6 @@
 namespace cd {
 
 namespace {
-
-struct ResW {
-  int cin = 0, cout = 0;
-  bool up = false, down = false, film = false;
-  GNW gn1, gn2;
-  ConvW *conv1 = nullptr, *conv2 = nullptr, *skip = nullptr;
-  int emb_off = 0;
-};
 
 struct STW {  // SpatialTransformer with one BasicTransformerBlock
   int C = 0, heads = 0, dh = 0, ctx = 0;
@@ -43,13 +33,6 @@ struct STW {  // SpatialTransformer with one BasicTransformerBlock
   // context cache (step invariant)
   bf16_t* k2c = nullptr;  // [B*L][C]
   bf16_t* v2c = nullptr;  // [B*L][C] (token-major: k_attention transposes V tiles with LDS transpose reads)
-};
-
-struct ABW {  // AttentionBlock (improved_ddpm/unet.py:268-315)
-  int C = 0, heads = 0, dh = 0;
-  GNW norm;
-  ConvW *qk = nullptr, *v = nullptr, *proj = nullptr;
-  float* vbias = nullptr;
 };
 
 struct Layer {
@@ -75,7 +58,7 @@ class UNetOpenAI : public UNet {
   TimeEmb te_;
   std::vector<ResW> res_;
   std::vector<STW> st_;
-  std::vector<ABW> ab_;
+  std::vector<AttnW> ab_;
   std::vector<Block> in_blocks_, out_blocks_;
   Block mid_;
   GNW out_norm_;
@@ -91,41 +74,15 @@ class UNetOpenAI : public UNet {
   int folded_version_ = -1;
   void refresh_ln_folds(Ctx& c);
   Act run_block(Ctx& c, const Block& b, Act h, const Act* skip, const float* proj, int proj_ld, bool t_shared);
-  Act res_fwd(Ctx& c, const ResW& r, const Act& x, const Act* x2, const float* proj, int proj_ld, bool t_shared);
   // dup_tail > 0: x holds the UNIQUE rows of a batch whose last dup_tail samples repeat the dup_tail samples ahead of them
   // (UNetIO::dup_tail; a classifier-free-guidance batch is dup_tail = x.B); everything ahead of the cross-attention runs on
   // x, then the token stream and the block input get the repeated samples appended and the rest runs on x.B + dup_tail
   Act st_fwd(Ctx& c, STW& s, const Act& x, int dup_tail = 0);
   // the 16-bit path of the block, into the caller's output rows
   void st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x_resid, Act& out, int dup_tail);
-  Act ab_fwd(Ctx& c, const ABW& a, const Act& x);
  public:
   ~UNetOpenAI() override { for (void* p : ctx_allocs_) (void)hipFree(p); }
 };
-
-GNW make_gn(ParamStore& ps, const std::string& pfx, int C, float eps) {
-  GNW g; g.C = C; g.eps = eps;
-  g.g = ps.new_vec(C, 1.f); g.b = ps.new_vec(C, 0.f);
-  ps.vec(pfx + ".weight", g.g, C);
-  ps.vec(pfx + ".bias", g.b, C);
-  return g;
-}
-LNW make_ln(ParamStore& ps, const std::string& pfx, int C) {
-  LNW g; g.C = C;
-  g.g = ps.new_vec(C, 1.f); g.b = ps.new_vec(C, 0.f);
-  ps.vec(pfx + ".weight", g.g, C);
-  ps.vec(pfx + ".bias", g.b, C);
-  return g;
-}
-// ref_ndim: rank of the reference weight tensor (2 = nn.Linear, 3 = Conv1d, 4 = Conv2d)
-ConvW* make_conv(ParamStore& ps, const std::string& pfx, int N, int Cin, int k, bool bias, bool geglu = false,
-                 int ref_ndim = 4, float wscale = 1.f) {
-  CD_CHECK(!(bias && wscale != 1.f), "a folded weight scale needs the bias scaled too");
-  ConvW* c = ps.new_conv(N, Cin, k, k, bias, geglu);
-  ps.conv_weight(pfx + ".weight", c, ref_ndim, wscale);
-  if (bias) ps.conv_bias(pfx + ".bias", c);
-  return c;
-}
 
 int UNetOpenAI::add_res(const std::string& pfx, int cin, int cout, bool up, bool down) {
   ResW r; r.cin = cin; r.cout = cout; r.up = up; r.down = down; r.film = desc.use_scale_shift_norm != 0;
@@ -188,9 +145,9 @@ int UNetOpenAI::add_st(const std::string& pfx, int C, int heads, int dh) {
 }
 
 int UNetOpenAI::add_ab(const std::string& pfx, int C, int heads) {
-  ABW a; a.C = C; a.heads = heads; a.dh = C / heads;
+  AttnW a; a.C = C; a.heads = heads;  // AttentionBlock (improved_ddpm/unet.py:268-315)
   a.norm = make_gn(params, pfx + ".norm", C, 1e-5f);
-  const int ch = a.dh;
+  const int ch = C / heads;
   // legacy layout: qkv rows are [head][q(ch) | k(ch) | v(ch)] (QKVAttentionLegacy, unet.py:333-336)
   a.qk = params.new_conv(2 * C, C, 1, 1, true);
   a.v = params.new_conv(C, C, 1, 1, false);
@@ -209,9 +166,7 @@ int UNetOpenAI::add_ab(const std::string& pfx, int C, int heads) {
 
 UNetOpenAI::UNetOpenAI(const cd_net_desc& d) {
   desc = d;
-  f32 = d.precision == CD_PREC_F32 || d.precision == CD_PREC_F32X3;
-  x3 = d.precision == CD_PREC_F32X3;
-  params.f32 = f32; params.x3 = x3;
+  set_precision(d);
 
   mc_ = d.model_channels; hidden_ = 4 * mc_;
   image_size = d.image_size; out_channels = d.out_channels;
@@ -328,53 +283,6 @@ size_t UNetOpenAI::workspace_hint(int B) const {
   return (size_t)B * hw * std::max(widest, (size_t)8 * mc_) * 2 * 24 + (64u << 20);
 }
 
-Act UNetOpenAI::res_fwd(Ctx& c, const ResW& r, const Act& x, const Act* x2, const float* proj, int proj_ld,
-                        bool t_shared) {
-  // output first (it outlives the block's temporaries)
-  const int Ho = r.up ? x.H * 2 : (r.down ? x.H / 2 : x.H);
-  const int Wo = r.up ? x.W * 2 : (r.down ? x.W / 2 : x.W);
-  Act out = alloc_act(c, x.B, Ho, Wo, r.cout, /*with_stats=*/true);
-  const int rpv = t_shared ? INT_MAX : Ho * Wo;  // output rows sharing one time-embedding vector
-  const size_t mk = c.arena->mark();
-  Act h = groupnorm_fwd(c, r.gn1, x, x2, /*silu=*/true);
-  Act xs = x;           // skip-path input (identity path needs a single dense tensor)
-  const Act* xs2 = x2;
-  bool up_in_conv = false;
-  if (r.down) {
-    CD_CHECK(!x2, "resblock_updown with concat input is not produced by the reference");
-    h = avgpool2_fwd(c, h);
-    xs = avgpool2_fwd(c, x); xs2 = nullptr;
-  } else if (r.up) {
-    CD_CHECK(!x2, "resblock_updown with concat input is not produced by the reference");
-    up_in_conv = true;
-    xs = upsample2_fwd(c, x); xs2 = nullptr;
-  }
-  ConvOpts o1; o1.up = up_in_conv; o1.want_stats = true;
-  const float* pr = proj + r.emb_off;
-  if (!r.film) { o1.rowvec = pr; o1.rowvec_ld = proj_ld; o1.rows_per_vec = rpv; }
-  Act h2 = conv_fwd(c, *r.conv1, h, nullptr, o1);
-  Act h3;
-  if (r.film) h3 = groupnorm_fwd(c, r.gn2, h2, nullptr, true, pr, t_shared ? 0 : proj_ld);
-  else h3 = groupnorm_fwd(c, r.gn2, h2, nullptr, true);
-  Act skip;
-  if (r.skip) {
-    ConvOpts os; os.pad = 0;
-    // (Round 4 measured the split form of this projection - its unnormalised input, or the concat of two, first written as
-    // fp16 pairs by split_rows_f32_fwd: on config 5 the conversion pass over the 256 x 256 tensors costs more than k_conv_f32
-    // saves - 2.93 -> 2.82 images/s same box, profiles/r4_c5r_split_skip_projection_ab.txt - so it stays on the fp32 matrix
-    // instructions.)
-    skip = conv_fwd(c, *r.skip, xs, xs2, os);
-  } else {
-    CD_CHECK(!xs2, "identity skip with concat input");
-    skip = xs;
-  }
-  ConvOpts o2; o2.resid = &skip; o2.out = out.p; o2.out_ld = out.ld; o2.out_stats = out.stats_buf;
-  conv_fwd(c, *r.conv2, h3, nullptr, o2);
-  out.stats = out.stats_buf;
-  c.arena->release(mk);
-  return out;
-}
-
 void UNetOpenAI::set_context(Ctx& c, const bf16_t* ctx, int B, int L) {
   if (st_.empty()) return;
   if (B != ctx_B_ || L != ctx_L_) {
@@ -388,8 +296,7 @@ void UNetOpenAI::set_context(Ctx& c, const bf16_t* ctx, int B, int L) {
     }
     ctx_B_ = B; ctx_L_ = L;
   }
-  const bool keep_f32 = c.f32, keep_x3 = c.x3;
-  c.f32 = f32; c.x3 = x3;  // (forward() sets these for its own duration; the context projections run outside it)
+  PrecisionScope prec(c, f32, x3);  // (forward() sets these for its own duration; the context projections run outside it)
   Act cx; cx.p = (bf16_t*)ctx; cx.B = 1; cx.H = B * L; cx.W = 1; cx.C = st_[0].ctx; cx.ld = cx.C; cx.f32 = f32;
   for (auto& s : st_) {
     ConvOpts o; o.pad = 0; o.out = s.k2c; o.out_ld = s.C;
@@ -397,7 +304,6 @@ void UNetOpenAI::set_context(Ctx& c, const bf16_t* ctx, int B, int L) {
     o.out = s.v2c;
     conv_fwd(c, *s.v2, cx, nullptr, o);
   }
-  c.f32 = keep_f32; c.x3 = keep_x3;
 }
 
 void UNetOpenAI::build_attn_control(Ctx& c, const float* mapper, const float* alpha, const float* weight, int B_ctrl,
@@ -587,21 +493,16 @@ void UNetOpenAI::st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x, Act& o
       CD_CHECK(Bu + ctrl_->rows == B, "cross-attention control: rows %d + %d of a batch of %d", Bu, ctrl_->rows, B);
       const size_t bi = (size_t)(&s - st_.data());
       CD_CHECK(bi < ctrl_->va.size(), "cross-attention control: no values for transformer block %d", (int)bi);
-      a = alloc_act(c, B, x.H, x.W, C);
-      AttnParams pu;
-      pu.q = q.p; pu.k = s.k2c; pu.v = s.v2c; pu.o = a.p;
-      pu.B = Bu; pu.H = s.heads; pu.Tq = T; pu.Tk = ctx_L_; pu.D = s.dh;
-      pu.ldq = q.ld; pu.ldk = C; pu.ldv = C; pu.ldo = a.ld;
-      pu.q_bs = (int64_t)T * q.ld; pu.k_bs = (int64_t)ctx_L_ * C; pu.v_bs = (int64_t)ctx_L_ * C; pu.o_bs = (int64_t)T * a.ld;
-      pu.scale = scale; pu.q_log2 = 1;
-      launch_attention(c.st, pu);
+      a = attention_fwd(c, q.p, q.ld, s.k2c, C, s.v2c, C, B, s.heads, T, ctx_L_, s.dh, scale, x.H, x.W, /*q_log2=*/true,
+                        /*rows=*/Bu);
+      const int64_t q_bs = (int64_t)T * q.ld, k_bs = (int64_t)ctx_L_ * C, o_bs = (int64_t)T * a.ld;
       CtrlAttnParams p;
-      p.q_own = q.p + (int64_t)Bu * pu.q_bs; p.q_src = q.p + (int64_t)ctrl_->src_b0 * pu.q_bs;
-      p.k_own = s.k2c + (int64_t)Bu * pu.k_bs; p.k_src = s.k2c + (int64_t)ctrl_->src_b0 * pu.k_bs;
-      p.va = ctrl_->va[bi]; p.vb = ctrl_->vb[bi]; p.o = a.p + (int64_t)Bu * pu.o_bs;
+      p.q_own = q.p + (int64_t)Bu * q_bs; p.q_src = q.p + (int64_t)ctrl_->src_b0 * q_bs;
+      p.k_own = s.k2c + (int64_t)Bu * k_bs; p.k_src = s.k2c + (int64_t)ctrl_->src_b0 * k_bs;
+      p.va = ctrl_->va[bi]; p.vb = ctrl_->vb[bi]; p.o = a.p + (int64_t)Bu * o_bs;
       p.B = ctrl_->rows; p.B_src = ctrl_->B_src; p.H = s.heads; p.Tq = T; p.L = ctx_L_; p.D = s.dh;
       p.ldq = q.ld; p.ldk = C; p.ldv = C; p.ldo = a.ld;
-      p.q_bs = pu.q_bs; p.k_bs = pu.k_bs; p.v_bs = pu.v_bs; p.o_bs = pu.o_bs;
+      p.q_bs = q_bs; p.k_bs = k_bs; p.v_bs = k_bs; p.o_bs = o_bs;
       p.scale = scale; p.q_log2 = 1;
       launch_cross_attention_ctrl(c.st, p);
     }
@@ -643,40 +544,6 @@ void UNetOpenAI::st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x, Act& o
   c.arena->release(mk);
 }
 
-Act UNetOpenAI::ab_fwd(Ctx& c, const ABW& a, const Act& x) {
-  const int B = x.B, T = x.H * x.W, C = a.C;
-  Act out = alloc_act(c, B, x.H, x.W, C, /*with_stats=*/true);
-  const size_t mk = c.arena->mark();
-  ConvOpts p0; p0.pad = 0;
-  Act n = groupnorm_fwd(c, a.norm, x, nullptr, false);
-  Act qk = conv_fwd(c, *a.qk, n, nullptr, p0);
-  if (c.f32) {  // fp32 path: V as ordinary tokens, its bias added to the output (rows of P sum to 1)
-    Act v = conv_fwd(c, *a.v, n, nullptr, p0);
-    Act o = attention_f32_fwd(c, qk, v, a.heads, a.dh, 1.0f / sqrtf((float)a.dh), a.vbias);
-    ConvOpts po; po.pad = 0; po.resid = &x; po.out = out.p; po.out_ld = out.ld;
-    conv_fwd(c, *a.proj, o, nullptr, po);
-    c.arena->release(mk);
-    return out;
-  }
-  const int Tpad = round_up(T, 64);
-  bf16_t* vt = (bf16_t*)c.arena->alloc((size_t)B * C * Tpad * 2);
-  if (Tpad != T) HIP_CHECK(hipMemsetAsync(vt, 0, (size_t)B * C * Tpad * 2, c.st));
-  vt_gemm_fwd(c, *a.v, n.p, n.ld, B, T, Tpad, vt);
-  Act o = alloc_act(c, B, x.H, x.W, C);
-  AttnParams p;
-  p.q = qk.p; p.k = qk.p + C; p.vt = vt; p.o = o.p;
-  p.B = B; p.H = a.heads; p.Tq = T; p.Tk = T; p.D = a.dh;
-  p.ldq = qk.ld; p.ldk = qk.ld; p.ldo = o.ld;
-  p.q_bs = (int64_t)T * qk.ld; p.k_bs = (int64_t)T * qk.ld; p.o_bs = (int64_t)T * o.ld;
-  p.vt_dpad = a.dh; p.vt_tpad = Tpad; p.scale = 1.0f / sqrtf((float)a.dh); p.obias = a.vbias;
-  launch_attention(c.st, p);
-  ConvOpts po; po.pad = 0; po.resid = &x; po.out = out.p; po.out_ld = out.ld; po.out_stats = out.stats_buf;
-  conv_fwd(c, *a.proj, o, nullptr, po);
-  out.stats = out.stats_buf;
-  c.arena->release(mk);
-  return out;
-}
-
 Act UNetOpenAI::run_block(Ctx& c, const Block& b, Act h, const Act* skip, const float* proj, int proj_ld,
                           bool t_shared) {
   bool first = true;
@@ -686,7 +553,7 @@ Act UNetOpenAI::run_block(Ctx& c, const Block& b, Act h, const Act* skip, const 
       case Layer::CONV_IN: { ConvOpts o; o.want_stats = true; h = conv_fwd(c, *l.conv, h, nullptr, o); break; }
       case Layer::RES: h = res_fwd(c, res_[l.idx], h, x2, proj, proj_ld, t_shared); break;
       case Layer::ST: h = st_fwd(c, st_[l.idx], h); break;
-      case Layer::AB: h = ab_fwd(c, ab_[l.idx], h); break;
+      case Layer::AB: h = attn_block_fwd(c, ab_[l.idx], h); break;
       case Layer::DOWN_CONV: { ConvOpts o; o.stride = 2; o.want_stats = true; h = conv_fwd(c, *l.conv, h, nullptr, o); break; }
       case Layer::UP_CONV: { ConvOpts o; o.up = true; o.want_stats = true; h = conv_fwd(c, *l.conv, h, nullptr, o); break; }
     }
@@ -718,7 +585,7 @@ void UNetOpenAI::refresh_ln_folds(Ctx& c) {
 
 void UNetOpenAI::forward(Ctx& c, const UNetIO& io) {
   const size_t mk0 = c.arena->mark();
-  c.f32 = f32; c.x3 = x3;
+  PrecisionScope prec(c, f32, x3);
   refresh_ln_folds(c);
   CD_CHECK(!io.ctrl || (!f32 && io.ctrl->va.size() == st_.size()), "U-Net: cross-attention control on a network it was not built for");
   CD_CHECK(!io.maps || !f32, "U-Net: per-word attention maps are not built for fp32 / fp32x3 networks (their transformer blocks "
@@ -731,19 +598,9 @@ void UNetOpenAI::forward(Ctx& c, const UNetIO& io) {
   const int B = io.B, R = image_size;
   // ---- time embedding: sinusoid -> Linear -> SiLU -> Linear, then every ResBlock's
   //      emb_layers (SiLU -> Linear) in one launch (openaimodel.py:506-511,723-724,263)
-  const int tB = io.t_shared ? 1 : B;
-  float* sinu = (float*)c.arena->alloc((size_t)tB * mc_ * 4);
-  float* e1 = (float*)c.arena->alloc((size_t)tB * hidden_ * 4);
-  float* emb = (float*)c.arena->alloc((size_t)tB * hidden_ * 4);
-  float* proj = (float*)c.arena->alloc((size_t)tB * te_.proj_total * 4);
-  launch_timestep_embedding(c.st, io.tab, io.step, io.t_explicit, sinu, tB, mc_, 0);
-  launch_vec_linear(c.st, sinu, mc_, te_.w0, te_.b0, e1, hidden_, tB, mc_, hidden_, 0, 1);
-  launch_vec_linear(c.st, e1, hidden_, te_.w1, te_.b1, emb, hidden_, tB, hidden_, hidden_, 0, 0);
-  launch_vec_linear(c.st, emb, hidden_, te_.proj_w, te_.proj_b, proj, te_.proj_total, tB, hidden_,
-                    te_.proj_total, 1, 0);
+  const float* proj = time_emb_fwd(c, te_, io);
   const int proj_ld = te_.proj_total;
-  Act x; x.p = (bf16_t*)io.xin; x.B = B; x.H = R; x.W = R; x.C = in_cpad; x.ld = in_cpad; x.f32 = f32;
-  if (x3) { x.split = true; x.ld = 2 * in_cpad; }  // the samplers hand CD_PREC_F32X3 networks their input as fp16 pairs
+  const Act x = net_input_act(io.xin, B, R, R, in_cpad, f32, x3);
   std::vector<Act> hs;
   Act h = x;
   size_t first_full = 0;  // first input block that runs at the full batch
@@ -790,7 +647,6 @@ void UNetOpenAI::forward(Ctx& c, const UNetIO& io) {
   ConvOpts oo; oo.out_f32 = true; oo.out = io.out; oo.out_ld = io.out_ld;
   conv_fwd(c, *out_conv_, hn, nullptr, oo);
   c.arena->release(mk0);
-  c.f32 = false; c.x3 = false;
   ctrl_ = nullptr;
   maps_ = nullptr;
 }

@@ -1,5 +1,5 @@
 """The implicit-GEMM kernel (csrc/conv_gemm.hip k_conv_gemm) as the batched plain GEMM the attention call sites launch, the
-AttnBlock core (csrc/nets_ho_vae.hip at_core) and k_softmax_rows: case tables, seeded operands, float64 references, fp32
+AttnBlock core (csrc/engine.hip at_core, one head) and k_softmax_rows: case tables, seeded operands, float64 references, fp32
 emulations and their mutants for tests/test_gemm_batched_host.py (CPU) and tests/test_gpu_gemm_batched.py (GPU, through
 cd_op_gemm_batched / cd_op_attn_block_core: the caller's device bytes in, the kernel's bytes out).
 
@@ -11,7 +11,7 @@ S[z] = alpha Q K^T   at_core, C > 160: both operands in    s/c192_t96 (ragged M 
                      one [B T][ld] tensor, fp32 output     s/c512_t256; x/split2 (16-bit output, zb-indexed split-K workspace)
 O[z] = P V + vbias   at_core, C > 160: K = T, ldw = Tpad   o/t96_c192 (ldw != Ktot, NaN in the V^T padding, ldo = C + 8),
                                                            o/t256_c512; x/resid_stats (residual and statistics per batch)
-at_core              nets_ho_vae.hip                       core/flash_c128_t100, core/wide_c192_t96, core/wide_c192_t64,
+at_core              engine.hip (attn_block_fwd)           core/flash_c128_t100, core/wide_c192_t96, core/wide_c192_t64,
                                                            core/wide_c320_t160, core/wide_c512_t256; refusal T = 100, C = 192
 k_softmax_rows       norm.hip                              sm/r5_c96, sm/r3_c64, sm/r2_c4096, sm/spike_r4_c300, sm/const_r2_c96
 

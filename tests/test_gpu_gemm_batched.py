@@ -110,7 +110,7 @@ def test_attn_block_core(engine, report, name):
         # the chain on the same operands: S = alpha q k^T (fp32) -> softmax rows -> P (16 bits, exact) -> P V^T^T + vbias
         qk = o["qk"].cuda()
         S = torch.empty((B, T, T), device="cuda", dtype=torch.float32)
-        alpha = float(np.float32(1.0) / np.sqrt(np.float32(Cc)))  # at_core's 1.0f / sqrtf((float)C)
+        alpha = float(np.float32(1.0) / np.sqrt(np.float32(Cc)))  # at_core's 1.0f / sqrtf((float)D), D = C with one head
         _ops.gemm_raw(engine, qk, c["ldqk"], T * c["ldqk"], _ops._at(qk, Cc), c["ldqk"], T * c["ldqk"], T, T, Cc, B, alpha,
                       None, S, T, 1)
         Pf = _ops.softmax_rows_dev(engine, S.view(B * T, T))
