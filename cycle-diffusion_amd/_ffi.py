@@ -81,6 +81,8 @@ SIGNATURES = {
                                   _VP, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP],
     "cd_cycle_translate_ctrl": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I,
                                 _VP, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP, _VP, _I, _I, _VP, _VP],
+    "cd_cycle_translate_blend": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I,
+                                 _VP, _VP, _VP, _I, _I, _VP, _VP, _I, _I, _I, _F, _I, _VP, _VP, _VP, _VP],
     "cd_ilvr_decode": [_VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _U64, _VP, _I, _I, _I, _VP, _VP, _U64, _VP],
     "cd_automask": [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _F, _F, _VP, _U64, _I, _F, _F, _I, _VP, _VP],
     "cd_word_maps": [_VP, _I, _VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _F, _F, _VP, _U64, _I, _I, _I, _VP, C.POINTER(_I)],
@@ -115,6 +117,7 @@ SIGNATURES = {
     "cd_op_sched_step": [_VP, _I, _I, _VP, _VP, _VP, _VP, _I, _F, _VP, _VP, _I, _I, _I, _I, _VP],
     "cd_op_gauss": [_VP, _U64, C.c_uint32, _I64, _I64, _VP],
     "cd_op_automask_reduce": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _F, _I, _VP, _VP, _VP],
+    "cd_op_local_blend_mask": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _VP],
     "cd_op_sched_step_masked": [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, _VP, _VP, _I, _I, _F, _F, _VP, _I, _I, _I, _I, _VP, _I],
     "cd_op_layout": [_VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _F, _F, _I],
     "cd_op_resample16": [_VP, _I, _VP, _VP, _I, _I, _I, _I],

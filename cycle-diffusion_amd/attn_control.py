@@ -160,3 +160,53 @@ def blend_mask(maps, threshold=0.3, pool=3, factor=1):
     m = torch.where(mx > 0, m / mx.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(m))
     keep = 1.0 - (m > threshold).float()
     return keep.repeat_interleave(int(factor), 2).repeat_interleave(int(factor), 3).contiguous()
+
+
+# ------------------------------------------------------------------------------------------------ local blend
+LOCAL_BLEND_MODES = ("none", "words")
+
+
+def local_blend_selectors(src_ids, tgt_ids, eos_id=CLIP_EOS, words=None):
+    """The selectors of cd_cycle_translate_blend for one sample: (sel_src [L], sel_tgt [L]) float32. Without `words`:
+    edited_selector both ways - the target positions not paired with an equal source token, and the source positions not
+    paired with an equal target token; a side that has none (an insertion leaves the source without one, identical prompts
+    leave both) is all zero, and an all-zero map edits nothing. words = (src_words, tgt_words): token-id sequences marked by
+    word_selector in their own prompt (an empty list: zero), their rows summed."""
+    s, t = np.asarray(src_ids), np.asarray(tgt_ids)
+    if s.ndim != 1 or s.shape != t.shape:
+        raise ValueError("src_ids and tgt_ids must both be one id row [L], got %s and %s" % (s.shape, t.shape))
+    if words is not None:
+        out = []
+        for row, ws in ((s, words[0]), (t, words[1])):
+            ws = list(ws)
+            out.append(np.minimum(word_selector(row, ws, eos_id).sum(0), 1.0).astype(np.float32) if ws
+                       else np.zeros(len(row), dtype=np.float32))
+        return out[0], out[1]
+
+    def one(a, b):  # the positions of b that a does not explain
+        try:
+            return edited_selector(a, b, eos_id)[0]
+        except ValueError:
+            return np.zeros(len(b), dtype=np.float32)
+
+    return one(t, s), one(s, t)
+
+
+def local_blend_start(fraction, K):
+    """n_start of a member that runs K decode steps: the blend begins after the first int(fraction * K) iterations"""
+    if not 0.0 <= float(fraction) <= 1.0:
+        raise ValueError("local_blend_start must lie in [0, 1] (the unblended fraction of the decode steps), got %r" % (fraction,))
+    return int(float(fraction) * int(K))
+
+
+LOCAL_BLEND_KEYS = ("local_blend", "local_blend_threshold", "local_blend_pool", "local_blend_side", "local_blend_start")
+
+
+def refuse_local_blend(kw, who):
+    """wrappers without the coupled text loop refuse the local blend's keys by name (removed from `kw` either way)"""
+    got = {k: kw.pop(k) for k in LOCAL_BLEND_KEYS if k in kw}
+    given = sorted(k for k, v in got.items() if v is not None and not (k == "local_blend" and str(v) == "none"))
+    if given:
+        raise ValueError("%s does not use %s: the local blend needs the source rows of the coupled translate loop of the latent "
+                         "text wrappers (SDStochasticText / LatentDiffStochasticText); remove %s from the [gan] section"
+                         % (who, ", ".join(given), "it" if len(given) == 1 else "them"))

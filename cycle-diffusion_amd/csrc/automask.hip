@@ -13,6 +13,8 @@
 // The per-word attention maps reuse k_automask_qsample and keep their two sums here, in the same arithmetic:
 //   k_word_map_accumulate  one included layer of a forward into that forward's per-row sums, nearest replication to the latent grid
 //   k_word_map_fold        the draws of a forward into the call's sums, ascending; the scale after the last forward
+// and the local blend of the coupled loop turns two such running sums into a keep-mask once per step:
+//   k_local_blend_mask     pool, image maximum, threshold and union of a decoder row's source and target map
 #include "common.h"
 #include "gauss.h"
 #include "kernels.h"
@@ -177,6 +179,60 @@ __global__ void __launch_bounds__(kThreads) k_word_map_fold(WordMapFold a) {
   }
 }
 
+// ---- prompt-to-prompt local blend: the keep-mask of one decoder row per workgroup. Both running sums of the
+// row are staged in LDS, the (pool x pool) maximum reads them from there, the image maximum is a wave reduction followed by
+// one over the waves (max does not depend on the order), and the 0 / 1 cells leave as f x f replicated stores, a row of the
+// output per pass of the workgroup. The pool is computed twice - ahead of the maximum and for the compare - rather than kept.
+__device__ inline float pooled_max(const float* m, int s, int y, int x, int r) {
+  const int y0 = y - r < 0 ? 0 : y - r, y1 = y + r > s - 1 ? s - 1 : y + r;
+  const int x0 = x - r < 0 ? 0 : x - r, x1 = x + r > s - 1 ? s - 1 : x + r;
+  float p = m[y0 * s + x0];
+  for (int yy = y0; yy <= y1; ++yy)
+    for (int xx = x0; xx <= x1; ++xx) p = fmaxf(p, m[yy * s + xx]);
+  return p;
+}
+
+__global__ void __launch_bounds__(kThreads) k_local_blend_mask(LocalBlendMask a) {
+  __shared__ float maps[2][kBlendMaxSide * kBlendMaxSide];
+  __shared__ unsigned char edit[kBlendMaxSide * kBlendMaxSide];
+  __shared__ float wmax[2][kThreads / 64];
+  const int r = blockIdx.x, tid = threadIdx.x, s = a.side, n = s * s, rad = a.pool / 2;
+  const float* src = a.acc_src + (int64_t)(r % a.B) * n;
+  const float* tgt = a.acc_tgt + (int64_t)r * n;
+  for (int i = tid; i < n; i += kThreads) {
+    maps[0][i] = src[i];
+    maps[1][i] = tgt[i];
+  }
+  __syncthreads();
+  float m0 = 0.f, m1 = 0.f;  // the sums are of softmax mass times weights; a map that is nowhere above 0 edits nowhere
+  for (int i = tid; i < n; i += kThreads) {
+    const int y = i / s, x = i - y * s;
+    m0 = fmaxf(m0, pooled_max(maps[0], s, y, x, rad));
+    m1 = fmaxf(m1, pooled_max(maps[1], s, y, x, rad));
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    m0 = fmaxf(m0, __shfl_xor(m0, o, 64));
+    m1 = fmaxf(m1, __shfl_xor(m1, o, 64));
+  }
+  if ((tid & 63) == 0) { wmax[0][tid >> 6] = m0; wmax[1][tid >> 6] = m1; }
+  __syncthreads();
+  float mx0 = wmax[0][0], mx1 = wmax[1][0];
+  for (int w = 1; w < kThreads / 64; ++w) { mx0 = fmaxf(mx0, wmax[0][w]); mx1 = fmaxf(mx1, wmax[1][w]); }
+  for (int i = tid; i < n; i += kThreads) {
+    const int y = i / s, x = i - y * s;
+    const bool e0 = mx0 > 0.f && pooled_max(maps[0], s, y, x, rad) / mx0 > a.thr;
+    const bool e1 = mx1 > 0.f && pooled_max(maps[1], s, y, x, rad) / mx1 > a.thr;
+    edit[i] = (e0 || e1) ? 1 : 0;
+  }
+  __syncthreads();
+  const int w = s * a.f, hw = w * w;
+  float* keep = a.keep + (int64_t)r * hw;
+  for (int o = tid; o < hw; o += kThreads) {
+    const int y = o / w, x = o - y * w;
+    keep[o] = edit[(y / a.f) * s + x / a.f] ? 0.f : 1.f;
+  }
+}
+
 bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 void check_automask(const AutoMaskArgs& a) {
@@ -217,6 +273,15 @@ void launch_word_map_accumulate(hipStream_t st, const WordMapAccum& a) {
   CD_CHECK(a.h % a.s == 0, "word maps: a %d x %d token grid does not divide the %d x %d latent", a.s, a.s, a.h, a.w);
   const int64_t nb = ((int64_t)a.rows * a.N * a.h * a.w + kThreads - 1) / kThreads;
   hipLaunchKernelGGL(k_word_map_accumulate, dim3((unsigned)(nb > 2048 ? 2048 : nb)), dim3(kThreads), 0, st, a);
+}
+
+void launch_local_blend_mask(hipStream_t st, const LocalBlendMask& a) {
+  CD_CHECK(a.acc_src && a.acc_tgt && a.keep && a.B > 0 && a.Bd > 0 && a.Bd % a.B == 0, "local blend: empty mask launch");
+  CD_CHECK(a.side > 0 && a.side <= kBlendMaxSide && a.f > 0 && (int64_t)a.side * a.f <= 32768,
+           "local blend: a %d x %d map (at most %d) replicated %d times", a.side, a.side, kBlendMaxSide, a.f);
+  CD_CHECK(a.pool >= 1 && a.pool <= kBlendMaxPool && a.pool % 2 == 1, "local blend: pool = %d is not an odd number in [1, %d]",
+           a.pool, kBlendMaxPool);
+  hipLaunchKernelGGL(k_local_blend_mask, dim3(a.Bd), dim3(kThreads), 0, st, a);
 }
 
 void launch_word_map_fold(hipStream_t st, const WordMapFold& a) {

@@ -1,6 +1,7 @@
 // extern "C" boundary (include/cyclediff.h): engine lifetime, weight loading, the network forwards and the sampler loops
 // (DPM-Encoder / coupled decode). The cd_op_* entry points of the parity tests are in capi_ops.hip.
 #include <algorithm>
+#include <cmath>
 
 #include "capi_internal.h"
 
@@ -312,6 +313,16 @@ struct CtrlArgs {
   const float* alpha = nullptr;   // [B_ctrl, L]
   const float* weight = nullptr;  // [B_ctrl, L]
   int B_ctrl = 0, n_ctrl = 0;
+};
+
+// Arguments of the local blend (cd_cycle_translate_blend), checked on the host before any launch
+struct BlendArgs {
+  const float* sel_src = nullptr;  // [B_sel, L]
+  const float* sel_tgt = nullptr;  // [B_sel, L]
+  int B_sel = 0, side = 0, pool = 0, n_start = 0;
+  float thr = 0.f;
+  float* acc_out = nullptr;   // [B + n_dec * B, side, side] or NULL
+  float* keep_out = nullptr;  // [n_dec * B, 1, h, w] or NULL
 };
 
 struct SamplerState {
@@ -656,7 +667,7 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
                        float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
                        const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
                        uint64_t seed, int last_uses_x0, float* z_out, float* x_out, const MaskArgs* mk,
-                       const CtrlArgs* ck = nullptr) {
+                       const CtrlArgs* ck = nullptr, const BlendArgs* bk = nullptr) {
   CD_CHECK(h && x0 && coef_enc_host && coef_dec_host && z_out && x_out && B > 0 && n_dec > 0 && K > 0, "bad argument");
   check_stream_band(noise, K, "cd_cycle_translate: noise");
   if (mk && mk->source == CD_MASK_QSAMPLE) check_stream_band(mk->noise, K, "keep-mask: mask_noise");
@@ -665,21 +676,45 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
   const int Bd = B * n_dec;
   if (mk) check_mask_args(*mk, u, sched_kind, B, /*coupled=*/true);
   const bool ctrl_on = ck && ck->n_ctrl != 0;
-  if (ck) {
+  CD_CHECK(!(mk && bk), "cd_cycle_translate_blend: a static keep-mask and the local blend exclude each other (the blend "
+                        "rewrites the mask after every step)");
+  // what the control and the local blend both need of the call; the blend needs it for every n_ctrl
+  const bool text_on = ctrl_on || bk;
+  const char* what = ctrl_on ? "cross-attention control" : "the local blend";
+  if (ck || bk) {
     // one forward serves both passes at the timestep of the DECODER's row k: the two tables must agree on it
     for (int k = 0; k < K; ++k)
-      CD_CHECK(coef_enc_host[k].t == coef_dec_host[k].t, "cd_cycle_translate_ctrl: the encoder's and the decoder's tables disagree "
-               "on the timestep of row %d (%d against %d)", k, coef_enc_host[k].t, coef_dec_host[k].t);
+      CD_CHECK(coef_enc_host[k].t == coef_dec_host[k].t, "%s: the encoder's and the decoder's tables disagree "
+               "on the timestep of row %d (%d against %d)", bk ? "cd_cycle_translate_blend" : "cd_cycle_translate_ctrl", k,
+               coef_enc_host[k].t, coef_dec_host[k].t);
+  }
+  if (text_on) {
+    CD_CHECK(sched_kind == CD_SCHED_DDIM, "%s is only defined for sched_kind = CD_SCHED_DDIM", what);
+    CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer && (enc_ctx_c || enc_ctx_uc),
+             "%s needs a network with a text context (and the contexts of both passes)", what);
+    CD_CHECK(!u->f32, "%s is not built for fp32 / fp32x3 networks (their transformer blocks run the fp32 "
+                      "attention of st_f32.hip): use the 16-bit precision", what);
+    CD_CHECK(ctx_len <= kCtrlKeys, "%s: context length %d above the %d keys the kernel keeps resident", what, ctx_len,
+             kCtrlKeys);
+  }
+  if (bk) {
+    const int R = u->image_size;
+    CD_CHECK(bk->sel_src && bk->sel_tgt, "the local blend: sel_src / sel_tgt is NULL");
+    CD_CHECK(bk->B_sel > 0 && B % bk->B_sel == 0, "the local blend shape mismatch: %d selector entries for a batch of %d",
+             bk->B_sel, B);
+    CD_CHECK(bk->side > 0 && bk->side <= kBlendMaxSide, "the local blend: side = %d outside [1, %d] (both maps of a row stay "
+             "in LDS)", bk->side, kBlendMaxSide);
+    CD_CHECK(R % bk->side == 0, "the local blend: a %d x %d token grid does not divide the %d x %d latent", bk->side, bk->side,
+             R, R);
+    CD_CHECK(u->count_text_blocks(bk->side, bk->side) > 0, "the local blend: no transformer block has a token grid of side %d",
+             bk->side);
+    CD_CHECK(bk->pool >= 1 && bk->pool <= kBlendMaxPool && bk->pool % 2 == 1, "the local blend: pool = %d is not an odd number "
+             "in [1, %d]", bk->pool, kBlendMaxPool);
+    CD_CHECK(bk->n_start >= 0 && bk->n_start <= K, "the local blend: n_start = %d outside [0, K = %d]", bk->n_start, K);
+    CD_CHECK(std::isfinite(bk->thr), "the local blend: the threshold is not finite");
   }
   if (ctrl_on) {
     CD_CHECK(ck->n_ctrl > 0 && ck->n_ctrl <= K, "cross-attention control: n_ctrl = %d outside [0, K = %d]", ck->n_ctrl, K);
-    CD_CHECK(sched_kind == CD_SCHED_DDIM, "cross-attention control is only defined for sched_kind = CD_SCHED_DDIM");
-    CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer && (enc_ctx_c || enc_ctx_uc),
-             "cross-attention control needs a network with a text context (and the contexts of both passes)");
-    CD_CHECK(!u->f32, "cross-attention control is not built for fp32 / fp32x3 networks (their transformer blocks run the fp32 "
-                      "attention of st_f32.hip): use the 16-bit precision");
-    CD_CHECK(ctx_len <= kCtrlKeys, "cross-attention control: context length %d above the %d keys the kernel keeps resident",
-             ctx_len, kCtrlKeys);
     CD_CHECK(ck->mapper && ck->alpha && ck->weight, "cross-attention control: mapper / alpha / weight is NULL");
     CD_CHECK(ck->B_ctrl > 0 && B % ck->B_ctrl == 0, "cross-attention control shape mismatch: %d control rows for a batch of %d",
              ck->B_ctrl, B);
@@ -689,9 +724,9 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
   Guidance ge = resolve_guidance(enc_ctx_c, enc_ctx_uc, enc_guidance);
   Guidance gd = resolve_guidance(dec_ctx_c, dec_ctx_uc, dec_guidance_per_sample ? 2.0f : dec_guidance);
   if (dec_guidance_per_sample) CD_CHECK(gd.cfg, "per-sample guidance needs the classifier-free-guidance batch (both contexts)");
-  if (ctrl_on)
+  if (text_on)
     CD_CHECK((ge.cfg || (enc_ctx_c && ge.ctx_single == enc_ctx_c)) && (gd.cfg || (dec_ctx_c && gd.ctx_single == dec_ctx_c)),
-             "cross-attention control needs conditional rows in both passes (a guidance scale of 0 runs none)");
+             "%s needs conditional rows in both passes (a guidance scale of 0 runs none)", what);
   CD_CHECK(sched_kind == CD_SCHED_DDIM || (!ge.cfg && !gd.cfg), "classifier-free guidance is only implemented for sched_kind = CD_SCHED_DDIM");
   const bool has_ctx = enc_ctx_c || enc_ctx_uc;
   CD_CHECK(has_ctx == (dec_ctx_c || dec_ctx_uc), "cd_cycle_translate: contexts for both passes or for neither");
@@ -719,6 +754,22 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
   }
   const size_t esz = f32 ? 4 : 2;
   const int64_t chw = (int64_t)C * HW, n = (int64_t)B * chw;
+  // the local blend: the running sums of the encoder's and of the decoder's conditional rows [B | Bd][side][side], collected
+  // beside every forward, and the keep-mask [Bd][HW] that k_local_blend_mask rewrites from them once per step
+  WordMapCollect wm;
+  float *acc = nullptr, *keep = nullptr;
+  if (bk) {
+    const int ss = bk->side * bk->side;
+    acc = (float*)h->arena.alloc((size_t)(B + Bd) * ss * 4);
+    keep = (float*)h->arena.alloc((size_t)Bd * HW * 4);
+    HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)(B + Bd) * ss * 4, h->st));
+    launch_fill_f32(h->st, keep, 1.f, (int64_t)Bd * HW);
+    wm.N = 1; wm.min_side = wm.max_side = bk->side;
+    WordMapCollect::Range rs, rt;
+    rs.row0 = ge.cfg ? B : 0; rs.rows = B; rs.sel = bk->sel_src; rs.B_sel = bk->B_sel; rs.acc = acc;
+    rt.row0 = Bn - Bd; rt.rows = Bd; rt.sel = bk->sel_tgt; rt.B_sel = bk->B_sel; rt.acc = acc + (size_t)B * ss;
+    wm.ranges = {rs, rt};
+  }
   float* xt_e = (float*)h->arena.alloc((size_t)B * chw * 4);
   float* xt_d = (float*)h->arena.alloc((size_t)Bd * chw * 4);
   char* xin = (char*)h->arena.alloc((size_t)Bn * HW * cpad * esz);
@@ -772,6 +823,7 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     io.xin = (const bf16_t*)xin; io.B = Bn; io.tab = tab_d; io.step = k; io.t_shared = true;  // rows k of both tables carry the same t
     io.dup_tail = dup_tail;
     io.ctrl = (ctrl_on && i < ck->n_ctrl) ? &actl : nullptr;
+    io.maps = bk ? &wm : nullptr;
     io.out = eh; io.out_ld = out_ld;
     u->forward(c, io);
     const int is_last = (last_uses_x0 && k == 0) ? 1 : 0;
@@ -784,12 +836,26 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     if (mk) {
       const MaskBlend next = blend_of(k - 1, i + 1);
       launch_decode_step(h->st, sched_kind, dec, &next, /*blend=*/k > 0);
+    } else if (bk && i >= bk->n_start) {
+      // the mask of this step from the sums so far, then the step and - the last step included - the blend with the
+      // encoder's x of the level just arrived at (xt_e after the encoder's step kernel above)
+      LocalBlendMask lm;
+      lm.acc_src = acc; lm.acc_tgt = acc + (size_t)B * bk->side * bk->side; lm.keep = keep;
+      lm.B = B; lm.Bd = Bd; lm.side = bk->side; lm.f = u->image_size / bk->side; lm.pool = bk->pool; lm.thr = bk->thr;
+      launch_local_blend_mask(h->st, lm);
+      MaskBlend lb;
+      lb.mask = keep; lb.mask_bmod = Bd; lb.src = xt_e; lb.src_bmod = B;
+      launch_decode_step(h->st, sched_kind, dec, &lb, /*blend=*/true);
     } else {
       launch_decode_step(h->st, sched_kind, dec);
     }
     h->pacer.tick(h->st);
   }
   HIP_CHECK(hipMemcpyAsync(x_out, xt_d, (size_t)Bd * chw * 4, hipMemcpyDeviceToDevice, h->st));
+  if (bk && bk->acc_out)
+    HIP_CHECK(hipMemcpyAsync(bk->acc_out, acc, (size_t)(B + Bd) * bk->side * bk->side * 4, hipMemcpyDeviceToDevice, h->st));
+  if (bk && bk->keep_out)
+    HIP_CHECK(hipMemcpyAsync(bk->keep_out, keep, (size_t)Bd * HW * 4, hipMemcpyDeviceToDevice, h->st));
 }
 
 int cd_cycle_translate(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
@@ -841,6 +907,29 @@ int cd_cycle_translate_ctrl(cd_handle h, int net, int sched_kind, const float* x
   cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
                        dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
                        z_out, x_out, mask ? &mk : nullptr, &ck);
+  CD_API_END
+}
+
+// The coupled loop with prompt-to-prompt's local blend: the word maps of the encoder's and of the decoder's
+// conditional rows are collected beside every forward, and from iteration n_start on the decoder's latent is held to the
+// encoder's outside the region the maps mark, the mask rebuilt after every step. With or without cross-attention control.
+int cd_cycle_translate_blend(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
+                             const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
+                             float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
+                             const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
+                             uint64_t seed, int last_uses_x0, const float* mapper, const float* alpha, const float* weight,
+                             int B_ctrl, int n_ctrl, const float* sel_src, const float* sel_tgt, int B_sel, int side, int pool,
+                             float thr, int n_start, float* acc_out, float* keep_out, float* z_out, float* x_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CtrlArgs ck;
+  ck.mapper = mapper; ck.alpha = alpha; ck.weight = weight; ck.B_ctrl = B_ctrl; ck.n_ctrl = n_ctrl;
+  BlendArgs bk;
+  bk.sel_src = sel_src; bk.sel_tgt = sel_tgt; bk.B_sel = B_sel; bk.side = side; bk.pool = pool; bk.thr = thr;
+  bk.n_start = n_start; bk.acc_out = acc_out; bk.keep_out = keep_out;
+  cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
+                       dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
+                       z_out, x_out, nullptr, &ck, &bk);
   CD_API_END
 }
 

@@ -1,7 +1,7 @@
 // The cd_op_* half of the extern "C" boundary (include/cyclediff.h): one kernel, or one building block of the engine, per
 // entry point, on operands the caller hands in. They exist for the parity tests (tests/_ops.py) and the micro-benchmarks;
-// the Python API itself calls only cd_op_lowpass, cd_op_gauss, cd_op_cross_attention_maps, cd_op_automask_reduce and
-// cd_op_bench_mfma_sustained. No network forward and no sampler loop runs through this file.
+// the Python API itself calls only cd_op_lowpass, cd_op_gauss, cd_op_cross_attention_maps, cd_op_automask_reduce,
+// cd_op_local_blend_mask and cd_op_bench_mfma_sustained. No network forward and no sampler loop runs through this file.
 //
 // A new test entry stages its operands with the helpers below and writes nothing of the kind itself:
 //   dense        op_rows16 (fp32 [rows][C] -> 16-bit), op_image16 (fp32 NCHW -> 16-bit NHWC Act)
@@ -597,6 +597,21 @@ int cd_op_automask_reduce(cd_handle h, const float* eps_src, const float* eps_tg
   m.map_out = map_out; m.mean_out = mean_out; m.keep_out = keep_out;
   launch_automask_accum(h->st, m);
   launch_automask_finish(h->st, m);
+  HIP_CHECK(hipStreamSynchronize(h->st));
+  CD_API_END
+}
+
+// one launch of k_local_blend_mask on caller-built sums
+int cd_op_local_blend_mask(cd_handle h, const float* acc_src, const float* acc_tgt, int B, int Bd, int side, int f, int pool,
+                           float thr, float* keep_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && acc_src && acc_tgt && keep_out && B > 0 && Bd > 0, "bad argument");
+  CD_CHECK(Bd % B == 0, "local blend shape mismatch: %d decoder rows for %d source rows", Bd, B);
+  LocalBlendMask lm;
+  lm.acc_src = acc_src; lm.acc_tgt = acc_tgt; lm.keep = keep_out;
+  lm.B = B; lm.Bd = Bd; lm.side = side; lm.f = f; lm.pool = pool; lm.thr = thr;
+  launch_local_blend_mask(h->st, lm);
   HIP_CHECK(hipStreamSynchronize(h->st));
   CD_API_END
 }

@@ -78,7 +78,8 @@ struct MaskBlend {
 
 void launch_init_xt(hipStream_t st, const StepArgs& a);
 void launch_encode_step(hipStream_t st, int kind, const StepArgs& a);
-// mk: SCHED_DDIM only, the step is followed by the blend of the next level unless blend is false (the last step)
+// mk: SCHED_DDIM only, the step is followed by the blend of the next level unless blend is false (the keep-mask entry points'
+// last step; the local blend of DESIGN.md 18 blends after every step, the last included)
 void launch_decode_step(hipStream_t st, int kind, const StepArgs& a, const MaskBlend* mk = nullptr, bool blend = false);
 // a.xt <- blend(a.xt) ahead of the first forward; uses a.geom and a.xin beside it
 void launch_mask_blend_init(hipStream_t st, const StepArgs& a, const MaskBlend& mk);
@@ -178,6 +179,21 @@ struct WordMapFold {
   float scale = 1.f;
 };
 void launch_word_map_fold(hipStream_t st, const WordMapFold& a);
+
+// ---------------------------------------------------------------- prompt-to-prompt local blend (automask.hip)
+// The keep-mask of one decoder row from the running sums of the word maps: for A = acc_src[r % B] and A = acc_tgt[r],
+//   p = max of A over |dy|, |dx| <= pool / 2 inside the image, mx = max p, e_A = mx > 0 && p / mx > thr;
+//   keep[r][y][x] = 1 - (e_src | e_tgt) at cell (y / f, x / f): exact 0 / 1 on the [side * f]^2 latent grid.
+constexpr int kBlendMaxSide = 64;  // both maps of a row stay in LDS: 2 * 64 * 64 * 4 B
+constexpr int kBlendMaxPool = 7;
+struct LocalBlendMask {
+  const float* acc_src = nullptr;  // [B][side][side]
+  const float* acc_tgt = nullptr;  // [Bd][side][side]
+  float* keep = nullptr;           // [Bd][side * f][side * f]
+  int B = 0, Bd = 0, side = 0, f = 1, pool = 1;
+  float thr = 0.f;
+};
+void launch_local_blend_mask(hipStream_t st, const LocalBlendMask& a);
 
 // ---------------------------------------------------------------- implicit-GEMM conv / GEMM (conv_gemm.hip)
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_GEGLU = 3, ACT_QGELU = 4, ACT_RELU = 5 };  // QGELU: x*sigmoid(1.702x) (CLIP)

@@ -506,7 +506,27 @@ void UNetOpenAI::st_core16(Ctx& c, STW& s, const Act& x_in, const Act& x, Act& o
       p.scale = scale; p.q_log2 = 1;
       launch_cross_attention_ctrl(c.st, p);
     }
-    if (maps_ && maps_->takes(x.H)) {  // the same q and keys once more, reduced to the mass on the chosen words
+    if (maps_ && maps_->ranged() && maps_->takes(x.H)) {  // ... of the chosen rows only, summed on the token grid
+      CD_CHECK(x.H == x.W && x.H == s.side, "word maps: block of side %d", x.H);
+      const int64_t q_bs = (int64_t)T * q.ld, k_bs = (int64_t)ctx_L_ * C;
+      for (const WordMapCollect::Range& rg : maps_->ranges) {
+        CD_CHECK(rg.row0 >= 0 && rg.rows > 0 && rg.row0 + rg.rows <= B, "word maps: rows %d + %d of a batch of %d", rg.row0,
+                 rg.rows, B);
+        WordMapParams mp;
+        mp.q = q.p + rg.row0 * q_bs; mp.k = s.k2c + rg.row0 * k_bs; mp.sel = rg.sel;
+        mp.maps = (float*)c.arena->alloc((size_t)rg.rows * T * 4);
+        mp.B = rg.rows; mp.B_sel = rg.B_sel; mp.H = s.heads; mp.Tq = T; mp.L = ctx_L_; mp.D = s.dh; mp.N = 1;
+        mp.ldq = q.ld; mp.ldk = C; mp.q_bs = q_bs; mp.k_bs = k_bs;
+        mp.scale = scale; mp.q_log2 = 1;
+        launch_cross_attention_maps(c.st, mp);
+        WordMapAccum ma;
+        ma.layer = mp.maps; ma.acc = rg.acc; ma.rows = rg.rows; ma.N = 1; ma.s = x.H; ma.h = x.H; ma.w = x.H;
+        ma.first = maps_->seen == 0 ? 1 : 0;
+        launch_word_map_accumulate(c.st, ma);
+      }
+      ++maps_->layers;
+      ++maps_->seen;
+    } else if (maps_ && maps_->takes(x.H)) {  // the same q and keys once more, reduced to the mass on the chosen words
       CD_CHECK(x.H == x.W && x.H == s.side && B == maps_->n_chunk * maps_->B, "word maps: block of side %d, %d rows", x.H, B);
       WordMapParams mp;
       mp.q = q.p; mp.k = s.k2c; mp.sel = maps_->sel;
@@ -590,8 +610,10 @@ void UNetOpenAI::forward(Ctx& c, const UNetIO& io) {
   CD_CHECK(!io.ctrl || (!f32 && io.ctrl->va.size() == st_.size()), "U-Net: cross-attention control on a network it was not built for");
   CD_CHECK(!io.maps || !f32, "U-Net: per-word attention maps are not built for fp32 / fp32x3 networks (their transformer blocks "
            "run the fp32 attention of st_f32.hip): use the 16-bit precision");
-  CD_CHECK(!(io.maps && io.ctrl), "U-Net: a forward collects per-word attention maps or runs cross-attention control, not both");
-  CD_CHECK(!io.maps || (io.dup_tail == 0 && !io.cfg_dup), "U-Net: per-word attention maps on a batch with repeated rows");
+  // (the ranged collection of the local blend runs beside both: WordMapCollect::Range)
+  const bool maps_all = io.maps && !io.maps->ranged();
+  CD_CHECK(!(maps_all && io.ctrl), "U-Net: a forward collects per-word attention maps or runs cross-attention control, not both");
+  CD_CHECK(!maps_all || (io.dup_tail == 0 && !io.cfg_dup), "U-Net: per-word attention maps on a batch with repeated rows");
   ctrl_ = io.ctrl;
   maps_ = io.maps;
   if (maps_) maps_->layers = 0;

@@ -451,10 +451,12 @@ class Engine:
 
     def _cycle_translate(self, net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
                          dec_guidance, n_dec, noise, seed, last_uses_x0, mask=None, mask_x0=None, qcoef=None, mask_noise=None,
-                         mask_seed=0, mask_source="q_sample", ctrl=None):
-        """The marshalling of the three coupled entry points: cd_cycle_translate without a mask and without `ctrl`,
+                         mask_seed=0, mask_source="q_sample", ctrl=None, blend=None):
+        """The marshalling of the coupled entry points: cd_cycle_translate without a mask and without `ctrl`,
         cd_cycle_translate_masked with a mask only, cd_cycle_translate_ctrl with `ctrl` = (mapper, alpha, weight, n_ctrl) - the
-        argument list of each is the one before it plus a tail, as cycle_translate_impl serves them from one body."""
+        argument list of each is the one before it plus a tail, as cycle_translate_impl serves them from one body.
+        cd_cycle_translate_blend with `blend` = (sel_src, sel_tgt, side, pool, thr, n_start) takes the control's tail (none:
+        NULL and n_ctrl = 0) without the mask's, then its own; it returns (z, x, acc, keep)."""
         x0 = self._f32(x0)
         K = len(coef_dec)
         assert len(coef_enc) == K + 1
@@ -472,8 +474,10 @@ class Engine:
         L = next((t.shape[1] for t in ctxs if t is not None), 0)
         for t, rows in zip(ctxs, (B, B, n_dec * B, n_dec * B)):
             assert t is None or t.shape[0] == rows, (t.shape, rows)
-        fn, tail, ctl = self.lib.cd_cycle_translate, [], None
-        if mask is not None or ctrl is not None:
+        fn, tail, ctl, sels, outs = self.lib.cd_cycle_translate, [], None, None, ()
+        if blend is not None and mask is not None:
+            raise ValueError("the local blend rewrites the keep-mask after every step: it takes no mask of the caller's")
+        if blend is None and (mask is not None or ctrl is not None):
             fn = self.lib.cd_cycle_translate_masked
             tail = [ptr(mask), ptr(mask_x0), Bm, src, C.c_void_p(qcoef.ctypes.data) if qcoef is not None else None,
                     ptr(mask_noise), C.c_uint64(mask_seed)]
@@ -485,13 +489,29 @@ class Engine:
                                  % (L, L, L, [tuple(t.shape) for t in ctl]))
             fn = self.lib.cd_cycle_translate_ctrl
             tail += [ptr(ctl[0]), ptr(ctl[1]), ptr(ctl[2]), Bc, int(ctrl[3])]
+        if blend is not None:
+            if ctrl is None:
+                tail = [None, None, None, 0, 0]
+            sels = [torch.as_tensor(t, dtype=torch.float32).to(x0.device).contiguous() for t in blend[:2]]
+            Bs = sels[0].shape[0]
+            if sels[0].dim() != 2 or tuple(sels[0].shape) != (Bs, L) or tuple(sels[1].shape) != (Bs, L):
+                raise ValueError("the local blend's selectors must both be [B_sel, %d], got %s"
+                                 % (L, [tuple(t.shape) for t in sels]))
+            side, pool, thr, n_start = int(blend[2]), int(blend[3]), float(blend[4]), int(blend[5])
+            if side <= 0:
+                raise ValueError("the local blend: side = %d is not a token grid side" % side)
+            acc = torch.empty(((1 + n_dec) * B, side, side), device=x0.device, dtype=torch.float32)
+            keep = torch.empty((n_dec * B, 1, H, W), device=x0.device, dtype=torch.float32)
+            fn = self.lib.cd_cycle_translate_blend
+            tail += [ptr(sels[0]), ptr(sels[1]), Bs, side, pool, C.c_float(thr), n_start, ptr(acc), ptr(keep)]
+            outs = (acc, keep)
         gvec, gscalar = self._guidance(dec_guidance, n_dec * B, "n_dec * B", x0.device)
         nz = self._f32(noise) if noise is not None else None
         check(fn(self.h, net, kind, ptr(x0), ptr(ctxs[0]), ptr(ctxs[1]), C.c_float(enc_guidance), ptr(ctxs[2]), ptr(ctxs[3]),
                  C.c_float(gscalar), ptr(gvec), L, B, n_dec, K, C.c_void_p(coef_enc.ctypes.data), C.c_void_p(coef_dec.ctypes.data),
                  ptr(nz), C.c_uint64(seed), int(last_uses_x0), *tail, ptr(z), ptr(x)))
-        self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise, ctl)  # the launches read them asynchronously
-        return z, x
+        self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise, ctl, sels)  # the launches read them asynchronously
+        return (z, x) + outs
 
     @staticmethod
     def _guidance(guidance, rows, what, device):
@@ -580,6 +600,32 @@ class Engine:
         return self._cycle_translate(net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
                                      dec_guidance, n_dec, noise, seed, last_uses_x0, mask, mask_x0, qcoef, mask_noise, mask_seed,
                                      mask_source, ctrl=(mapper, alpha, weight, n_ctrl))
+
+    def cycle_translate_blend(self, net, kind, x0, coef_enc, coef_dec, sel_src, sel_tgt, side, pool=3, thr=0.3, n_start=0,
+                              ctrl=None, enc_ctx_c=None, enc_ctx_uc=None, enc_guidance=1.0, dec_ctx_c=None, dec_ctx_uc=None,
+                              dec_guidance=1.0, n_dec=1, noise=None, seed=0, last_uses_x0=True):
+        """cd_cycle_translate_blend: cycle_translate (or, with ctrl = (mapper, alpha, weight, n_ctrl), cycle_translate_ctrl)
+        with prompt-to-prompt's local blend. sel_src / sel_tgt [B_sel, L] weigh the key positions of the source / target
+        prompt, B_sel dividing B; the maps of the text cross-attentions of token grid `side` on them are summed over layers and
+        steps, and from iteration n_start on every step is followed by x <- x_enc * keep + (1 - keep) * x with keep rebuilt from
+        the sums (pool, threshold on the map's own maximum, union of source and target).
+        Returns (z, x, acc [(1 + n_dec) * B, side, side], keep [n_dec * B, 1, H, W])."""
+        return self._cycle_translate(net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
+                                     dec_guidance, n_dec, noise, seed, last_uses_x0, ctrl=ctrl,
+                                     blend=(sel_src, sel_tgt, side, pool, thr, n_start))
+
+    def local_blend_mask(self, acc_src, acc_tgt, f=1, pool=3, thr=0.3):
+        """cd_op_local_blend_mask: one launch of the blend's mask kernel. acc_src [B, side, side], acc_tgt [Bd, side, side]
+        (decoder row r belongs to source row r % B) -> keep [Bd, 1, side * f, side * f] of 0 / 1, 1 = keep the source."""
+        a, t = self._f32(acc_src), self._f32(acc_tgt)
+        if a.dim() != 3 or t.dim() != 3 or a.shape[1] != a.shape[2] or tuple(t.shape[1:]) != tuple(a.shape[1:]):
+            raise ValueError("the sums must be [B, side, side] and [Bd, side, side], got %s and %s"
+                             % (tuple(a.shape), tuple(t.shape)))
+        side = a.shape[1]
+        keep = torch.empty((t.shape[0], 1, side * int(f), side * int(f)), device=a.device, dtype=torch.float32)
+        check(self.lib.cd_op_local_blend_mask(self.h, ptr(a), ptr(t), a.shape[0], t.shape[0], side, int(f), int(pool),
+                                              C.c_float(thr), ptr(keep)))
+        return keep
 
     def ilvr_decode(self, net, kind, z, coef, ref, down_n, qcoef, range_t=0, n_eps=0, noise_tail=None, seed=0, ref_noise=None,
                     ref_seed=0):

@@ -18,7 +18,7 @@ None of these classes has a translate(): Model.forward runs encode() then forwar
 """
 import torch
 
-from .. import _ffi, auto_mask, schedule
+from .. import _ffi, attn_control, auto_mask, schedule
 from .ddpm_ddim_wrapper import DDPMDDIMWrapper
 from .latent_text_wrapper import LatentDiffStochasticTextWrapper, SDStochasticTextWrapper
 
@@ -91,6 +91,7 @@ class _LatentDDIBText(_LatentBaseline):
         # the inversion is the whole chain (skip_steps shortens it); cross-attention control needs the coupled loop's source rows
         _reject("DDIB", white_box_steps=white_box_steps, cac_steps=kw.pop("cac_steps", None), cac_mode=kw.pop("cac_mode", None))
         auto_mask.refuse(kw, "DDIB")
+        attn_control.refuse_local_blend(kw, "DDIB")
         kw.setdefault("encoder_unconditional_guidance_scales", [1.0])
         kw.setdefault("decoder_unconditional_guidance_scales", [1.0])
         super().__init__(source_model_type, custom_steps, 0.0, -1, list(skip_steps), n_trials=1, couple=False, **kw)
@@ -141,6 +142,7 @@ class _LatentSDEditText(_LatentBaseline):
                 encoder_unconditional_guidance_scales=encoder_unconditional_guidance_scales,
                 cac_steps=kw.pop("cac_steps", None), cac_mode=kw.pop("cac_mode", None))
         auto_mask.refuse(kw, "SDEdit")
+        attn_control.refuse_local_blend(kw, "SDEdit")
         kw.setdefault("decoder_unconditional_guidance_scales", [1.0])
         super().__init__(source_model_type, custom_steps, eta, -1, [0], encoder_unconditional_guidance_scales=[1.0],
                          n_trials=n_trials or 1, couple=False, **kw)
@@ -277,6 +279,7 @@ class DDPMILVRWrapper(_NoCoupledLoop, DDPMDDIMWrapper):
         from .ddpm_ddim_wrapper import MODEL_TYPES, _desc
         _reject("ILVR", sdedit_strengths=sdedit_strengths, skip_steps=skip_steps, white_box_steps=white_box_steps)
         auto_mask.refuse(kw, "ILVR")
+        attn_control.refuse_local_blend(kw, "ILVR")
         for name, v, lo in (("ilvr_down_n", ilvr_down_n, 1), ("ilvr_range_t", ilvr_range_t, 0)):
             if isinstance(v, bool) or not isinstance(v, int) or v < lo:
                 raise ValueError("%s must be an integer >= %d, got %r" % (name, lo, v))

@@ -17,7 +17,7 @@ import os
 
 import torch
 
-from .. import _ffi, auto_mask, schedule
+from .. import _ffi, attn_control, auto_mask, schedule
 from ..engine import afhq_iddpm_desc, ho_ddpm_desc
 from ..runtime import get_engine, load_or_init_weights
 
@@ -56,6 +56,7 @@ class DDPMDDIMWrapper(torch.nn.Module):
                  noise_on_cpu=False, precision="fp32", net_desc=None, allow_lossy_ddim=False, **auto_mask_keys):
         super().__init__()
         auto_mask.refuse(auto_mask_keys, "%s (gan_type DDPM_DDIM and the pixel baselines)" % type(self).__name__)
+        attn_control.refuse_local_blend(auto_mask_keys, "%s (gan_type DDPM_DDIM and the pixel baselines)" % type(self).__name__)
         if auto_mask_keys:
             raise TypeError("unexpected [gan] keys %s" % sorted(auto_mask_keys))
         if str(precision) not in PRECISIONS:

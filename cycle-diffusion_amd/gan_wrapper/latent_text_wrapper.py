@@ -79,8 +79,29 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                  n_trials=None, cond_stage=None, ranker=None, device=None, text_encoder=None,
                  noise_on_cpu=False, fold_ensemble=True, ranker_path=None, precision="fp16", couple=True,
                  mask_source="q_sample", cac_steps=0.0, cac_mode="refine", auto_mask=None, auto_mask_draws=10,
-                 auto_mask_strength=0.5, auto_mask_ratio=3.0, auto_mask_threshold=0.5, auto_mask_dilate=0, auto_mask_seed=0):
+                 auto_mask_strength=0.5, auto_mask_ratio=3.0, auto_mask_threshold=0.5, auto_mask_dilate=0, auto_mask_seed=0,
+                 local_blend=None, local_blend_threshold=0.3, local_blend_pool=3, local_blend_side=0, local_blend_start=0.2):
         super().__init__()
+        # `[gan] local_blend = words` (default none): prompt-to-prompt's local blend on the coupled loop - the
+        # decoder's latent is held to the encoder's outside the region the word maps of the edited words mark, the mask rebuilt
+        # after every step from iteration int(local_blend_start * K) on. `local_blend_side`: the token grid whose blocks are
+        # collected (0: image_size / 4), `local_blend_pool` / `local_blend_threshold`: the LocalBlend rule
+        self.local_blend = "none" if local_blend is None else str(local_blend)
+        if self.local_blend not in attn_control.LOCAL_BLEND_MODES:
+            raise ValueError("local_blend must be one of %s" % (attn_control.LOCAL_BLEND_MODES,))
+        self.local_blend_threshold, self.local_blend_pool = float(local_blend_threshold), int(local_blend_pool)
+        self.local_blend_side, self.local_blend_start = int(local_blend_side), float(local_blend_start)
+        if not np.isfinite(self.local_blend_threshold):
+            raise ValueError("local_blend_threshold must be finite, got %r" % (local_blend_threshold,))
+        if self.local_blend_pool % 2 != 1 or not 1 <= self.local_blend_pool <= 7:
+            raise ValueError("local_blend_pool must be an odd number in [1, 7], got %r" % (local_blend_pool,))
+        if self.local_blend_side < 0:
+            raise ValueError("local_blend_side must be a token grid side (0: image_size / 4), got %r" % (local_blend_side,))
+        attn_control.local_blend_start(self.local_blend_start, 1)
+        if self.local_blend != "none" and str(precision) in ("fp32", "fp32x3"):
+            raise ValueError("local_blend needs the 16-bit precision: the word maps are not built for the fp32 / fp32x3 "
+                             "networks' transformer blocks")
+        self.last_local_blend_mask, self.last_local_blend_masks = None, None
         # `[gan] auto_mask = diffedit` (default none): translate() / forward() without a `mask=` estimate the keep-mask from the
         # two prompts (the keys: auto_mask.py) and take the masked path with it; an explicit `mask=` wins
         self.auto_mask_opts = am.AutoMaskOptions(auto_mask, auto_mask_draws, auto_mask_strength, auto_mask_ratio,
@@ -500,7 +521,7 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         return "cond" if scale == 1.0 else ("uncond" if scale == 0.0 else "cfg")
 
     # ---- encode + generate as ONE coupled loop (north_star; include/cyclediff.h cd_cycle_translate)
-    def translate(self, image, encode_text, decode_text, mask=None, attn_ctrl=None):
+    def translate(self, image, encode_text, decode_text, mask=None, attn_ctrl=None, local_blend=None):
         """What Model.forward composes (model/text_unsupervised_translation.py:24-40): `self(encode(image, encode_text), image,
         encode_text, decode_text)`, with the DPM-Encoder and the decode of every ensemble member running as one loop - step k of
         both evaluates the same U-Net at the same timestep, and the decode step needs eps_k only after its forward, so each
@@ -523,7 +544,21 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         loop, so this ALWAYS runs coupled too, in chunks of samples past COUPLE_MAX_TOKENS. Composes with a keep-mask of either
         source; draw order and member order do not change. With cac_steps = 0 and no attn_ctrl nothing below changes.
         `[gan] auto_mask = diffedit` without a `mask`: the keep-mask is estimated from the two prompts on the x0 the masked
-        path works on (auto_mask()) and that path runs with it; with auto_mask = none nothing below changes."""
+        path works on (auto_mask()) and that path runs with it; with auto_mask = none nothing below changes.
+        `[gan] local_blend = words` or `local_blend` = (src_words, tgt_words), two lists of strings: prompt-to-prompt's local
+        blend. The word maps of the source and of the target rows of this very run are summed over blocks and
+        steps, and from iteration int(local_blend_start * K) of a member's K-step loop on every decode step is followed by x <-
+        x_enc * keep + (1 - keep) * x, keep rebuilt from the sums each time. Without words the selectors mark the tokens the
+        prompts do not share (attn_control.local_blend_selectors); identical prompts mark none and keep everything. ALWAYS
+        the coupled loop, in chunks of samples past COUPLE_MAX_TOKENS; composes with cac_steps / attn_ctrl, not with a
+        keep-mask. last_local_blend_masks: the final masks [B, 1, h, w] per candidate, last_local_blend_mask the first one's.
+        With local_blend off nothing below changes."""
+        blend = local_blend is not None or getattr(self, "local_blend", "none") != "none"
+        if blend and (mask is not None or self._auto_mask_on()):
+            raise ValueError("local_blend builds its own keep-mask after every step: it takes no mask= and no auto_mask")
+        if blend and self.precision in ("fp32", "fp32x3"):
+            raise ValueError("local_blend needs the 16-bit precision: the word maps are not built for the fp32 / fp32x3 "
+                             "networks' transformer blocks")
         if mask is None and self._auto_mask_on():
             mask = AUTO_MASK  # estimated below, once x0 exists
         sch = self._schedule()
@@ -545,6 +580,12 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         if ctrl and (len(ride) != n_dec or main == "uncond" or "uncond" in enc_kinds):
             raise ValueError("cross-attention control: every decoder scale must ride in the coupled loop (all guided, or one "
                              "unguided scale) and no scale may be 0 - the control acts on conditional rows")
+        if blend and not whole:
+            raise ValueError("local_blend needs the DPM-Encoder over the whole chain (white_box_steps = custom_steps + 1): the "
+                             "steps past a shorter prefix have no source rows")
+        if blend and (len(ride) != n_dec or main == "uncond" or "uncond" in enc_kinds):
+            raise ValueError("local_blend: every decoder scale must ride in the coupled loop (all guided, or one unguided "
+                             "scale) and no scale may be 0 - the maps are those of conditional rows")
         m = None if mask is None or mask is AUTO_MASK else self._latent_mask(mask, bsz)
         encoder = mask is not None and self.mask_source == "encoder"
         if encoder and not whole:
@@ -553,8 +594,21 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         if encoder and len(ride) != n_dec:
             raise ValueError("mask_source = 'encoder': every decoder scale must ride in the coupled loop (all guided, or "
                              "one unguided scale) - a candidate decoded from z afterwards has no encoder trajectory")
-        coupled = ctrl or encoder or bool(self.couple and whole and fits)
+        coupled = ctrl or encoder or blend or bool(self.couple and whole and fits)
         self.last_translate_coupled = coupled
+        sels, keep_parts = None, {}
+        if blend:
+            src_ids, eos = self._control_ids(encode_text)
+            tgt_ids, _ = self._control_ids(decode_text)
+            words = None
+            if local_blend is not None:
+                words = []
+                for ws in local_blend:
+                    wids = self._control_ids(list(ws))[0] if len(ws) else []
+                    words.append([list(r[1:attn_control.prompt_length(r, eos)]) for r in wids])
+            pairs = [attn_control.local_blend_selectors(src_ids[b], tgt_ids[b], eos, words) for b in range(bsz)]
+            sels = [torch.from_numpy(np.stack([p[i] for p in pairs], 0)).to(self.device) for i in (0, 1)]
+            side = self.local_blend_side or self.image_size // 4
         ctl = None
         if ctrl:
             if attn_ctrl is None:
@@ -601,7 +655,17 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                         if not encoder:  # decoder row (jr * n + mi) * nb + b
                             kw.update(mask_x0=x0[sl].contiguous(), qcoef=sch.coef_qsample(skip), mask_noise=torch.cat(
                                 [mask_noise[i * n_dec + j][:, sl] for j in ride for i in idx], dim=1).contiguous())
-                    if ctl is not None:
+                    if sels is not None:
+                        K = len(sch) - skip
+                        z, x, _acc, keep = self.engine.cycle_translate_blend(
+                            *args, sels[0][sl].contiguous(), sels[1][sl].contiguous(), side, pool=self.local_blend_pool,
+                            thr=self.local_blend_threshold, n_start=attn_control.local_blend_start(self.local_blend_start, K),
+                            ctrl=None if ctl is None else (ctl[0][sl].contiguous(), ctl[1][sl].contiguous(),
+                                                           ctl[2][sl].contiguous(), int(self.cac_steps * K)), **kw)
+                        for mi, i in enumerate(idx):
+                            for jr, j in enumerate(ride):
+                                keep_parts.setdefault(i * n_dec + j, []).append(keep[(jr * n + mi) * nb:(jr * n + mi + 1) * nb])
+                    elif ctl is not None:
                         if m is not None:
                             kw["mask"] = m[sl].contiguous()
                         z, x = self.engine.cycle_translate_ctrl(
@@ -617,6 +681,9 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                             lat_parts.setdefault(i * n_dec + j, []).append(x[(jr * n + mi) * nb:(jr * n + mi + 1) * nb])
         z_ensemble = [p[0] if len(p) == 1 else torch.cat(p, 0) for p in z_parts]  # one part: the whole batch fitted
         latents = {k: v[0] if len(v) == 1 else torch.cat(v, 0) for k, v in lat_parts.items()}
+        if sels is not None:
+            self.last_local_blend_masks = [torch.cat(keep_parts[k], 0) for k in sorted(keep_parts)]
+            self.last_local_blend_mask = self.last_local_blend_masks[0]
         img_ensemble = self.generate(z_ensemble, decode_text, latents=latents, mask_noise=mask_noise, **masked)
         return self._select(img_ensemble, image, encode_text, decode_text)
 
@@ -639,6 +706,9 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         if getattr(self, "cac_steps", 0.0) > 0:
             raise ValueError("cac_steps > 0 needs translate(): in encode() + forward() the source rows whose attention maps the "
                              "control injects no longer exist; use translate(image, encode_text, decode_text)")
+        if getattr(self, "local_blend", "none") != "none":
+            raise ValueError("local_blend needs translate(): in encode() + forward() the source rows whose word maps and whose "
+                             "latents the blend uses no longer exist; use translate(image, encode_text, decode_text)")
         if mask is None and self._auto_mask_on():
             mask = AUTO_MASK  # estimated below on the re-encoded x0
         if mask is None:

@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from .. import _ffi, auto_mask, schedule
+from .. import _ffi, attn_control, auto_mask, schedule
 from ..engine import ldm_uncond_unet_desc, vq_f4_vae_desc
 from ..runtime import apply_ema_shadow, get_engine, load_or_init_weights, read_checkpoint
 
@@ -41,6 +41,7 @@ class LatentDiffStochasticWrapper(torch.nn.Module):
                  unet_desc=None, vae_desc=None, state_dict=None, precision=None, allow_lossy_16bit=False, **auto_mask_keys):
         super().__init__()
         auto_mask.refuse(auto_mask_keys, "%s (an unconditional model: no prompts to compare)" % type(self).__name__)
+        attn_control.refuse_local_blend(auto_mask_keys, "%s (an unconditional model: no prompts)" % type(self).__name__)
         if auto_mask_keys:
             raise TypeError("unexpected [gan] keys %s" % sorted(auto_mask_keys))
         if enforce_class_input:

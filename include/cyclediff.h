@@ -282,6 +282,45 @@ int cd_cycle_translate_ctrl(cd_handle h, int net, int sched_kind, const float* x
                             const float* mapper, const float* alpha, const float* weight, int B_ctrl, int n_ctrl,
                             float* z_out, float* x_out);
 
+/* cd_cycle_translate(_ctrl) with prompt-to-prompt's LocalBlend (Hertz et al. 2022; no counterpart in the reference tree,
+ * DESIGN.md 18): the target is edited only where the word maps of this very sampling run - source branch and target branch
+ * together - look at the chosen words; elsewhere the decoder's latent is held to the DPM-Encoder's own x_t of every level.
+ * Arguments as cd_cycle_translate_ctrl's without the seven keep-mask arguments (n_ctrl = 0: no control), plus sel_src /
+ * sel_tgt [B_sel,L] fp32 device weights over the key positions of the source / target prompt, B a multiple of B_sel.
+ * With Bd = n_dec*B, k = K-1-i, h the latent side and f = h / side, iteration i does:
+ *   1. The one forward over [enc rows | dec rows] of cd_cycle_translate(_ctrl). In every text cross-attention (attn2) of a
+ *      transformer block whose token grid side equals `side`, for the encoder's CONDITIONAL rows (sample b, selector
+ *      sel_src[b % B_sel]) and the decoder's CONDITIONAL rows (the last Bd rows; row r, selector sel_tgt[(r % B) % B_sel]):
+ *          m[r, q] = (1/H) * sum_hd sum_j sel[j] * P_hd[q, j]   (hd ascending),   P = softmax(Q_own K_own^T * scale)
+ *      (cd_word_maps' quantity with N = 1) - the row's OWN attention also in an iteration under control.
+ *   2. acc[row] [side,side] fp32, zero before iteration 0, gains the layers one by one in the forward's order: one running
+ *      sum over the iterations in loop order.
+ *   3. The encoder's step kernel, unchanged: z_out is bit-identical to cd_cycle_translate's.
+ *   4. If i >= n_start, the mask: for decoder row r, b = r % B, and each A of acc_src[b], acc_tgt[r]:
+ *          p = max of A over |dy|, |dx| <= pool/2 inside the image;  mx = max p over the image;
+ *          e_A = (mx > 0) && (p / mx > thr)                          (fp32 division)
+ *      keep = 1 - (e_src | e_tgt), exact 0 / 1, each cell replicated f x f onto [Bd,1,h,w]; 1 = keep the source.
+ *   5. The decode step of row k (cd_ddim_decode's arithmetic) and, if i >= n_start, the blend
+ *          x <- src * keep + (1 - keep) * x       (fp32, in cd_ddim_decode_masked's operation order)
+ *      with src = the encoder's x of the level just arrived at (after step 3), of encoder row r % B. Unlike the keep-mask
+ *      entry points the blend also follows the LAST step (under last_uses_x0 the kept cells of x_out are x0 bit for bit), and
+ *      nothing is blended ahead of the first forward. Iterations i < n_start run exactly the launches of
+ *      cd_cycle_translate(_ctrl).
+ * acc_out [(B + Bd),side,side] or NULL: the final sums, source rows first. keep_out [Bd,1,h,w] or NULL: the mask of the last
+ * iteration, all ones if n_start == K. thr < 0 edits everywhere a map is above 0, thr >= 1 edits nowhere.
+ * Refused (error text, nothing launched), for every n_ctrl: tables whose rows k < K disagree on the timestep, sched_kind !=
+ * CD_SCHED_DDIM, networks without a text context, precision CD_PREC_F32 / CD_PREC_F32X3, ctx_len > 96, a pass without
+ * conditional rows (guidance 0); B % B_sel != 0; side > 64, h % side != 0, a side that matches no block; pool even or outside
+ * [1, 7]; n_start outside [0, K]; thr not finite; and what cd_cycle_translate_ctrl refuses of the control for n_ctrl != 0. */
+int cd_cycle_translate_blend(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
+                             const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
+                             float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
+                             const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
+                             uint64_t seed, int last_uses_x0, const float* mapper, const float* alpha, const float* weight,
+                             int B_ctrl, int n_ctrl, const float* sel_src, const float* sel_tgt, int B_sel, int side, int pool,
+                             float thr, int n_start, float* acc_out /* [B+n_dec*B,side,side] */,
+                             float* keep_out /* [n_dec*B,1,h,w] */, float* z_out, float* x_out);
+
 /* ILVR (Choi et al., ICCV 2021: Iterative Latent Variable Refinement), the reference-image-conditioned sampler of the
  * paper's unpaired table; no counterpart in the reference tree. cd_ddim_decode's loop on an unconditional
  * pixel DDPM, with the running image pulled to the low-pass band of a reference image after the step of every row k > range_t:
@@ -489,6 +528,11 @@ int cd_op_gauss(cd_handle h, uint64_t seed, uint32_t stream, int64_t first, int6
  * map_out [B,1,H,W] (or NULL), mean_out [B] (or NULL), keep_out [B,1,H,W]; refused as cd_automask refuses n, ratio, thr, dilate */
 int cd_op_automask_reduce(cd_handle h, const float* eps_src, const float* eps_tgt, int n, int B, int C, int H, int W,
                           float ratio, float thr, int dilate, float* map_out, float* mean_out, float* keep_out);
+/* one launch of cd_cycle_translate_blend's mask kernel (k_local_blend_mask, step 4 of its definition) on caller-built sums:
+ * acc_src [B,side,side], acc_tgt [Bd,side,side] fp32 device, Bd a multiple of B -> keep_out [Bd,1,side*f,side*f] of 0 / 1.
+ * Refused: side outside [1, 64], f < 1, pool even or outside [1, 7], Bd % B != 0. */
+int cd_op_local_blend_mask(cd_handle h, const float* acc_src, const float* acc_tgt, int B, int Bd, int side, int f, int pool,
+                           float thr, float* keep_out);
 /* the masked step kernels on explicit tensors (bit-exact checks). mode 0: x <- blend(x) (the blend ahead of the first forward);
  * mode 2: the CD_SCHED_DDIM decode step of cd_op_sched_step followed, when blend != 0, by the blend. src [B_mask,C,HW] is x0
  * (CD_MASK_QSAMPLE: src_k = qa*x0 + qb*mask_noise, mask_noise [B,C,HW] required) or the source latent itself (CD_MASK_ENCODER);

@@ -86,6 +86,10 @@ def folded_calls(model, batches, fold, seed, device):
                 if getattr(getattr(w, "auto_mask_opts", None), "on", False) and w.last_auto_mask is not None:
                     f = w.vae_factor  # nearest x f: every latent pixel becomes its f x f block
                     batch["auto_keep"] = w.last_auto_mask.repeat_interleave(f, 2).repeat_interleave(f, 3).cpu()
+                # `[gan] local_blend = words`: the final mask of the blend takes the same path (first candidate's)
+                if getattr(w, "local_blend", "none") != "none" and getattr(w, "last_local_blend_mask", None) is not None:
+                    f = w.vae_factor
+                    batch["auto_keep"] = w.last_local_blend_mask.repeat_interleave(f, 2).repeat_interleave(f, 3).cpu()
         yield batch, orig, img
 
 
