@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libcyclediff.so")
 
 CD_NET_UNET_OPENAI, CD_NET_UNET_HO, CD_NET_VAE_KL, CD_NET_CLIP_TEXT, CD_NET_BERT_XTR = 1, 2, 3, 4, 5
-CD_NET_OCLIP_TEXT, CD_NET_OCLIP_VISION, CD_NET_INCEPTION_FID = 6, 7, 8
+CD_NET_OCLIP_TEXT, CD_NET_OCLIP_VISION, CD_NET_INCEPTION_FID, CD_NET_LPIPS = 6, 7, 8, 9
 CD_SCHED_DDIM, CD_SCHED_DDPM = 0, 1
 CD_PREC_16, CD_PREC_F32, CD_PREC_F32X3 = 0, 1, 2
 CD_MASK_QSAMPLE, CD_MASK_ENCODER = 0, 1
@@ -67,6 +67,8 @@ SIGNATURES = {
     "cd_clip_text_features": [_VP, _I, _VP, _I, _I, _VP],
     "cd_clip_image_features": [_VP, _I, _VP, _I, _VP],
     "cd_inception_features": [_VP, _I, _VP, _I, _I, _VP],
+    "cd_lpips": [_VP, _I, _VP, _VP, _I, _I, _I, _VP, _VP],
+    "cd_lpips_tap": [_VP, _I, _VP, _I, _I, _I, _I, _VP],
     "cd_vae_encode": [_VP, _I, _VP, _VP, _U64, _I, _I, _I, _F, _VP],
     "cd_vae_decode": [_VP, _I, _VP, _I, _I, _F, _F, _F, _VP],
     "cd_dpm_encode": [_VP, _I, _I, _VP, _VP, _VP, _I, _F, _I, _I, _VP, _VP, _U64, _I, _VP],
@@ -132,6 +134,8 @@ SIGNATURES = {
     "cd_op_global_avg": [_VP, _VP, _I, _I, _I, _I, _VP],
     "cd_op_basic_conv": [_VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _VP, _VP,
                          _VP],
+    "cd_op_lpips_layer": [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP],
+    "cd_op_pool2x2": [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, _VP],
     "cd_op_bench_conv": [_VP, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_float)],
     "cd_op_bench_mfma_sustained": [_VP, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)],
     "cd_op_probe": [_VP, _I, _VP, _VP, _SZ],

@@ -14,7 +14,7 @@ LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libcyclediff.so")
 SOURCES = ["sched.hip", "ilvr.hip", "automask.hip", "elementwise.hip", "norm.hip", "conv_gemm.hip", "lin_stream.hip", "attn.hip", "f32_path.hip", "st_f32.hip", "diag.hip", "engine.hip",
-           "unet_openai.hip", "nets_ho_vae.hip", "clip_text.hip", "inception.hip",
+           "unet_openai.hip", "nets_ho_vae.hip", "clip_text.hip", "inception.hip", "lpips.hip",
            "capi.hip", "capi_ops.hip"]
 HEADERS = ["common.h", "kernels.h", "gauss.h", "engine.h", "capi_internal.h", os.path.join("..", "..", "include", "cyclediff.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",

@@ -126,6 +126,7 @@ int cd_net_create(cd_handle h, const cd_net_desc* d, int* net_id) {
     case CD_NET_OCLIP_TEXT:
     case CD_NET_OCLIP_VISION: n = make_clip_text(*d); break;
     case CD_NET_INCEPTION_FID: n = make_inception_fid(*d); break;
+    case CD_NET_LPIPS: n = make_lpips(*d); break;
     default: CD_CHECK(false, "unknown net kind %d", d->kind);
   }
   n->params.overflow = h->overflow_dev;
@@ -438,6 +439,30 @@ int cd_inception_features(cd_handle h, int net, const float* img, int B, int sto
   ArenaScope arena_scope(h->arena);
   Ctx c = h->ctx();
   inception_fid_features(h->nets[net].get(), c, img, B, stop_block, out);
+  CD_API_END
+}
+
+int cd_lpips(cd_handle h, int net, const float* img0, const float* img1, int B, int H, int W, float* per_layer, float* out) {
+  CD_API_BEGIN
+  CD_CHECK(h, "null handle");
+  enter_engine(h);
+  CD_CHECK(net >= 0 && net < (int)h->nets.size(), "bad net id %d", net);
+  CD_CHECK(img0 && img1 && out, "bad argument");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  lpips_distance(h->nets[net].get(), c, img0, img1, B, H, W, per_layer, out);
+  CD_API_END
+}
+
+int cd_lpips_tap(cd_handle h, int net, const float* img, int B, int H, int W, int tap, float* out) {
+  CD_API_BEGIN
+  CD_CHECK(h, "null handle");
+  enter_engine(h);
+  CD_CHECK(net >= 0 && net < (int)h->nets.size(), "bad net id %d", net);
+  CD_CHECK(img && out, "bad argument");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  lpips_tap(h->nets[net].get(), c, img, B, H, W, tap, out);
   CD_API_END
 }
 

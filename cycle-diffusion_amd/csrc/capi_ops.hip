@@ -1168,4 +1168,43 @@ int cd_op_basic_conv(cd_handle h, const float* x, int B, int Cin, int H, int W, 
   CD_API_END
 }
 
+// ---- the LPIPS kernels (lpips.hip), through the launchers the network calls
+int cd_op_lpips_layer(cd_handle h, const float* f0, const float* f1, const float* w, int B, int HW, int C, int in_pad,
+                      float* out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && f0 && f1 && w && out && B > 0 && HW > 0 && C > 0 && in_pad >= 0, "bad argument");
+  CD_CHECK((int64_t)B * HW < (1 << 30), "bad argument (too many rows)");
+  ArenaScope arena_scope(h->arena);
+  const int ld = C + in_pad;
+  const int64_t rows = (int64_t)B * HW;
+  float* part = (float*)h->arena.alloc((size_t)B * lpips_layer_chunks(HW, C > 512 ? 512 : C) * sizeof(float));
+  if (C % 8 == 0 && C <= 512 && ld % 8 == 0) {  // else: the launcher refuses below, before anything is staged
+    bf16_t* a = op_nan_rows16(h, rows, ld);
+    bf16_t* b = op_nan_rows16(h, rows, ld);
+    op_put_cols16(h, a, ld, 0, f0, rows, C);
+    op_put_cols16(h, b, ld, 0, f1, rows, C);
+    launch_lpips_layer(h->st, a, b, ld, B, HW, C, w, part, nullptr, 0, false, out);
+  } else {
+    launch_lpips_layer(h->st, nullptr, nullptr, ld, B, HW, C, w, part, nullptr, 0, false, out);
+  }
+  CD_API_END
+}
+
+int cd_op_pool2x2(cd_handle h, const float* x, int B, int C, int H, int W, int in_pad, int out_off, int out_ld, float* y) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && y && B > 0 && C > 0 && H > 0 && W > 0 && in_pad >= 0 && out_off >= 0, "bad argument");
+  CD_CHECK(C % 8 == 0 && in_pad % 8 == 0 && out_off % 8 == 0 && out_ld % 8 == 0, "C, in_pad, out_off, out_ld: multiples of 8 elements");
+  CD_CHECK(out_off + C <= out_ld, "the slice [%d, %d) does not fit a row of %d", out_off, out_off + C, out_ld);
+  CD_CHECK(H >= 2 && W >= 2, "bad argument (image smaller than the window)");
+  ArenaScope arena_scope(h->arena);
+  const Act a = op_upload_nhwc16(h, x, B, C, C + in_pad, H, W);
+  const int64_t rows = (int64_t)B * (H / 2) * (W / 2);
+  bf16_t* ob = op_nan_rows16(h, rows, out_ld);
+  launch_pool2x2(h->st, a.p, a.ld, B, H, W, C, ob + out_off, out_ld);
+  op_download_nchw(h, ob, false, out_ld, y, (int)rows + 64, out_ld, 1);
+  CD_API_END
+}
+
 }  // extern "C"

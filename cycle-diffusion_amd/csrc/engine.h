@@ -421,4 +421,10 @@ std::unique_ptr<TextEncoder> make_clip_text(const cd_net_desc& d);
 std::unique_ptr<Net> make_inception_fid(const cd_net_desc& d);
 void inception_fid_features(Net* n, Ctx& c, const float* img, int B, int stop_block, float* out);
 
+// LPIPS v0.1 on the AlexNet / VGG16 features (lpips.hip): img0 / img1 fp32 NCHW [B][3][H][W] in [-1, 1] -> out [B] (and
+// per_layer [B][5] when not null); lpips_tap: un-normalised ReLU output of tap 0..4 as fp32 NCHW
+std::unique_ptr<Net> make_lpips(const cd_net_desc& d);
+void lpips_distance(Net* n, Ctx& c, const float* img0, const float* img1, int B, int H, int W, float* per_layer, float* out);
+void lpips_tap(Net* n, Ctx& c, const float* img, int B, int H, int W, int tap, float* out);
+
 }  // namespace cd

@@ -561,4 +561,19 @@ ConvGemmParams basic_conv_params(const bf16_t* x, int ldx, int B, int H, int W, 
                                  int N, int KH, int KW, int stride, int pad_t, int pad_l, void* out, int out_ld,
                                  const bf16_t* zeros);
 
+// ---------------------------------------------------------------- LPIPS (lpips.hip)
+// the package's scaling layer and the layout change in one pass: x fp32 NCHW [B][3][HW] -> y 16-bit NHWC [B][HW][32],
+// channel c < 3 = (x - shift[c]) / scale[c], channels 3..31 zero
+void launch_lpips_input(hipStream_t st, const float* x, bf16_t* y, int B, int HW);
+// 2 x 2 stride-2 max pool over 16-bit NHWC (floor of odd sizes): x [B][H][W] pixels of stride ldx -> y [B][H / 2][W / 2] pixels
+// of stride ldy. C, ldx, ldy multiples of 8.
+void launch_pool2x2(hipStream_t st, const bf16_t* x, int ldx, int B, int H, int W, int C, bf16_t* y, int ldy);
+// one LPIPS tap: f0, f1 16-bit [B][HW] pixels of stride ld, C channels (C % 8 == 0, C <= 512, ld % 8 == 0), w fp32 [C]:
+//   d[b] = mean over pixels of sum_c w[c] (f0_c / (|f0| + 1e-10) - f1_c / (|f1| + 1e-10))^2
+// part: fp32 scratch [B][lpips_layer_chunks(HW, C)]. per_layer (or null) [B][5] gets d at column `layer`; out[b] = d[b], or
+// out[b] += d[b] when `accumulate`. No atomics: the same bits for an image whatever the batch around it.
+int lpips_layer_chunks(int HW, int C);
+void launch_lpips_layer(hipStream_t st, const bf16_t* f0, const bf16_t* f1, int ld, int B, int HW, int C, const float* w,
+                        float* part, float* per_layer, int layer, bool accumulate, float* out);
+
 }  // namespace cd

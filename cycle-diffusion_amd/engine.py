@@ -178,6 +178,119 @@ def inception_synthetic_state_dict(seed=0):
     return sd
 
 
+# ---- LPIPS (csrc/lpips.hip): the torchvision `features` stacks the `lpips` package taps
+LPIPS_SHIFT = (-.030, -.088, -.188)
+LPIPS_SCALE = (.458, .448, .450)
+LPIPS_MIN_SIZE = {"alex": 31, "vgg": 16}
+
+
+def lpips_desc(net="alex"):
+    """LPIPS v0.1 on the AlexNet ("alex") or VGG16 ("vgg") backbone: num_res_blocks carries the number of convs (5 / 13),
+    which selects the backbone; 16-bit storage, any input size from LPIPS_MIN_SIZE up; no other descriptor field is read."""
+    if net not in ("alex", "vgg"):
+        raise ValueError("LPIPS backbone %r: 'alex' or 'vgg'" % (net,))
+    return make_desc(_ffi.CD_NET_LPIPS, image_size=0, in_channels=3, out_channels=1, model_channels=0,
+                     num_res_blocks=5 if net == "alex" else 13, channel_mult=(), precision=_ffi.CD_PREC_16)
+
+
+def lpips_layers(net="alex"):
+    """[(features index, in_channels, out_channels, kernel, stride, pad, pool ahead of it (0 / 2 / 3), tap or -1)] of every
+    conv of the backbone, in the engine's declaration order. Pools are stride 2: 3 x 3 (alex) or 2 x 2 (vgg), floor mode."""
+    if net == "alex":
+        return [(0, 3, 64, 11, 4, 2, 0, 0), (3, 64, 192, 5, 1, 2, 3, 1), (6, 192, 384, 3, 1, 1, 3, 2),
+                (8, 384, 256, 3, 1, 1, 0, 3), (10, 256, 256, 3, 1, 1, 0, 4)]
+    if net != "vgg":
+        raise ValueError("LPIPS backbone %r: 'alex' or 'vgg'" % (net,))
+    out, cin, tap = [], 3, 0
+    for idx, width in zip((0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28),
+                          (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)):
+        is_tap = idx in (2, 7, 14, 21, 28)
+        out.append((idx, cin, width, 3, 1, 1, 2 if idx in (5, 10, 17, 24) else 0, tap if is_tap else -1))
+        tap += int(is_tap)
+        cin = width
+    return out
+
+
+def lpips_tap_shapes(net, H, W):
+    """[(C, h, w)] of the five taps for an H x W input"""
+    shapes, h, w = [], H, W
+    for _, _, cout, k, stride, pad, pool, tap in lpips_layers(net):
+        if pool == 2:
+            h, w = h // 2, w // 2
+        elif pool == 3:
+            h, w = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+        h, w = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+        if tap >= 0:
+            shapes.append((cout, h, w))
+    return shapes
+
+
+def lpips_pair_bytes(net, H, W):
+    """Arena high-water of cd_lpips per PAIR of H x W images (16-bit activations; lpips.hip's allocation order: the input
+    rows, then per stage the next stage's pooled input ahead of the stage's own conv outputs, which are released behind the
+    pool). The per-image partial sums of k_lpips_layer (a few KB) are not counted."""
+    layers = lpips_layers(net)
+    held = H * W * 32  # elements per image that stay allocated
+    peak, h, w, i = held, H, W, 0
+    while i < len(layers):
+        e = i
+        while layers[e][7] < 0:
+            e += 1
+        sizes, hh, ww = [], h, w
+        for _, _, cout, k, stride, pad, _, _ in layers[i:e + 1]:
+            hh, ww = (hh + 2 * pad - k) // stride + 1, (ww + 2 * pad - k) // stride + 1
+            sizes.append(cout * hh * ww)
+        pool = layers[e + 1][6] if e + 1 < len(layers) else 0
+        if pool:
+            h, w = (hh // 2, ww // 2) if pool == 2 else ((hh - 3) // 2 + 1, (ww - 3) // 2 + 1)
+            held += layers[e][2] * h * w
+            peak = max(peak, held + sum(sizes))
+        else:
+            h, w = hh, ww
+            held += sum(sizes)
+            peak = max(peak, held)
+        i = e + 1
+    return 2 * 2 * peak  # two images, two bytes per element
+
+
+def lpips_synthetic_state_dict(net="alex", seed=0):
+    """Seeded synthetic LPIPS weights in the engine's naming (`features.N.weight|bias`, `lin{l}.weight`): He-normal convs
+    (std sqrt(2 / fan_in)), small biases, and NON-NEGATIVE `lin` weights of mean about 1 / C (as the trained ones are
+    non-negative), so that activations and the five terms stay at scale through all 13 layers."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for idx, cin, cout, k, _, _, _, tap in lpips_layers(net):
+        sd["features.%d.weight" % idx] = torch.randn((cout, cin, k, k), generator=g) * float(np.sqrt(2.0 / (cin * k * k)))
+        sd["features.%d.bias" % idx] = 0.05 * torch.randn(cout, generator=g)
+        if tap >= 0:
+            sd["lin%d.weight" % tap] = (2.0 / cout) * torch.rand((1, cout, 1, 1), generator=g)
+    return sd
+
+
+def lpips_engine_state_dict(sd):
+    """Either checkpoint layout -> the engine's naming. A full `lpips.LPIPS(net=...)` state_dict has
+    `net.slice{k}.{N}.weight|bias` (N = the torchvision `features` index), `lin{l}.model.1.weight`, the same again under
+    `lins.{l}.*`, and `scaling_layer.shift|scale`; the alternative is a torchvision backbone state_dict (`features.N.*`,
+    `classifier.*`) merged with the package's linear file (`lin{l}.model.1.weight`). `lins.*`, `classifier.*` and
+    `scaling_layer.*` are skipped; the scaling constants, when present, must be the ones the engine applies."""
+    out = {}
+    for k, v in sd.items():
+        if k.startswith(("lins.", "classifier.")) or k.endswith(".num_batches_tracked"):
+            continue
+        if k.startswith("scaling_layer."):
+            want = LPIPS_SHIFT if k.endswith("shift") else LPIPS_SCALE
+            got = [float(t) for t in torch.as_tensor(v).flatten()]
+            assert len(got) == 3 and all(abs(a - b) < 1e-6 for a, b in zip(got, want)), (k, got)
+            continue
+        parts = k.split(".")
+        if parts[0] == "net" and parts[1].startswith("slice"):
+            k = "features." + ".".join(parts[2:])
+        elif parts[0].startswith("lin") and parts[1:] == ["model", "1", "weight"]:
+            k = parts[0] + ".weight"
+        out[k] = v
+    return out
+
+
 class Engine:
     """One engine per rank / stream (cd_engine_create)."""
 
@@ -192,6 +305,7 @@ class Engine:
             # the bump arena is reserved up front: 32 GB covers the largest folded-ensemble VAE decode (32 images
             # at 512x512) many times over and leaves room for several engines per GPU (bench.py replicas)
             workspace_bytes = int(min(32 << 30, free * 0.45))
+        self.workspace_bytes = int(workspace_bytes)
         self.stream = torch.cuda.current_stream(self.device)
         h = C.c_void_p()
         check(self.lib.cd_engine_create(C.c_void_p(self.stream.cuda_stream), C.c_size_t(workspace_bytes), C.byref(h)))
@@ -355,6 +469,39 @@ class Engine:
             shape = (B,) + INCEPTION_BLOCK_SHAPES[stop_block]
         out = torch.empty(shape, device=img.device, dtype=torch.float32)
         check(self.lib.cd_inception_features(self.h, net, ptr(img), B, int(stop_block), ptr(out)))
+        return out
+
+    def load_lpips_state_dict(self, net, sd):
+        """LPIPS weights in either checkpoint layout or the engine's own naming (lpips_engine_state_dict). Raises KeyError
+        on a missing tensor."""
+        n, first = self.load_state_dict(net, lpips_engine_state_dict(sd), strict=True)
+        if n:
+            raise KeyError("LPIPS state_dict lacks %d tensors, first: %s" % (n, first))
+
+    def _lpips_name(self, net):
+        return "alex" if self._descs[net].num_res_blocks == 5 else "vgg"
+
+    def lpips(self, net, img0, img1, per_layer=False):
+        """cd_lpips: [B, 3, H, W] fp32 in [-1, 1], twice -> the LPIPS distance [B] (and the five tap terms [B, 5])."""
+        img0, img1 = self._f32(img0), self._f32(img1)
+        assert img0.dim() == 4 and img0.shape[1] == 3 and img0.shape == img1.shape, (img0.shape, img1.shape)
+        B, _, H, W = img0.shape
+        out = torch.empty((B,), device=img0.device, dtype=torch.float32)
+        layers = torch.empty((B, 5), device=img0.device, dtype=torch.float32) if per_layer else None
+        check(self.lib.cd_lpips(self.h, net, ptr(img0), ptr(img1), B, H, W, ptr(layers), ptr(out)))
+        return (out, layers) if per_layer else out
+
+    def lpips_tap(self, net, img, tap):
+        """cd_lpips_tap: the un-normalised ReLU output of tap 0..4 as fp32 NCHW."""
+        img = self._f32(img)
+        assert img.dim() == 4 and img.shape[1] == 3, img.shape
+        B, _, H, W = img.shape
+        if not 0 <= int(tap) < 5:
+            raise ValueError("LPIPS tap %r outside 0..4" % (tap,))
+        shapes = lpips_tap_shapes(self._lpips_name(net), H, W)
+        shape = shapes[int(tap)] if min(shapes[-1]) > 0 else (1, 1, 1)  # too small: the engine refuses and names the minimum
+        out = torch.empty((B,) + tuple(shape), device=img.device, dtype=torch.float32)
+        check(self.lib.cd_lpips_tap(self.h, net, ptr(img), B, H, W, int(tap), ptr(out)))
         return out
 
     def vae_encode(self, net, img, noise=None, seed=0, sample=True, scale=0.18215):

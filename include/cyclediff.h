@@ -28,7 +28,7 @@ extern "C" {
 typedef struct cd_engine* cd_handle;
 
 enum { CD_NET_UNET_OPENAI = 1, CD_NET_UNET_HO = 2, CD_NET_VAE_KL = 3, CD_NET_CLIP_TEXT = 4, CD_NET_BERT_XTR = 5,
-       CD_NET_OCLIP_TEXT = 6, CD_NET_OCLIP_VISION = 7, CD_NET_INCEPTION_FID = 8 };
+       CD_NET_OCLIP_TEXT = 6, CD_NET_OCLIP_VISION = 7, CD_NET_INCEPTION_FID = 8, CD_NET_LPIPS = 9 };
 enum { CD_SCHED_DDIM = 0, CD_SCHED_DDPM = 1 };
 enum { CD_PREC_16 = 0, CD_PREC_F32 = 1, CD_PREC_F32X3 = 2 };
 /* what a keep-mask holds its region to: q_sample(x0, t) freshly noised per step (the reference, ddim.py:427-430), or the
@@ -58,7 +58,12 @@ enum { CD_MASK_QSAMPLE = 0, CD_MASK_ENCODER = 1 };
  *                 CD_PREC_16 (the only one implemented), no other field is read. Weights keyed by that network's
  *                 state_dict names, `X.conv.weight`, `X.bn.weight`, `X.bn.bias`, `X.bn.running_mean`, `X.bn.running_var`
  *                 for every BasicConv2d X (`Conv2d_1a_3x3`, `Mixed_5b.branch1x1`, ...); BatchNorm (eps 1e-3) is folded
- *                 into the packed weights inside the engine before the next forward */
+ *                 into the packed weights inside the engine before the next forward
+ *   LPIPS       : the perceptual distance LPIPS v0.1 on the torchvision AlexNet or VGG16 `features` stack; descriptor field
+ *                 reused: num_res_blocks = number of convs, which selects the backbone (5 = AlexNet, 13 = VGG16); precision =
+ *                 CD_PREC_16 (the only one implemented); no image_size (any H x W from 31 / 16 up), no other field is read.
+ *                 Weights keyed `features.N.weight`, `features.N.bias` (N = the torchvision `features` index of the conv) and
+ *                 `lin{l}.weight` [1, C_l, 1, 1] for the five taps l */
 typedef struct cd_net_desc {
   int kind;
   int image_size;          /* spatial size of the network input (latent 64, pixel 256, ...)      */
@@ -151,6 +156,12 @@ int cd_text_encode(cd_handle h, int net, const int32_t* tokens, int B, int L, fl
  * (256/288/288x35x35), 10 Mixed_6a (768x17x17), 11-14 Mixed_6b..6e (768x17x17), 15 Mixed_7a (1280x8x8), 16-17 Mixed_7b/7c
  * (2048x8x8). */
 int cd_inception_features(cd_handle h, int net, const float* img, int B, int stop_block, float* out);
+/* LPIPS v0.1 (the `lpips` package's `LPIPS(net=...)(x0, x1)`, spatial=False): img0, img1 [B,3,H,W] fp32 in [-1,1] -> out [B];
+ * per_layer (or NULL) [B,5] = the five tap terms whose sum (in tap order) is out. Both images run as one batch of 2 B.
+ * Refused before any launch: B < 1, H or W below 31 (alex) / 16 (vgg) - a tap would be empty. */
+int cd_lpips(cd_handle h, int net, const float* img0, const float* img1, int B, int H, int W, float* per_layer, float* out);
+/* the un-normalised ReLU output of tap 0..4 of the backbone (scaling layer included) as fp32 NCHW [B,C_tap,H_tap,W_tap] */
+int cd_lpips_tap(cd_handle h, int net, const float* img, int B, int H, int W, int tap, float* out);
 int cd_clip_text_features(cd_handle h, int net, const int32_t* tokens, int B, int L, float* out);
 int cd_clip_image_features(cd_handle h, int net, const float* img, int B, float* out);
 
@@ -609,6 +620,15 @@ int cd_op_global_avg(cd_handle h, const float* x, int B, int HW, int C, int in_p
 int cd_op_basic_conv(cd_handle h, const float* x, int B, int Cin, int H, int W, int in_ld, const float* w, const float* gamma,
                      const float* beta, const float* mean, const float* var, int N, int KH, int KW, int stride, int pad_t,
                      int pad_l, int out_off, int out_ld, int tile, float* y, float* w_packed, float* bias_out);
+/* ---- the kernels of LPIPS (csrc/lpips.hip), one at a time, test-only; NaN / 0xFF guards as above ----
+ * one tap's distance: f0, f1 fp32 [B][HW][C] (pixel rows), stored 16-bit with row stride C + in_pad (pad columns NaN, a 64-row
+ * block of 0xFF behind the last row), w fp32 [C] -> out [B] = mean over pixels of sum_c w_c (f0_c / (|f0| + 1e-10) - f1_c /
+ * (|f1| + 1e-10))^2. Refused: C % 8, C > 512, (C + in_pad) % 8. */
+int cd_op_lpips_layer(cd_handle h, const float* f0, const float* f1, const float* w, int B, int HW, int C, int in_pad,
+                      float* out);
+/* the 2 x 2 stride-2 max pool of VGG16 (floor of odd sizes), operands and result laid out as cd_op_pool3x3's: y = the whole
+ * buffer fp32 [B*(H/2)*(W/2) + 64][out_ld]. Refused: C % 8, in_pad % 8, out_off % 8, out_ld % 8, out_off + C > out_ld, H or W < 2. */
+int cd_op_pool2x2(cd_handle h, const float* x, int B, int C, int H, int W, int in_pad, int out_off, int out_ld, float* y);
 /* micro-benchmark of one conv / GEMM shape on synthetic data (scripts/bench_gemm.py): average ms per launch.
  * act: low byte = activation; | 0x100 = in-place residual update of the output; | 0x200 = fused GroupNorm statistics */
 int cd_op_bench_conv(cd_handle h, int B, int H, int W, int C0, int C1, int N, int k, int stride, int up,

@@ -135,6 +135,12 @@ def main(argv=None):
     ap.add_argument("--fid_inception", default=None,
                     help="Inception-v3 state_dict for FID / KID (pytorch-fid pt_inception-2015-12-05-*.pth; default "
                          "CYCLEDIFF_FID_INCEPTION, or seeded synthetic weights with --synthetic-weights)")
+    ap.add_argument("--lpips", default=None, choices=("alex", "vgg"),
+                    help="adds per-sample LPIPS v0.1 of the written output against the source image (at the wrapper's "
+                         "resolution) to metrics.json, and `lpips_keep` for samples with a keep-mask; backbone on the engine")
+    ap.add_argument("--lpips_weights", default=None, metavar="PATH[,PATH]",
+                    help="LPIPS weights: one full lpips.LPIPS state_dict, or backbone.pth,linear.pth (default "
+                         "CYCLEDIFF_LPIPS_WEIGHTS, or seeded synthetic weights with --synthetic-weights)")
     ap.add_argument("--save_masks", action="store_true",
                     help="`[gan] auto_mask = diffedit`: also write every sample's estimated keep-mask, upsampled to the image "
                          "(white = kept), as <id>_mask.png beside its image")
@@ -184,12 +190,16 @@ def main(argv=None):
 
     fid_net = fid_origin = ranker = None
     engine = getattr(wrapper, "engine", None)
-    if a.fid_ref_dir or a.text_metrics:
+    lpips_net = lpips_origin = None
+    if a.fid_ref_dir or a.text_metrics or a.lpips:
         from cycle_diffusion_amd.runtime import get_engine
         engine = engine or get_engine(dev)
     if a.fid_ref_dir:
         from cycle_diffusion_amd.utils import fid
         fid_net, fid_origin = fid.load_inception(engine, a.fid_inception)
+    if a.lpips:
+        from cycle_diffusion_amd.utils import lpips
+        lpips_net, lpips_origin = lpips.load_lpips(engine, a.lpips, a.lpips_weights)
     if a.text_metrics:
         from cycle_diffusion_amd.utils import text_metrics
         ranker = getattr(wrapper, "ranker", None)
@@ -203,6 +213,17 @@ def main(argv=None):
             grid_pairs.append((orig.detach().clamp(0, 1).cpu(), img.detach().clamp(0, 1).cpu()))
         keep = [j for j in range(img.shape[0]) if not batch["is_padding"][j]]
         feats = fid.features(engine, fid_net, img[keep]) if fid_net is not None and keep else None
+        lp = lp_keep = None
+        if lpips_net is not None and keep:
+            lp = lpips.distance(engine, lpips_net, img[keep], orig[keep])
+            # this project's definition: both images times the keep-mask in [-1, 1] space (the edit region mid-grey in both)
+            km = [batch["mask"][j] if "mask" in batch and batch["has_mask"][j] else
+                  batch["auto_keep"][j] if "auto_keep" in batch else None for j in keep]
+            sel = [i for i, m in enumerate(km) if m is not None]
+            if sel:
+                idx = [keep[i] for i in sel]
+                d = lpips.distance_keep(engine, lpips_net, img[idx], orig[idx], torch.stack([km[i] for i in sel]))
+                lp_keep = {keep[i]: float(v) for i, v in zip(sel, d)}
         heat = None
         if a.word_maps and "encode_text" in batch and hasattr(wrapper, "word_maps"):
             heat = word_map_images(wrapper, orig, batch["decode_text"], batch["encode_text"], a.seed)
@@ -236,6 +257,10 @@ def main(argv=None):
                     from PIL import Image
                     Image.fromarray((batch["auto_keep"][j, 0].numpy() * 255).astype("uint8")).save(
                         os.path.join(a.output_dir, "%06d_mask.png" % sid))
+            if lp is not None:
+                row["lpips"] = float(lp[keep.index(j)])
+                if lp_keep is not None and j in lp_keep:
+                    row["lpips_keep"] = lp_keep[j]
             if scores is not None:
                 row["clip"], row["d-clip"] = scores[0][j], scores[1][j]
             if feats is not None:
@@ -261,7 +286,7 @@ def main(argv=None):
         assert len({r["sample_id"] for r in rows}) == len(rows)  # padding rows were skipped where they were produced
         rows.sort(key=lambda r: r["sample_id"])
         summary = {k: sum(r[k] for r in rows) / max(1, len(rows)) for k in ("psnr", "ssim", "l2")}
-        for k in ("psnr_keep", "psnr_edit", "edit_fraction"):  # only when masked / auto-masked samples exist
+        for k in ("psnr_keep", "psnr_edit", "edit_fraction", "lpips_keep"):  # only when masked / auto-masked samples exist
             masked = [r[k] for r in rows if k in r]
             if masked:
                 summary[k] = sum(masked) / len(masked)
@@ -272,6 +297,11 @@ def main(argv=None):
                 for k in ("clip", "d-clip"):
                     summary[k] = sum(r[k] for r in scored) / len(scored)
             extra["text_metrics"] = {"n": len(scored), "weights_origin": getattr(ranker, "weights_origin", None)}
+        if a.lpips:
+            scored = [r["lpips"] for r in rows if "lpips" in r]
+            if scored:
+                summary["lpips"] = sum(scored) / len(scored)
+            extra["lpips_eval"] = {"net": a.lpips, "weights_origin": lpips_origin, "n": len(scored)}
         if fid_net is not None:
             import numpy as np
             gen = np.stack([r.pop("_inception") for r in rows])
