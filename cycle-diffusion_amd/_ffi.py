@@ -40,6 +40,14 @@ class StepCoef(C.Structure):
                 ("sigma", C.c_float), ("r", C.c_float), ("t_mask", C.c_float), ("t", C.c_int32)]
 
 
+class SegaConcept(C.Structure):
+    _fields_ = [("scale", C.c_float), ("weight", C.c_float), ("lo", C.c_int32), ("frac", C.c_float),
+                ("warm", C.c_int32), ("cool", C.c_int32)]
+
+
+SEGA_CONCEPT_DTYPE = np.dtype([("scale", "<f4"), ("weight", "<f4"), ("lo", "<i4"), ("frac", "<f4"), ("warm", "<i4"),
+                               ("cool", "<i4")])
+
 STEP_COEF_DTYPE = np.dtype([("sa", "<f4"), ("s1a", "<f4"), ("sap", "<f4"), ("dirc", "<f4"), ("sigma", "<f4"),
                             ("r", "<f4"), ("t_mask", "<f4"), ("t", "<i4")])
 
@@ -85,6 +93,9 @@ SIGNATURES = {
                                 _VP, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP, _VP, _I, _I, _VP, _VP],
     "cd_cycle_translate_blend": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I,
                                  _VP, _VP, _VP, _I, _I, _VP, _VP, _I, _I, _I, _F, _I, _VP, _VP, _VP, _VP],
+    "cd_cycle_translate_sega": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I,
+                                _VP, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP, _VP, _I, _I, _VP, _VP, _I, _F, _F, _VP, _VP, _VP,
+                                _VP, _VP],
     "cd_ilvr_decode": [_VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _U64, _VP, _I, _I, _I, _VP, _VP, _U64, _VP],
     "cd_automask": [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _F, _F, _VP, _U64, _I, _F, _F, _I, _VP, _VP],
     "cd_word_maps": [_VP, _I, _VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _F, _F, _VP, _U64, _I, _I, _I, _VP, C.POINTER(_I)],
@@ -121,6 +132,7 @@ SIGNATURES = {
     "cd_op_automask_reduce": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _F, _I, _VP, _VP, _VP],
     "cd_op_local_blend_mask": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _VP],
     "cd_op_sched_step_masked": [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, _VP, _VP, _I, _I, _F, _F, _VP, _I, _I, _I, _I, _VP, _I],
+    "cd_op_sega_guidance": [_VP, _VP, _I, _I, _I, _I, _I, _F, _VP, _VP, _I, _F, _F, _VP, _VP, _VP, _VP, _VP],
     "cd_op_layout": [_VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _F, _F, _I],
     "cd_op_resample16": [_VP, _I, _VP, _VP, _I, _I, _I, _I],
     "cd_op_copy_rows16": [_VP, _VP, _I, _VP, _I, _I64, _I],

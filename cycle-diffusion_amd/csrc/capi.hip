@@ -326,6 +326,17 @@ struct BlendArgs {
   float* keep_out = nullptr;  // [n_dec * B, 1, h, w] or NULL
 };
 
+// Arguments of semantic guidance (cd_cycle_translate_sega), checked on the host before any launch
+struct SegaArgs {
+  const float* edit_ctx = nullptr;             // [E * Bd, L, Dc], concept-major
+  const cd_sega_concept* concepts = nullptr;   // [E], host
+  int E = 0;
+  float s_m = 0.f, beta = 0.f;
+  float* tau_out = nullptr;   // [K, Bd, E] or NULL
+  int32_t* kept_out = nullptr;  // [K, Bd, E] or NULL
+  float* mask_out = nullptr;  // [Bd, E, C, H, W] or NULL
+};
+
 struct SamplerState {
   UNet* u = nullptr;
   int B = 0, Bn = 0, C = 0, HW = 0, cpad = 0, out_ld = 0;
@@ -692,8 +703,10 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
                        float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
                        const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
                        uint64_t seed, int last_uses_x0, float* z_out, float* x_out, const MaskArgs* mk,
-                       const CtrlArgs* ck = nullptr, const BlendArgs* bk = nullptr) {
+                       const CtrlArgs* ck = nullptr, const BlendArgs* bk = nullptr, const SegaArgs* sk = nullptr) {
   CD_CHECK(h && x0 && coef_enc_host && coef_dec_host && z_out && x_out && B > 0 && n_dec > 0 && K > 0, "bad argument");
+  CD_CHECK(!(sk && bk), "semantic guidance and the local blend are not built together: call cd_cycle_translate_sega without "
+                        "the blend, or cd_cycle_translate_blend without concepts");
   check_stream_band(noise, K, "cd_cycle_translate: noise");
   if (mk && mk->source == CD_MASK_QSAMPLE) check_stream_band(mk->noise, K, "keep-mask: mask_noise");
   ArenaScope arena_scope(h->arena);
@@ -706,12 +719,23 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
   // what the control and the local blend both need of the call; the blend needs it for every n_ctrl
   const bool text_on = ctrl_on || bk;
   const char* what = ctrl_on ? "cross-attention control" : "the local blend";
-  if (ck || bk) {
+  if (ck || bk || sk) {
     // one forward serves both passes at the timestep of the DECODER's row k: the two tables must agree on it
     for (int k = 0; k < K; ++k)
       CD_CHECK(coef_enc_host[k].t == coef_dec_host[k].t, "%s: the encoder's and the decoder's tables disagree "
-               "on the timestep of row %d (%d against %d)", bk ? "cd_cycle_translate_blend" : "cd_cycle_translate_ctrl", k,
+               "on the timestep of row %d (%d against %d)",
+               sk ? "cd_cycle_translate_sega" : bk ? "cd_cycle_translate_blend" : "cd_cycle_translate_ctrl", k,
                coef_enc_host[k].t, coef_dec_host[k].t);
+  }
+  if (sk) {
+    const char* sg = "semantic guidance";
+    CD_CHECK(sk->E >= 1 && sk->E <= kSegaMaxConcepts, "%s: E = %d concepts outside [1, %d]", sg, sk->E, kSegaMaxConcepts);
+    CD_CHECK(sk->edit_ctx && sk->concepts, "%s: edit_ctx / concepts_host is NULL", sg);
+    CD_CHECK(sched_kind == CD_SCHED_DDIM, "%s is only defined for sched_kind = CD_SCHED_DDIM", sg);
+    CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer && u->desc.context_dim > 0 && ctx_len > 0,
+             "%s needs a network with a text context: the concepts are contexts", sg);
+    CD_CHECK(!u->f32, "%s is not built for precision CD_PREC_F32 / CD_PREC_F32X3 networks: use the 16-bit precision", sg);
+    check_sega_params(sk->concepts, sk->E, (int64_t)u->desc.in_channels * u->image_size * u->image_size, K, sk->s_m, sk->beta);
   }
   if (text_on) {
     CD_CHECK(sched_kind == CD_SCHED_DDIM, "%s is only defined for sched_kind = CD_SCHED_DDIM", what);
@@ -755,7 +779,13 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
   CD_CHECK(sched_kind == CD_SCHED_DDIM || (!ge.cfg && !gd.cfg), "classifier-free guidance is only implemented for sched_kind = CD_SCHED_DDIM");
   const bool has_ctx = enc_ctx_c || enc_ctx_uc;
   CD_CHECK(has_ctx == (dec_ctx_c || dec_ctx_uc), "cd_cycle_translate: contexts for both passes or for neither");
-  const int Ben = ge.cfg ? 2 * B : B, Bdn = gd.cfg ? 2 * Bd : Bd, Bn = Ben + Bdn;
+  if (sk)
+    CD_CHECK(gd.cfg, "semantic guidance: dec_guidance = %g (or a missing context) leaves the decoder pass without its "
+                     "unconditional or its conditional rows; the concept directions are taken against the unconditional row",
+             (double)dec_guidance);
+  // decoder batch rows under semantic guidance: [uncond Bd | concept 0 Bd | ... | concept E-1 Bd | cond Bd]
+  const int E = sk ? sk->E : 0;
+  const int Ben = ge.cfg ? 2 * B : B, Bdn = gd.cfg ? (2 + E) * Bd : Bd, Bn = Ben + Bdn;
   Ctx c = h->ctx();
   if (has_ctx) {
     const int Dc = u->desc.context_dim;
@@ -764,7 +794,11 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     void* cx = h->arena.alloc((size_t)Bn * ctx_len * Dc * (f32 ? 4 : 2));
     auto put = [&](const float* src, int rows, size_t row0) { put_ctx(h, u, src, cx, row0, rows, ctx_len, Dc); };
     if (ge.cfg) { put(enc_ctx_uc, B, 0); put(enc_ctx_c, B, B); } else put(ge.ctx_single, B, 0);
-    if (gd.cfg) { put(dec_ctx_uc, Bd, Ben); put(dec_ctx_c, Bd, Ben + Bd); } else put(gd.ctx_single, Bd, Ben);
+    if (gd.cfg) {
+      put(dec_ctx_uc, Bd, Ben);
+      if (sk) put(sk->edit_ctx, E * Bd, Ben + Bd);  // concept-major, as the rows lie
+      put(dec_ctx_c, Bd, Ben + (size_t)(1 + E) * Bd);
+    } else put(gd.ctx_single, Bd, Ben);
     u->set_context(c, (const bf16_t*)cx, Bn, ctx_len);
   } else {
     CD_CHECK(u->desc.context_dim <= 0 || !u->desc.use_spatial_transformer, "network expects a cross-attention context");
@@ -817,8 +851,27 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
   enc.gauss.seed = seed; enc.z.bstride = zbs;
   dec.xt = xt_d;
   dec.geom.B = Bd; dec.geom.C = C; dec.geom.HW = HW; dec.geom.tab = tab_d;
-  dec.xin.xin = xin_d; dec.xin.cpad = cpad; dec.xin.dup = gd.cfg ? 1 : 0;
+  dec.xin.xin = xin_d; dec.xin.cpad = cpad; dec.xin.dup = gd.cfg ? 1 + E : 0;  // every concept row's input is the row's latent
   dec.gauss.seed = seed; dec.eps.bstride = zbs; dec.eps.bmod = n_dec > 1 ? B : 0;
+  // semantic guidance: two launches between the forward and the decode step turn u, c and the concept rows into the eps the
+  // step reads - fp32 NCHW, no combine left to do (cfg = 0); no step kernel's arithmetic changes
+  SegaStep sg;
+  if (sk) {
+    sg.eh = eh_d;
+    sg.Bd = Bd; sg.C = C; sg.HW = HW; sg.E = E;
+    sg.tab = (const SegaConcept*)upload_table(h, sk->concepts, (size_t)E * sizeof(SegaConcept));
+    sg.abuf = (float*)h->arena.alloc((size_t)Bd * E * chw * 4);
+    sg.tau = (float*)h->arena.alloc((size_t)K * Bd * E * 4);  // [K, Bd, E]: 0 where the concept is inactive
+    sg.kept = (int*)h->arena.alloc((size_t)K * Bd * E * 4);
+    sg.nu = (float*)h->arena.alloc((size_t)Bd * chw * 4);     // zero before iteration 0, nothing kept between calls
+    sg.eps = (float*)h->arena.alloc((size_t)Bd * chw * 4);
+    sg.s_m = sk->s_m; sg.beta = sk->beta;
+    HIP_CHECK(hipMemsetAsync(sg.tau, 0, (size_t)K * Bd * E * 4, h->st));
+    HIP_CHECK(hipMemsetAsync(sg.kept, 0, (size_t)K * Bd * E * 4, h->st));
+    HIP_CHECK(hipMemsetAsync(sg.nu, 0, (size_t)Bd * chw * 4, h->st));
+    if (sk->mask_out) HIP_CHECK(hipMemsetAsync(sk->mask_out, 0, (size_t)Bd * E * chw * 4, h->st));
+    eh_d.p = sg.eps; eh_d.sb = chw; eh_d.sc = HW; eh_d.sp = 1; eh_d.cfg = 0; eh_d.gvec = nullptr;
+  }
   // x_T (ddim.py:477-479), z[:, 0]; the decoder starts from the same tensor (sd_wrapper:153), once per decoder scale
   enc.geom.step = K; enc.gauss.noise = noise; enc.gauss.stream = 0u; enc.z.p = z_out;
   launch_init_xt(h->st, enc);
@@ -834,10 +887,11 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     return b;
   };
   if (mk) launch_mask_blend_init(h->st, dec, blend_of(K - 1, 0));
-  else if (!f32) launch_nchw_to_nhwc(h->st, xt_d, xin_d, Bd, C, HW, cpad, 1.f, 0.f, gd.cfg ? 1 : 0);
+  else if (!f32) launch_nchw_to_nhwc(h->st, xt_d, xin_d, Bd, C, HW, cpad, 1.f, 0.f, gd.cfg ? 1 + E : 0);
   // rows that repeat the rows just ahead of them (the decoder's cond half repeats its uncond half): the network computes
   // everything ahead of the first cross-attention once for them - only when the encoder half has no such pair of its own
-  const int dup_tail = (gd.cfg && !ge.cfg) ? Bd : 0;
+  // (not under semantic guidance: the shared prefix covers one pair of halves, not the concept rows between them)
+  const int dup_tail = (gd.cfg && !ge.cfg && !sk) ? Bd : 0;
   for (int i = 0; i < K; ++i) {
     const int k = K - 1 - i;
     if (f32) {
@@ -858,6 +912,13 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     enc.gauss.noise = nz; enc.gauss.stream = (uint32_t)(1 + i); enc.z.p = zslot;
     launch_encode_step(h->st, sched_kind, enc);
     dec.geom.step = k; dec.eps.p = zslot; dec.gauss.stream = (uint32_t)(0x1000 + i);
+    if (sk) {
+      SegaStep it = sg;
+      it.active = sega_active_mask(sk->concepts, E, i);
+      it.tau = sg.tau + (size_t)i * Bd * E; it.kept = sg.kept + (size_t)i * Bd * E;
+      it.mask_out = it.active ? sk->mask_out : nullptr;  // the mask of the last iteration in which a concept was active
+      launch_sega_guidance(h->st, it);
+    }
     if (mk) {
       const MaskBlend next = blend_of(k - 1, i + 1);
       launch_decode_step(h->st, sched_kind, dec, &next, /*blend=*/k > 0);
@@ -877,6 +938,10 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     h->pacer.tick(h->st);
   }
   HIP_CHECK(hipMemcpyAsync(x_out, xt_d, (size_t)Bd * chw * 4, hipMemcpyDeviceToDevice, h->st));
+  if (sk && sk->tau_out)
+    HIP_CHECK(hipMemcpyAsync(sk->tau_out, sg.tau, (size_t)K * Bd * E * 4, hipMemcpyDeviceToDevice, h->st));
+  if (sk && sk->kept_out)
+    HIP_CHECK(hipMemcpyAsync(sk->kept_out, sg.kept, (size_t)K * Bd * E * 4, hipMemcpyDeviceToDevice, h->st));
   if (bk && bk->acc_out)
     HIP_CHECK(hipMemcpyAsync(bk->acc_out, acc, (size_t)(B + Bd) * bk->side * bk->side * 4, hipMemcpyDeviceToDevice, h->st));
   if (bk && bk->keep_out)
@@ -955,6 +1020,33 @@ int cd_cycle_translate_blend(cd_handle h, int net, int sched_kind, const float* 
   cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
                        dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
                        z_out, x_out, nullptr, &ck, &bk);
+  CD_API_END
+}
+
+// The coupled loop with semantic guidance on its decoder rows: E concept rows per decoder row ride in the same
+// forward, and k_sega_threshold / k_sega_combine (sega.hip) build the eps of the unchanged decode step from them. With or
+// without a keep-mask and cross-attention control.
+int cd_cycle_translate_sega(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
+                            const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
+                            float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
+                            const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
+                            uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
+                            int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
+                            const float* mapper, const float* alpha, const float* weight, int B_ctrl, int n_ctrl,
+                            const float* edit_ctx, const cd_sega_concept* concepts_host, int E, float momentum_scale,
+                            float momentum_beta, float* tau_out, int32_t* kept_out, float* mask_out, float* z_out,
+                            float* x_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  const MaskArgs mk = mask_args_of(mask, mask_x0, B_mask, mask_source, qsample_coef_host, mask_noise, mask_seed);
+  CtrlArgs ck;
+  ck.mapper = mapper; ck.alpha = alpha; ck.weight = weight; ck.B_ctrl = B_ctrl; ck.n_ctrl = n_ctrl;
+  SegaArgs sk;
+  sk.edit_ctx = edit_ctx; sk.concepts = concepts_host; sk.E = E; sk.s_m = momentum_scale; sk.beta = momentum_beta;
+  sk.tau_out = tau_out; sk.kept_out = kept_out; sk.mask_out = mask_out;
+  cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
+                       dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
+                       z_out, x_out, mask ? &mk : nullptr, &ck, nullptr, &sk);
   CD_API_END
 }
 
@@ -1073,6 +1165,26 @@ int cd_ilvr_decode(cd_handle h, int net, int sched_kind, const float* z, int z_s
 
 // ---- keep-mask estimation (csrc/automask.hip)
 // the parameters cd_automask and cd_op_automask_reduce (capi_ops.hip) share, each refused by name
+void check_sega_params(const cd_sega_concept* cp, int E, int64_t N, int K, float momentum_scale, float momentum_beta) {
+  static_assert(sizeof(cd_sega_concept) == sizeof(SegaConcept), "concept ABI");
+  const char* sg = "semantic guidance";
+  CD_CHECK(E >= 1 && E <= kSegaMaxConcepts, "%s: E = %d concepts outside [1, %d]", sg, E, kSegaMaxConcepts);
+  CD_CHECK(cp, "%s: concepts_host is NULL", sg);
+  CD_CHECK(std::isfinite(momentum_scale), "%s: momentum_scale is not finite", sg);
+  CD_CHECK(std::isfinite(momentum_beta) && momentum_beta >= 0.f && momentum_beta <= 1.f,
+           "%s: momentum_beta = %g outside [0, 1]", sg, (double)momentum_beta);
+  for (int e = 0; e < E; ++e) {
+    CD_CHECK(std::isfinite(cp[e].scale), "%s: the scale of concept %d is not finite", sg, e);
+    CD_CHECK(std::isfinite(cp[e].weight), "%s: the weight of concept %d is not finite", sg, e);
+    CD_CHECK(cp[e].lo >= 0 && cp[e].lo <= N - 1, "%s: lo = %d of concept %d outside [0, N - 1 = %lld]", sg, cp[e].lo, e,
+             (long long)(N - 1));
+    CD_CHECK(cp[e].frac >= 0.f && cp[e].frac < 1.f, "%s: frac = %g of concept %d outside [0, 1)", sg, (double)cp[e].frac, e);
+    CD_CHECK(cp[e].warm >= 0 && cp[e].warm <= cp[e].cool && (K < 0 || cp[e].cool <= K),
+             "%s: warm = %d / cool = %d of concept %d outside 0 <= warm <= cool <= K (K = %d; negative: unbounded)", sg,
+             cp[e].warm, cp[e].cool, e, K);
+  }
+}
+
 void check_automask_params(int n_draws, float ratio, float thr, int dilate) {
   CD_CHECK(n_draws >= 1 && n_draws <= kStreamBandSteps, "keep-mask estimate: n_draws must lie in [1, %d] (the width of its stream "
                                                         "band), got %d", kStreamBandSteps, n_draws);

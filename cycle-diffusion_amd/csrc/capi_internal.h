@@ -162,4 +162,11 @@ StepCoef* upload_coef(cd_engine* h, const cd_step_coef* host, int n);
 LowpassTaps upload_taps(cd_engine* h, int n_in, int n_out);             // ILVR's resampling taps
 void check_lowpass_geometry(int R, int down_n);
 void check_automask_params(int n_draws, float ratio, float thr, int dilate);
+// semantic guidance's concept rows and momentum; K < 0: no loop length to hold warm / cool against
+void check_sega_params(const cd_sega_concept* concepts_host, int E, int64_t N, int K, float momentum_scale, float momentum_beta);
+inline uint32_t sega_active_mask(const cd_sega_concept* cp, int E, int i) {  // bit e: warm_e <= i < cool_e
+  uint32_t m = 0;
+  for (int e = 0; e < E; ++e) m |= (cp[e].warm <= i && i < cp[e].cool) ? 1u << e : 0u;
+  return m;
+}
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }

@@ -651,6 +651,34 @@ int cd_op_sched_step_masked(cd_handle h, int mode, const cd_step_coef* coef_host
   CD_API_END
 }
 
+int cd_op_sega_guidance(cd_handle h, const float* eps_all, int Bd, int C, int HW, int E, int ld, float guidance,
+                        const float* guidance_per_sample, const cd_sega_concept* concepts_host, int iteration,
+                        float momentum_scale, float momentum_beta, float* nu, float* eps_out, float* tau_out,
+                        int32_t* kept_out, float* mask_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && eps_all && nu && eps_out && tau_out && kept_out && Bd > 0 && C > 0 && HW > 0 && iteration >= 0, "bad argument");
+  CD_CHECK(ld >= C, "semantic guidance: ld = %d below C = %d", ld, C);
+  check_sega_params(concepts_host, E, (int64_t)C * HW, -1, momentum_scale, momentum_beta);
+  ArenaScope arena_scope(h->arena);
+  const int rows = (2 + E) * Bd;
+  float* nhwc = (float*)h->arena.alloc((size_t)rows * HW * ld * 4);
+  launch_nchw_to_nhwc_f32(h->st, eps_all, nhwc, rows, C, HW, ld, 1.f, 0.f);
+  SegaStep a;
+  a.eh.p = nhwc; a.eh.sb = (int64_t)HW * ld; a.eh.sc = 1; a.eh.sp = ld; a.eh.g = guidance; a.eh.gvec = guidance_per_sample;
+  a.Bd = Bd; a.C = C; a.HW = HW; a.E = E;
+  a.active = sega_active_mask(concepts_host, E, iteration);
+  a.tab = (const SegaConcept*)upload_table(h, concepts_host, (size_t)E * sizeof(SegaConcept));
+  a.abuf = (float*)h->arena.alloc((size_t)Bd * E * C * HW * 4);
+  a.tau = tau_out; a.kept = kept_out; a.nu = nu; a.eps = eps_out; a.mask_out = mask_out;
+  a.s_m = momentum_scale; a.beta = momentum_beta;
+  HIP_CHECK(hipMemsetAsync(tau_out, 0, (size_t)Bd * E * 4, h->st));
+  HIP_CHECK(hipMemsetAsync(kept_out, 0, (size_t)Bd * E * 4, h->st));
+  launch_sega_guidance(h->st, a);
+  HIP_CHECK(hipStreamSynchronize(h->st));
+  CD_API_END
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------ hardware layout probes

@@ -23,7 +23,7 @@ __global__ void k_nchw_to_nhwc(const float* __restrict__ x, bf16_t* __restrict__
     if (c < C) v = x[((int64_t)b * C + c) * HW + pix] * scale + shift;
     const bf16_t h = f2bf(v);
     y[i] = h;
-    if (dup) y[i + n] = h;
+    for (int j = 1; j <= dup; ++j) y[i + (int64_t)j * n] = h;
   }
 }
 

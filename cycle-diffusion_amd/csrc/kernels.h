@@ -42,7 +42,9 @@ struct GaussSrc {  // a standard-normal draw per element: the tensor [B, C, HW],
 struct XinOut {  // the next forward's 16-bit NHWC input [B, HW, cpad], or null -> not written
   bf16_t* xin = nullptr;
   int cpad = 0;
-  int dup = 0;  // 1: written again B samples on (the classifier-free-guidance batch [uncond | cond] of one x_t)
+  int dup = 0;  // n: written n more times, each B samples on (1: the classifier-free-guidance batch [uncond | cond] of one
+                // x_t; 1 + E: semantic guidance's [uncond | E concepts | cond] - the step kernels of sched.hip only: the
+                // ILVR and keep-mask-estimate kernels take 0 / 1)
 };
 struct EpsIn {  // injected eps (decode only): sample b at p[b * bstride], or null -> drawn from the GaussSrc
   const float* p = nullptr;
@@ -85,6 +87,32 @@ void launch_decode_step(hipStream_t st, int kind, const StepArgs& a, const MaskB
 void launch_mask_blend_init(hipStream_t st, const StepArgs& a, const MaskBlend& mk);
 // out[i] = the draw of element first + i from g, i < n (cd_op_gauss: the generator as the tests see it)
 void launch_gauss_fill(hipStream_t st, GaussSrc g, int64_t first, float* out, int64_t n);
+
+// ---------------------------------------------------------------- semantic guidance (sega.hip)
+constexpr int kSegaMaxConcepts = 8;
+struct SegaConcept {  // == cd_sega_concept: one edit concept, its threshold as the two order statistics' rank and weight
+  float scale, weight;  // s_e (signed: negative steers away), w_e
+  int lo;               // floor(q * (N - 1))
+  float frac;           // q * (N - 1) - lo, in [0, 1)
+  int warm, cool;       // active on iterations warm <= i < cool
+};
+// One iteration's guidance on the Bd decoder rows. eh views the network's output from the decoder's first row on: batch rows
+// [uncond Bd | concept 0 Bd | ... | concept E-1 Bd | cond Bd]; eh.g / eh.gvec the row's guidance scale (eh.cfg is not read).
+struct SegaStep {
+  EpsHat eh;
+  int Bd = 0, C = 0, HW = 0, E = 0;
+  uint32_t active = 0;               // bit e: concept e is active in this iteration
+  const SegaConcept* tab = nullptr;  // [E], device
+  float* abuf = nullptr;             // [Bd * E, C * HW] scratch: |d_e| of the active concepts
+  float* tau = nullptr;              // [Bd, E], written for the active concepts only
+  int* kept = nullptr;               // [Bd, E], #{a >= tau}, likewise
+  float* nu = nullptr;               // [Bd, C, HW] momentum, in / out
+  float* eps = nullptr;              // [Bd, C, HW] fp32 NCHW: what the decode step reads through an EpsHat with cfg = 0
+  float* mask_out = nullptr;         // [Bd, E, C, HW] of 0 / 1 (0 for an inactive concept), or null
+  float s_m = 0.f, beta = 0.f;
+};
+// k_sega_threshold on a (Bd, active concepts) grid - not launched when none is active - then k_sega_combine
+void launch_sega_guidance(hipStream_t st, const SegaStep& a);
 
 // ---------------------------------------------------------------- ILVR low-pass conditioning (ilvr.hip)
 // A resize matrix M [n_out, n_in] as its nonzero taps: row i is w[t * n_out + i] at column first[i] + t, t = 0 .. P-1
@@ -463,7 +491,8 @@ void launch_transpose_v(hipStream_t st, const bf16_t* v, int ldv, int64_t v_bs, 
 void launch_mfma_sustained(hipStream_t st, int target_ms, float* tflops, float* ghz);
 
 // ---------------------------------------------------------------- elementwise (elementwise.hip)
-// fp32 NCHW [B][C][HW] -> bf16 NHWC [B][HW][Cpad] (pad channels zero), y = x*scale + shift
+// fp32 NCHW [B][C][HW] -> bf16 NHWC [B][HW][Cpad] (pad channels zero), y = x*scale + shift; dup: the number of further copies
+// of the B rows written behind them
 void launch_nchw_to_nhwc(hipStream_t st, const float* x, bf16_t* y, int B, int C, int HW, int Cpad,
                          float scale, float shift, int dup);
 // fp32/bf16 NHWC (ld) -> fp32 NCHW, y = x*scale + shift

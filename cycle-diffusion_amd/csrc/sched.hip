@@ -14,43 +14,18 @@
 #include "common.h"
 #include "gauss.h"
 #include "kernels.h"
+#include "sched_elem.h"
 
 namespace cd {
 
 #pragma clang fp contract(off)
-
-// element i = b*C*HW + rem of an NCHW tensor, rem = c*HW + p
-struct Elem {
-  int64_t i, rem;
-  int b, c, p;
-};
-
-// grid-stride loop over the B*C*HW elements
-template <class F>
-__device__ inline void for_each_elem(const StepGeom& g, F f) {
-  const int64_t chw = (int64_t)g.C * g.HW, n = (int64_t)g.B * chw;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    Elem e;
-    e.i = i;
-    e.b = (int)(i / chw);
-    e.rem = i - (int64_t)e.b * chw;
-    e.c = (int)(e.rem / g.HW);
-    e.p = (int)(e.rem - (int64_t)e.c * g.HW);
-    f(e);
-  }
-}
 
 __device__ inline void write_xin(const XinOut& o, const StepGeom& g, const Elem& e, float v) {
   if (!o.xin) return;
   bf16_t h = f2bf(v);
   size_t at = ((size_t)e.b * g.HW + e.p) * o.cpad + e.c;
   o.xin[at] = h;
-  if (o.dup) o.xin[at + (size_t)g.B * g.HW * o.cpad] = h;
-}
-
-__device__ inline float eps_hat_at(const EpsHat& eh, int b, const Elem& e) {
-  return eh.p[(int64_t)b * eh.sb + (int64_t)e.c * eh.sc + (int64_t)e.p * eh.sp];
+  for (int j = 1; j <= o.dup; ++j) o.xin[at + (size_t)j * g.B * g.HW * o.cpad] = h;
 }
 
 // combine classifier-free guidance: e = e_u + g*(e_c - e_u)   (ddim.py:555-559)
@@ -210,11 +185,6 @@ __global__ void k_decode_step_ddpm(StepArgs a) {
     a.xt[el.i] = xn;
     write_xin(a.xin, a.geom, el, xn);
   });
-}
-
-static inline dim3 ew_grid(const StepGeom& g) {
-  int64_t n = ((int64_t)g.B * g.C * g.HW + 255) / 256;
-  return dim3((unsigned)(n > 2048 ? 2048 : (n < 1 ? 1 : n)));
 }
 
 void launch_init_xt(hipStream_t st, const StepArgs& a) {

@@ -598,12 +598,14 @@ class Engine:
 
     def _cycle_translate(self, net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
                          dec_guidance, n_dec, noise, seed, last_uses_x0, mask=None, mask_x0=None, qcoef=None, mask_noise=None,
-                         mask_seed=0, mask_source="q_sample", ctrl=None, blend=None):
+                         mask_seed=0, mask_source="q_sample", ctrl=None, blend=None, sega=None):
         """The marshalling of the coupled entry points: cd_cycle_translate without a mask and without `ctrl`,
         cd_cycle_translate_masked with a mask only, cd_cycle_translate_ctrl with `ctrl` = (mapper, alpha, weight, n_ctrl) - the
         argument list of each is the one before it plus a tail, as cycle_translate_impl serves them from one body.
         cd_cycle_translate_blend with `blend` = (sel_src, sel_tgt, side, pool, thr, n_start) takes the control's tail (none:
-        NULL and n_ctrl = 0) without the mask's, then its own; it returns (z, x, acc, keep)."""
+        NULL and n_ctrl = 0) without the mask's, then its own; it returns (z, x, acc, keep).
+        cd_cycle_translate_sega with `sega` = (edit_ctx, concepts, momentum_scale, momentum_beta) takes the mask's and the
+        control's tails (none: NULL / 0), then its own; it returns (z, x, tau, kept, mask)."""
         x0 = self._f32(x0)
         K = len(coef_dec)
         assert len(coef_enc) == K + 1
@@ -624,7 +626,9 @@ class Engine:
         fn, tail, ctl, sels, outs = self.lib.cd_cycle_translate, [], None, None, ()
         if blend is not None and mask is not None:
             raise ValueError("the local blend rewrites the keep-mask after every step: it takes no mask of the caller's")
-        if blend is None and (mask is not None or ctrl is not None):
+        if blend is not None and sega is not None:
+            raise ValueError("semantic guidance and the local blend are not built together")
+        if blend is None and (mask is not None or ctrl is not None or sega is not None):
             fn = self.lib.cd_cycle_translate_masked
             tail = [ptr(mask), ptr(mask_x0), Bm, src, C.c_void_p(qcoef.ctypes.data) if qcoef is not None else None,
                     ptr(mask_noise), C.c_uint64(mask_seed)]
@@ -636,6 +640,23 @@ class Engine:
                                  % (L, L, L, [tuple(t.shape) for t in ctl]))
             fn = self.lib.cd_cycle_translate_ctrl
             tail += [ptr(ctl[0]), ptr(ctl[1]), ptr(ctl[2]), Bc, int(ctrl[3])]
+        if sega is not None:
+            if ctrl is None:
+                tail += [None, None, None, 0, 0]
+            ectx = self._f32(sega[0])
+            table = np.ascontiguousarray(sega[1], dtype=_ffi.SEGA_CONCEPT_DTYPE)
+            E, Bd = len(table), n_dec * B
+            if ectx.dim() != 3 or ectx.shape[0] != E * Bd or (L and ectx.shape[1] != L):
+                raise ValueError("edit_ctx must be [E * n_dec * B = %d, %d, Dc] (concept-major), got %s"
+                                 % (E * Bd, L, tuple(ectx.shape)))
+            tau = torch.empty((K, Bd, E), device=x0.device, dtype=torch.float32)
+            kept = torch.empty((K, Bd, E), device=x0.device, dtype=torch.int32)
+            emask = torch.empty((Bd, E, Cc, H, W), device=x0.device, dtype=torch.float32)
+            fn = self.lib.cd_cycle_translate_sega
+            tail += [ptr(ectx), C.c_void_p(table.ctypes.data), E, C.c_float(sega[2]), C.c_float(sega[3]), ptr(tau), ptr(kept),
+                     ptr(emask)]
+            sels = (ectx, table)
+            outs = (tau, kept, emask)
         if blend is not None:
             if ctrl is None:
                 tail = [None, None, None, 0, 0]
@@ -760,6 +781,41 @@ class Engine:
         return self._cycle_translate(net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
                                      dec_guidance, n_dec, noise, seed, last_uses_x0, ctrl=ctrl,
                                      blend=(sel_src, sel_tgt, side, pool, thr, n_start))
+
+    def cycle_translate_sega(self, net, kind, x0, coef_enc, coef_dec, edit_ctx, concepts, momentum_scale=0.3, momentum_beta=0.6,
+                             ctrl=None, mask=None, mask_x0=None, qcoef=None, mask_noise=None, mask_seed=0,
+                             mask_source="q_sample", enc_ctx_c=None, enc_ctx_uc=None, enc_guidance=1.0, dec_ctx_c=None,
+                             dec_ctx_uc=None, dec_guidance=1.0, n_dec=1, noise=None, seed=0, last_uses_x0=True):
+        """cd_cycle_translate_sega: cycle_translate (or, with mask / ctrl = (mapper, alpha, weight, n_ctrl), its masked /
+        controlled form) with semantic guidance. edit_ctx [E * n_dec * B, L, Dc] concept-major; concepts: E rows of
+        (scale, weight, lo, frac, warm, cool) (semantic_guidance.concept_table). Returns (z, x, tau [K, n_dec * B, E],
+        kept [K, n_dec * B, E] int32, mask [n_dec * B, E, C, H, W] of 0 / 1 from the last iteration with an active concept)."""
+        return self._cycle_translate(net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
+                                     dec_guidance, n_dec, noise, seed, last_uses_x0, mask, mask_x0, qcoef, mask_noise, mask_seed,
+                                     mask_source, ctrl=ctrl, sega=(edit_ctx, concepts, momentum_scale, momentum_beta))
+
+    def op_sega_guidance(self, eps_all, concepts, iteration, nu, guidance=1.0, momentum_scale=0.3, momentum_beta=0.6, ld=None,
+                         want_mask=True):
+        """cd_op_sega_guidance: one iteration's two launches. eps_all [(2 + E) * Bd, C, HW] in batch-row order uncond |
+        concepts | cond, nu [Bd, C, HW] (updated in place) -> (eps [Bd, C, HW], tau [Bd, E], kept [Bd, E] int32, mask
+        [Bd, E, C, HW] or None)."""
+        eps_all, nu = self._f32(eps_all), self._f32(nu)
+        table = np.ascontiguousarray(concepts, dtype=_ffi.SEGA_CONCEPT_DTYPE)
+        E = len(table)
+        rows, Cc, HW = eps_all.shape
+        Bd = rows // (2 + E)
+        if Bd * (2 + E) != rows or tuple(nu.shape) != (Bd, Cc, HW):
+            raise ValueError("eps_all %s / nu %s do not fit E = %d" % (tuple(eps_all.shape), tuple(nu.shape), E))
+        gvec, gscalar = (None, float(guidance)) if isinstance(guidance, (int, float)) else \
+            (torch.as_tensor(guidance, dtype=torch.float32).to(eps_all.device).contiguous(), 1.0)
+        eps = torch.empty((Bd, Cc, HW), device=eps_all.device, dtype=torch.float32)
+        tau = torch.empty((Bd, E), device=eps_all.device, dtype=torch.float32)
+        kept = torch.empty((Bd, E), device=eps_all.device, dtype=torch.int32)
+        mask = torch.empty((Bd, E, Cc, HW), device=eps_all.device, dtype=torch.float32) if want_mask else None
+        check(self.lib.cd_op_sega_guidance(self.h, ptr(eps_all), Bd, Cc, HW, E, Cc if ld is None else int(ld), C.c_float(gscalar),
+                                           ptr(gvec), C.c_void_p(table.ctypes.data), int(iteration), C.c_float(momentum_scale),
+                                           C.c_float(momentum_beta), ptr(nu), ptr(eps), ptr(tau), ptr(kept), ptr(mask)))
+        return eps, tau, kept, mask
 
     def local_blend_mask(self, acc_src, acc_tgt, f=1, pool=3, thr=0.3):
         """cd_op_local_blend_mask: one launch of the blend's mask kernel. acc_src [B, side, side], acc_tgt [Bd, side, side]

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import _ffi, attn_control, schedule
+from .. import semantic_guidance as sgm
 from .. import auto_mask as am
 from ..engine import kl_f8_vae_desc, ldm_text_unet_desc, sd_v1_unet_desc
 from ..runtime import get_engine, load_or_init_weights, read_checkpoint, synthetic_allowed
@@ -80,8 +81,20 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                  noise_on_cpu=False, fold_ensemble=True, ranker_path=None, precision="fp16", couple=True,
                  mask_source="q_sample", cac_steps=0.0, cac_mode="refine", auto_mask=None, auto_mask_draws=10,
                  auto_mask_strength=0.5, auto_mask_ratio=3.0, auto_mask_threshold=0.5, auto_mask_dilate=0, auto_mask_seed=0,
-                 local_blend=None, local_blend_threshold=0.3, local_blend_pool=3, local_blend_side=0, local_blend_start=0.2):
+                 local_blend=None, local_blend_threshold=0.3, local_blend_pool=3, local_blend_side=0, local_blend_start=0.2,
+                 edit_concepts="", edit_momentum_scale=0.3, edit_momentum_beta=0.6):
         super().__init__()
+        # `[gan] edit_concepts = "+glasses:5:0.9; -smile"` (default: none): semantic guidance on the coupled loop -
+        # each item `[+|-]text[:scale[:threshold]]` is an edit concept that steers every sample of a translate() call towards
+        # (+) or away from (-) its text beside the target prompt; `edit_momentum_scale` / `edit_momentum_beta`: the momentum
+        self.edit_concepts = sgm.parse_concepts(edit_concepts)
+        self.edit_momentum_scale, self.edit_momentum_beta = float(edit_momentum_scale), float(edit_momentum_beta)
+        if self.edit_concepts:
+            sgm.check_concepts(self.edit_concepts, self.edit_momentum_scale, self.edit_momentum_beta)
+            if str(precision) in ("fp32", "fp32x3"):
+                raise ValueError("edit_concepts needs the 16-bit precision: semantic guidance is not built for the fp32 / fp32x3 "
+                                 "networks")
+        self.last_edit_masks, self.last_edit_taus = None, None
         # `[gan] local_blend = words` (default none): prompt-to-prompt's local blend on the coupled loop - the
         # decoder's latent is held to the encoder's outside the region the word maps of the edited words mark, the mask rebuilt
         # after every step from iteration int(local_blend_start * K) on. `local_blend_side`: the token grid whose blocks are
@@ -521,7 +534,7 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         return "cond" if scale == 1.0 else ("uncond" if scale == 0.0 else "cfg")
 
     # ---- encode + generate as ONE coupled loop (north_star; include/cyclediff.h cd_cycle_translate)
-    def translate(self, image, encode_text, decode_text, mask=None, attn_ctrl=None, local_blend=None):
+    def translate(self, image, encode_text, decode_text, mask=None, attn_ctrl=None, local_blend=None, edit_concepts=None):
         """What Model.forward composes (model/text_unsupervised_translation.py:24-40): `self(encode(image, encode_text), image,
         encode_text, decode_text)`, with the DPM-Encoder and the decode of every ensemble member running as one loop - step k of
         both evaluates the same U-Net at the same timestep, and the decode step needs eps_k only after its forward, so each
@@ -552,8 +565,26 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         prompts do not share (attn_control.local_blend_selectors); identical prompts mark none and keep everything. ALWAYS
         the coupled loop, in chunks of samples past COUPLE_MAX_TOKENS; composes with cac_steps / attn_ctrl, not with a
         keep-mask. last_local_blend_masks: the final masks [B, 1, h, w] per candidate, last_local_blend_mask the first one's.
-        With local_blend off nothing below changes."""
+        With local_blend off nothing below changes.
+        `[gan] edit_concepts` or `edit_concepts` = a list of semantic_guidance.EditConcept (which overrides the config; an empty
+        list switches it off): semantic guidance. Every concept's context - from get_condition, like the
+        prompts' - rides as one more decoder row per candidate in the forward of every step, and the decode step consumes
+        eps = e_u + g (e_c - e_u) + the thresholded, weighted sum of the concept directions + momentum. The list applies to
+        every sample of the call. ALWAYS the coupled loop, in chunks of samples past COUPLE_MAX_TOKENS (the concept rows are
+        counted); composes with a keep-mask and with cac_steps / attn_ctrl, not with local_blend. last_edit_masks: per
+        candidate the kept elements [B, E, C, h, w] of the last iteration with an active concept, last_edit_taus the
+        thresholds [K, B, E]. Without concepts nothing below changes."""
+        concepts = list(edit_concepts) if edit_concepts is not None else list(getattr(self, "edit_concepts", None) or [])
+        sega = len(concepts) > 0
         blend = local_blend is not None or getattr(self, "local_blend", "none") != "none"
+        if sega:
+            s_m, beta = getattr(self, "edit_momentum_scale", 0.3), getattr(self, "edit_momentum_beta", 0.6)
+            sgm.check_concepts(concepts, s_m, beta)
+            if blend:
+                raise ValueError("edit_concepts and local_blend are not built together: switch one of them off")
+            if self.precision in ("fp32", "fp32x3"):
+                raise ValueError("edit_concepts needs the 16-bit precision: semantic guidance is not built for the fp32 / fp32x3 "
+                                 "networks")
         if blend and (mask is not None or self._auto_mask_on()):
             raise ValueError("local_blend builds its own keep-mask after every step: it takes no mask= and no auto_mask")
         if blend and self.precision in ("fp32", "fp32x3"):
@@ -571,6 +602,8 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         ride = [j for j in range(n_dec) if kinds[j] == main and (main == "cfg" or dec_scales[j] == dec_scales[kinds.index(main)])]
         enc_kinds = [self._kind(float(sc)) for sc in self.encoder_unconditional_guidance_scales]
         rows1 = (2 if "cfg" in enc_kinds else 1) + len(ride) * (2 if main == "cfg" else 1)  # rows of one sample of one member
+        if sega:
+            rows1 += len(ride) * len(concepts)  # one more decoder row per concept and candidate
         tokens = self.image_size ** 2
         fits = bsz * rows1 * tokens <= self.couple_max_tokens
         ctrl = attn_ctrl is not None or self.cac_steps > 0
@@ -580,6 +613,12 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         if ctrl and (len(ride) != n_dec or main == "uncond" or "uncond" in enc_kinds):
             raise ValueError("cross-attention control: every decoder scale must ride in the coupled loop (all guided, or one "
                              "unguided scale) and no scale may be 0 - the control acts on conditional rows")
+        if sega and not whole:
+            raise ValueError("edit_concepts needs the DPM-Encoder over the whole chain (white_box_steps = custom_steps + 1): "
+                             "the guidance lives in the coupled loop")
+        if sega and (len(ride) != n_dec or main != "cfg"):
+            raise ValueError("edit_concepts: every decoder scale must ride in the coupled loop and be guided (neither 0 nor "
+                             "1) - a concept's direction is taken against the unconditional row")
         if blend and not whole:
             raise ValueError("local_blend needs the DPM-Encoder over the whole chain (white_box_steps = custom_steps + 1): the "
                              "steps past a shorter prefix have no source rows")
@@ -594,7 +633,7 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         if encoder and len(ride) != n_dec:
             raise ValueError("mask_source = 'encoder': every decoder scale must ride in the coupled loop (all guided, or "
                              "one unguided scale) - a candidate decoded from z afterwards has no encoder trajectory")
-        coupled = ctrl or encoder or blend or bool(self.couple and whole and fits)
+        coupled = ctrl or encoder or blend or sega or bool(self.couple and whole and fits)
         self.last_translate_coupled = coupled
         sels, keep_parts = None, {}
         if blend:
@@ -623,6 +662,9 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         if mask is AUTO_MASK:
             m = self._auto_mask_ctx(x0, c_src, c_tgt)[0]
         masked = {} if m is None else dict(mask=m, x0=x0)  # generate()'s share of the keep-mask
+        c_edit, emask_parts, tau_parts = None, {}, {}
+        if sega:
+            c_edit = [self.get_condition([str(cc.text)] * bsz, bsz)[0] for cc in concepts]
         if not coupled:  # what encode() + forward() do
             z_ensemble = self._encode_members(x0, c_src, uc, members)
             return self._select(self.generate(z_ensemble, decode_text, **masked), image, encode_text, decode_text)
@@ -655,7 +697,21 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                         if not encoder:  # decoder row (jr * n + mi) * nb + b
                             kw.update(mask_x0=x0[sl].contiguous(), qcoef=sch.coef_qsample(skip), mask_noise=torch.cat(
                                 [mask_noise[i * n_dec + j][:, sl] for j in ride for i in idx], dim=1).contiguous())
-                    if sels is not None:
+                    if sega:
+                        K = len(sch) - skip
+                        if m is not None:
+                            kw["mask"] = m[sl].contiguous()
+                        z, x, taus, _kept, emask = self.engine.cycle_translate_sega(
+                            *args, torch.cat([ce[sl].repeat(n * nr, 1, 1) for ce in c_edit], 0).contiguous(),
+                            sgm.concept_table(concepts, K, int(np.prod(x0.shape[1:]))), s_m, beta,
+                            ctrl=None if ctl is None else (ctl[0][sl].contiguous(), ctl[1][sl].contiguous(),
+                                                           ctl[2][sl].contiguous(), int(self.cac_steps * K)), **kw)
+                        for mi, i in enumerate(idx):
+                            for jr, j in enumerate(ride):
+                                rows = slice((jr * n + mi) * nb, (jr * n + mi + 1) * nb)
+                                emask_parts.setdefault(i * n_dec + j, []).append(emask[rows])
+                                tau_parts.setdefault(i * n_dec + j, []).append(taus[:, rows])
+                    elif sels is not None:
                         K = len(sch) - skip
                         z, x, _acc, keep = self.engine.cycle_translate_blend(
                             *args, sels[0][sl].contiguous(), sels[1][sl].contiguous(), side, pool=self.local_blend_pool,
@@ -681,6 +737,9 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                             lat_parts.setdefault(i * n_dec + j, []).append(x[(jr * n + mi) * nb:(jr * n + mi + 1) * nb])
         z_ensemble = [p[0] if len(p) == 1 else torch.cat(p, 0) for p in z_parts]  # one part: the whole batch fitted
         latents = {k: v[0] if len(v) == 1 else torch.cat(v, 0) for k, v in lat_parts.items()}
+        if sega:
+            self.last_edit_masks = [torch.cat(emask_parts[k], 0) for k in sorted(emask_parts)]
+            self.last_edit_taus = [torch.cat(tau_parts[k], 1) for k in sorted(tau_parts)]
         if sels is not None:
             self.last_local_blend_masks = [torch.cat(keep_parts[k], 0) for k in sorted(keep_parts)]
             self.last_local_blend_mask = self.last_local_blend_masks[0]
@@ -706,6 +765,9 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         if getattr(self, "cac_steps", 0.0) > 0:
             raise ValueError("cac_steps > 0 needs translate(): in encode() + forward() the source rows whose attention maps the "
                              "control injects no longer exist; use translate(image, encode_text, decode_text)")
+        if getattr(self, "edit_concepts", None):
+            raise ValueError("edit_concepts needs translate(): in encode() + forward() the coupled loop in which the concept "
+                             "rows ride no longer exists; use translate(image, encode_text, decode_text)")
         if getattr(self, "local_blend", "none") != "none":
             raise ValueError("local_blend needs translate(): in encode() + forward() the source rows whose word maps and whose "
                              "latents the blend uses no longer exist; use translate(image, encode_text, decode_text)")

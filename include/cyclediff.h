@@ -332,6 +332,62 @@ int cd_cycle_translate_blend(cd_handle h, int net, int sched_kind, const float* 
                              float thr, int n_start, float* acc_out /* [B+n_dec*B,side,side] */,
                              float* keep_out /* [n_dec*B,1,h,w] */, float* z_out, float* x_out);
 
+/* One edit concept of semantic guidance. Its quantile threshold q in [0, 1] over the N = C*H*W values of a latent arrives as
+ * the rank and the weight of the two order statistics it lies between, computed by the caller in float64:
+ * lo = floor(q*(N-1)), frac = (float)(q*(N-1) - lo); the kernels see no float64 and no q. */
+typedef struct cd_sega_concept {
+  float scale;   /* s_e, signed: negative steers away from the concept */
+  float weight;  /* w_e of the sum over concepts */
+  int32_t lo;    /* in [0, N-1] */
+  float frac;    /* in [0, 1) */
+  int32_t warm;  /* the concept is active on iterations warm <= i < cool (iteration 0 = the noisiest step) */
+  int32_t cool;
+} cd_sega_concept;
+
+/* cd_cycle_translate(_masked / _ctrl) with semantic guidance (SEGA; Brack et al., NeurIPS 2023; no counterpart in the
+ * reference tree): E edit concepts, each a text context with its own signed scale, threshold, weight and window
+ * of iterations, steer the decoder rows beside the one target prompt. Arguments up to n_ctrl as cd_cycle_translate_ctrl's
+ * (mask = NULL: no keep-mask; n_ctrl = 0: no control), plus edit_ctx [E*Bd,L,Dc] fp32 device, concept-major (row e*Bd + r is
+ * concept e for decoder row r, Bd = n_dec*B), concepts_host [E] and the momentum's scale s_m and decay beta.
+ * The forward of every iteration runs over the batch rows
+ *     [ enc (uncond | cond) | dec uncond Bd | dec concept 0 Bd | ... | dec concept E-1 Bd | dec cond Bd ]
+ * every concept row on the decoder row's latent. With u, c, p_e the network's outputs of decoder row r's unconditional,
+ * conditional and concept-e rows, g_r the row's guidance scale and N = C*H*W, iteration i computes per element j, in fp32
+ * in this operation order without contraction:
+ *     base   = u + g_r * (c - u)
+ *     d_e    = (p_e - u) * s_e ,  a_e = |d_e|                       for the concepts with warm_e <= i < cool_e
+ *     tau_e  = A[lo_e] + (A[hi_e] - A[lo_e]) * frac_e               A = the N values a_e[r, .] ascending, hi = min(lo+1, N-1)
+ *     m_e    = (a_e >= tau_e) ? d_e : 0
+ *     gamma  = ((0 + w_0*m_0) + w_1*m_1) + ...                      active concepts only, ascending e
+ *     gamma' = gamma + s_m * nu[r, j]
+ *     nu[r,j] <- beta * nu[r,j] + (1 - beta) * gamma'               nu = 0 before iteration 0; updated in every iteration
+ *     eps    = base + gamma'
+ * and the decode step of row k = K-1-i (cd_ddim_decode's arithmetic, the keep-mask blend included) consumes eps in the place
+ * of the classifier-free-guidance combine. tau is torch.quantile(|d|.flatten(1), q, dim = 1) to rounding; q = 0 keeps
+ * every element, q = 1 only the maximum. The order statistics are exact (radix selection on the bit patterns); a NaN sorts
+ * above +inf. An inactive concept contributes nothing: the momentum is built from applied guidance only. The encoder's rows,
+ * the unconditional and conditional rows and z_out are those of the call without concepts, bit for bit; nothing is kept
+ * between calls.
+ * tau_out [K,Bd,E] fp32, kept_out [K,Bd,E] int32 (#{a_e >= tau_e}), both by iteration and 0 where the concept is inactive;
+ * mask_out [Bd,E,C,H,W] fp32 of 0 / 1: the kept elements of the last iteration in which any concept was active, 0 for a
+ * concept inactive in it. Each may be NULL.
+ * Refused (error text, nothing launched): E outside [1, 8]; sched_kind != CD_SCHED_DDIM; a network without a text context;
+ * precision CD_PREC_F32 / CD_PREC_F32X3; a decoder pass without both its unconditional and its conditional rows
+ * (dec_guidance 0 or 1, a missing context); lo outside [0, N-1]; frac outside [0, 1); warm / cool outside
+ * 0 <= warm <= cool <= K; a non-finite scale, weight, momentum_scale or momentum_beta; momentum_beta outside [0, 1]; tables
+ * whose rows k < K disagree on the timestep; and what cd_cycle_translate_masked / _ctrl refuse of a mask or a control. The
+ * local blend of cd_cycle_translate_blend is not built together with concepts. */
+int cd_cycle_translate_sega(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
+                            const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
+                            float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
+                            const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
+                            uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
+                            int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
+                            const float* mapper, const float* alpha, const float* weight, int B_ctrl, int n_ctrl,
+                            const float* edit_ctx, const cd_sega_concept* concepts_host, int E, float momentum_scale,
+                            float momentum_beta, float* tau_out /* [K,n_dec*B,E] */, int32_t* kept_out /* [K,n_dec*B,E] */,
+                            float* mask_out /* [n_dec*B,E,C,H,W] */, float* z_out, float* x_out);
+
 /* ILVR (Choi et al., ICCV 2021: Iterative Latent Variable Refinement), the reference-image-conditioned sampler of the
  * paper's unpaired table; no counterpart in the reference tree. cd_ddim_decode's loop on an unconditional
  * pixel DDPM, with the running image pulled to the low-pass band of a reference image after the step of every row k > range_t:
@@ -552,6 +608,16 @@ int cd_op_sched_step_masked(cd_handle h, int mode, const cd_step_coef* coef_host
                             float guidance, const float* eps_in, const float* mask, const float* src, int B_mask,
                             int mask_source, float qa, float qb, const float* mask_noise, int blend, int B, int C, int HW,
                             void* xin16_out, int cfg_dup);
+/* one iteration of cd_cycle_translate_sega's guidance - its two launches, k_sega_threshold and k_sega_combine - on caller
+ * tensors (bit-exact checks). eps_all [(2+E)*Bd,C,HW] fp32 device NCHW in batch-row order uncond | concept 0 .. E-1 | cond; the
+ * op stages it to the form the network writes, fp32 NHWC with row stride ld >= C, and the kernels read that. guidance, or
+ * guidance_per_sample [Bd] (device) when not NULL; concepts_host [E]; iteration: the i that warm / cool are held against;
+ * nu [Bd,C,HW] in / out. Outputs: eps_out [Bd,C,HW]; tau_out [Bd,E], kept_out [Bd,E] (0 for an inactive concept); mask_out
+ * [Bd,E,C,HW] or NULL. Refused as cd_cycle_translate_sega refuses the concept rows and the momentum, and ld < C. */
+int cd_op_sega_guidance(cd_handle h, const float* eps_all, int Bd, int C, int HW, int E, int ld, float guidance,
+                        const float* guidance_per_sample, const cd_sega_concept* concepts_host, int iteration,
+                        float momentum_scale, float momentum_beta, float* nu, float* eps_out, float* tau_out,
+                        int32_t* kept_out, float* mask_out);
 /* ---- bare single-kernel entry points of the small HBM-bound kernels (csrc/elementwise.hip), test-only ----
  * Every pointer is device memory that the caller laid out itself; a 16-bit tensor is the storage words of cd_act_format().
  * Each call checks its arguments, makes exactly one launch and synchronises: no staging kernel of the engine's sits between

@@ -90,6 +90,11 @@ def folded_calls(model, batches, fold, seed, device):
                 if getattr(w, "local_blend", "none") != "none" and getattr(w, "last_local_blend_mask", None) is not None:
                     f = w.vae_factor
                     batch["auto_keep"] = w.last_local_blend_mask.repeat_interleave(f, 2).repeat_interleave(f, 3).cpu()
+        # `[gan] edit_concepts`: per concept the channel-max of the first candidate's final edit mask, as pixels
+        for w in wrappers:
+            if getattr(w, "edit_concepts", None) and getattr(w, "last_edit_masks", None):
+                f = w.vae_factor
+                batch["edit_masks"] = w.last_edit_masks[0].amax(2).repeat_interleave(f, 2).repeat_interleave(f, 3).cpu()
         yield batch, orig, img
 
 
@@ -143,7 +148,8 @@ def main(argv=None):
                          "CYCLEDIFF_LPIPS_WEIGHTS, or seeded synthetic weights with --synthetic-weights)")
     ap.add_argument("--save_masks", action="store_true",
                     help="`[gan] auto_mask = diffedit`: also write every sample's estimated keep-mask, upsampled to the image "
-                         "(white = kept), as <id>_mask.png beside its image")
+                         "(white = kept), as <id>_mask.png beside its image; `[gan] edit_concepts`: every concept's final edit "
+                         "mask (channel maximum, white = edited) as edit_masks/<id>_<e>.png")
     ap.add_argument("--text_metrics", action="store_true",
                     help="text tasks: per-sample CLIP and directional CLIP (evaluation/translate_text.py) on the unclamped "
                          "outputs; ViT-B/32 weights from CYCLEDIFF_CLIP_RANKER")
@@ -257,6 +263,12 @@ def main(argv=None):
                     from PIL import Image
                     Image.fromarray((batch["auto_keep"][j, 0].numpy() * 255).astype("uint8")).save(
                         os.path.join(a.output_dir, "%06d_mask.png" % sid))
+            if a.save_masks and "edit_masks" in batch:  # white = the elements concept e edited in its last active iteration
+                from PIL import Image
+                os.makedirs(os.path.join(a.output_dir, "edit_masks"), exist_ok=True)
+                for e in range(batch["edit_masks"].shape[1]):
+                    Image.fromarray((batch["edit_masks"][j, e].numpy() * 255).astype("uint8")).save(
+                        os.path.join(a.output_dir, "edit_masks", "%06d_%d.png" % (sid, e)))
             if lp is not None:
                 row["lpips"] = float(lp[keep.index(j)])
                 if lp_keep is not None and j in lp_keep:
