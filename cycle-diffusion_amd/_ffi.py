@@ -45,6 +45,39 @@ class SegaConcept(C.Structure):
                 ("warm", C.c_int32), ("cool", C.c_int32)]
 
 
+# the argument struct of cd_cycle_translate and its four option structs (NULL = the feature is off); device pointers and
+# host tables alike cross as c_void_p
+class KeepMask(C.Structure):
+    _fields_ = [("mask", C.c_void_p), ("x0", C.c_void_p), ("B_mask", C.c_int), ("source", C.c_int),
+                ("qsample_coef_host", C.c_void_p), ("noise", C.c_void_p), ("seed", C.c_uint64)]
+
+
+class AttnCtrl(C.Structure):
+    _fields_ = [("mapper", C.c_void_p), ("alpha", C.c_void_p), ("weight", C.c_void_p), ("B_ctrl", C.c_int),
+                ("n_ctrl", C.c_int)]
+
+
+class LocalBlend(C.Structure):
+    _fields_ = [("sel_src", C.c_void_p), ("sel_tgt", C.c_void_p), ("B_sel", C.c_int), ("side", C.c_int), ("pool", C.c_int),
+                ("thr", C.c_float), ("n_start", C.c_int), ("acc_out", C.c_void_p), ("keep_out", C.c_void_p)]
+
+
+class Sega(C.Structure):
+    _fields_ = [("edit_ctx", C.c_void_p), ("concepts_host", C.c_void_p), ("E", C.c_int), ("momentum_scale", C.c_float),
+                ("momentum_beta", C.c_float), ("tau_out", C.c_void_p), ("kept_out", C.c_void_p), ("mask_out", C.c_void_p)]
+
+
+class TranslateArgs(C.Structure):
+    _fields_ = [("size", C.c_uint32), ("net", C.c_int), ("sched_kind", C.c_int), ("x0", C.c_void_p),
+                ("enc_ctx_c", C.c_void_p), ("enc_ctx_uc", C.c_void_p), ("enc_guidance", C.c_float),
+                ("dec_ctx_c", C.c_void_p), ("dec_ctx_uc", C.c_void_p), ("dec_guidance", C.c_float),
+                ("dec_guidance_per_sample", C.c_void_p), ("ctx_len", C.c_int), ("B", C.c_int), ("n_dec", C.c_int),
+                ("K", C.c_int), ("coef_enc_host", C.c_void_p), ("coef_dec_host", C.c_void_p), ("noise", C.c_void_p),
+                ("seed", C.c_uint64), ("last_uses_x0", C.c_int), ("z_out", C.c_void_p), ("x_out", C.c_void_p),
+                ("mask", C.POINTER(KeepMask)), ("ctrl", C.POINTER(AttnCtrl)), ("blend", C.POINTER(LocalBlend)),
+                ("sega", C.POINTER(Sega))]
+
+
 SEGA_CONCEPT_DTYPE = np.dtype([("scale", "<f4"), ("weight", "<f4"), ("lo", "<i4"), ("frac", "<f4"), ("warm", "<i4"),
                                ("cool", "<i4")])
 
@@ -83,19 +116,9 @@ SIGNATURES = {
     "cd_ddim_decode": [_VP, _I, _I, _VP, _I, _I, _VP, _VP, _I, _F, _I, _I, _VP, _VP, _U64, _VP],
     "cd_ddim_decode_v": [_VP, _I, _I, _VP, _I, _I, _VP, _VP, _I, _VP, _I, _I, _VP, _VP, _U64, _VP],
     "cd_ddim_invert": [_VP, _I, _I, _VP, _VP, _VP, _I, _F, _I, _I, _VP, _VP, _VP],
-    "cd_cycle_translate": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I, _VP,
-                           _VP],
+    "cd_cycle_translate": [_VP, C.POINTER(TranslateArgs)],
     "cd_ddim_decode_masked": [_VP, _I, _I, _VP, _I, _I, _VP, _VP, _I, _F, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP, _I, _I, _VP, _VP,
                               _U64, _VP],
-    "cd_cycle_translate_masked": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I,
-                                  _VP, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP],
-    "cd_cycle_translate_ctrl": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I,
-                                _VP, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP, _VP, _I, _I, _VP, _VP],
-    "cd_cycle_translate_blend": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I,
-                                 _VP, _VP, _VP, _I, _I, _VP, _VP, _I, _I, _I, _F, _I, _VP, _VP, _VP, _VP],
-    "cd_cycle_translate_sega": [_VP, _I, _I, _VP, _VP, _VP, _F, _VP, _VP, _F, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _U64, _I,
-                                _VP, _VP, _I, _I, _VP, _VP, _U64, _VP, _VP, _VP, _I, _I, _VP, _VP, _I, _F, _F, _VP, _VP, _VP,
-                                _VP, _VP],
     "cd_ilvr_decode": [_VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _U64, _VP, _I, _I, _I, _VP, _VP, _U64, _VP],
     "cd_automask": [_VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _F, _F, _VP, _U64, _I, _F, _F, _I, _VP, _VP],
     "cd_word_maps": [_VP, _I, _VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _F, _F, _VP, _U64, _I, _I, _I, _VP, C.POINTER(_I)],

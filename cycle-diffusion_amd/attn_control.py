@@ -1,6 +1,6 @@
 """Host side of the cross-attention control (prompt-to-prompt, Hertz et al. 2022, on the coupled translate loop).
 
-build_control() turns the token ids of a source and a target prompt into what cd_cycle_translate_ctrl consumes:
+build_control() turns the token ids of a source and a target prompt into what cd_cycle_translate's cd_attn_ctrl consumes:
     M [B, L, L]   mapper: (P_src . M)[j] = sum_i P_src[i] M[i, j] - the source attention map seen from target position j
     alpha [B, L]  1 where target position j takes the mapped source map, 0 where it keeps its own
     w [B, L]      re-weighting of target position j (1 = unchanged)
@@ -167,7 +167,7 @@ LOCAL_BLEND_MODES = ("none", "words")
 
 
 def local_blend_selectors(src_ids, tgt_ids, eos_id=CLIP_EOS, words=None):
-    """The selectors of cd_cycle_translate_blend for one sample: (sel_src [L], sel_tgt [L]) float32. Without `words`:
+    """The selectors of the local blend (cd_local_blend) for one sample: (sel_src [L], sel_tgt [L]) float32. Without `words`:
     edited_selector both ways - the target positions not paired with an equal source token, and the source positions not
     paired with an equal target token; a side that has none (an insertion leaves the source without one, identical prompts
     leave both) is all zero, and an all-zero map edits nothing. words = (src_words, tgt_words): token-id sequences marked by

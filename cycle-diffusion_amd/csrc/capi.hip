@@ -11,7 +11,7 @@ void set_last_error(const char* what) { g_err = what; }
 extern "C" {
 
 const char* cd_last_error(void) { return g_err.c_str(); }
-int cd_version(void) { return 100; }
+int cd_version(void) { return 101; }
 int cd_act_format(void) { return CD_ACT_FP16 ? 1 : 0; }
 
 int cd_engine_create(void* hip_stream, size_t workspace_bytes, cd_handle* out) {
@@ -248,26 +248,6 @@ StepCoef* upload_coef(cd_engine* h, const cd_step_coef* host, int n) {
 
 namespace {
 
-// Arguments of the region-keeping decode (cd_ddim_decode_masked / cd_cycle_translate_masked), checked on the host before
-// any launch. `B` is the decoder's batch.
-struct MaskArgs {
-  const float* mask = nullptr;        // [B_mask, 1, H, W]
-  const float* x0 = nullptr;          // [B_mask, C, H, W] ("q_sample")
-  int B_mask = 0;
-  int source = CD_MASK_QSAMPLE;
-  const float* qcoef_host = nullptr;  // K x (qa, qb)
-  const float* noise = nullptr;       // [K, B, C, H, W] or NULL -> Philox(seed)
-  uint64_t seed = 0;
-};
-// the entry points' seven mask arguments, in the order they take them
-MaskArgs mask_args_of(const float* mask, const float* x0, int B_mask, int source, const float* qcoef_host, const float* noise,
-                      uint64_t seed) {
-  MaskArgs mk;
-  mk.mask = mask; mk.x0 = x0; mk.B_mask = B_mask; mk.source = source; mk.qcoef_host = qcoef_host;
-  mk.noise = noise; mk.seed = seed;
-  return mk;
-}
-
 // The generator's streams are banded by loop, 4096 streams to a band (tests/_philox_ref.py STREAMS):
 // 0 x_T and 1 + i the encoder, 0x1000 + i the decode, 0x2000 / 0x2001 + i the refinement, 0x3000 + j the inversion,
 // 0x4000 + slot the keep-mask's q-sample, 0x5000 + i ILVR's reference, 0x6000 + i the keep-mask estimate's draws, 0x7a65 the
@@ -280,7 +260,9 @@ void check_stream_band(const void* noise, int steps, const char* what) {
            "pass the noise tensor", what, kStreamBandSteps, steps);
 }
 
-void check_mask_args(const MaskArgs& m, UNet* u, int sched_kind, int B, bool coupled) {
+// the keep-mask of the region-keeping decode and of the coupled loop, checked on the host before any launch; `B` is the
+// decoder's batch
+void check_mask_args(const cd_keep_mask& m, UNet* u, int sched_kind, int B, bool coupled) {
   CD_CHECK(sched_kind == CD_SCHED_DDIM, "a keep-mask is only defined for sched_kind = CD_SCHED_DDIM (the reference has no mask "
                                         "hook on DDPMDDIMWrapper)");
   CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer,
@@ -288,17 +270,17 @@ void check_mask_args(const MaskArgs& m, UNet* u, int sched_kind, int B, bool cou
   CD_CHECK(m.mask, "mask is NULL");
   CD_CHECK(m.B_mask > 0 && B % m.B_mask == 0, "mask shape mismatch: %d mask rows for a batch of %d", m.B_mask, B);
   if (m.source == CD_MASK_ENCODER) {
-    CD_CHECK(coupled, "mask_source = encoder needs the coupled loop (cd_cycle_translate_masked): the encoder's trajectory "
+    CD_CHECK(coupled, "mask_source = encoder needs the coupled loop (cd_cycle_translate): the encoder's trajectory "
                       "does not exist in a separate decode");
-    CD_CHECK(!m.qcoef_host && !m.noise, "mask_source = encoder takes no q-sample table and no mask noise: pass NULL");
+    CD_CHECK(!m.qsample_coef_host && !m.noise, "mask_source = encoder takes no q-sample table and no mask noise: pass NULL");
   } else {
     CD_CHECK(m.source == CD_MASK_QSAMPLE, "bad mask_source %d", m.source);
-    CD_CHECK(m.x0 && m.qcoef_host, "mask_source = q_sample needs x0 and the q-sample coefficient table");
+    CD_CHECK(m.x0 && m.qsample_coef_host, "mask_source = q_sample needs x0 and the q-sample coefficient table");
   }
 }
 
 // the blend of level k (table row k) whose q-sample draw is slot `slot` (the loop's iteration number)
-MaskBlend mask_blend_of(const MaskArgs& m, const float2* qtab, int k, int slot, int64_t n) {
+MaskBlend mask_blend_of(const cd_keep_mask& m, const float2* qtab, int k, int slot, int64_t n) {
   MaskBlend b;
   b.mask = m.mask; b.mask_bmod = m.B_mask;
   b.src = m.x0; b.src_bmod = m.B_mask;
@@ -307,35 +289,6 @@ MaskBlend mask_blend_of(const MaskArgs& m, const float2* qtab, int k, int slot, 
   b.gauss.seed = m.seed; b.gauss.stream = (uint32_t)(0x4000 + slot);
   return b;
 }
-
-// Arguments of the cross-attention control (cd_cycle_translate_ctrl), checked on the host before any launch
-struct CtrlArgs {
-  const float* mapper = nullptr;  // [B_ctrl, L, L]
-  const float* alpha = nullptr;   // [B_ctrl, L]
-  const float* weight = nullptr;  // [B_ctrl, L]
-  int B_ctrl = 0, n_ctrl = 0;
-};
-
-// Arguments of the local blend (cd_cycle_translate_blend), checked on the host before any launch
-struct BlendArgs {
-  const float* sel_src = nullptr;  // [B_sel, L]
-  const float* sel_tgt = nullptr;  // [B_sel, L]
-  int B_sel = 0, side = 0, pool = 0, n_start = 0;
-  float thr = 0.f;
-  float* acc_out = nullptr;   // [B + n_dec * B, side, side] or NULL
-  float* keep_out = nullptr;  // [n_dec * B, 1, h, w] or NULL
-};
-
-// Arguments of semantic guidance (cd_cycle_translate_sega), checked on the host before any launch
-struct SegaArgs {
-  const float* edit_ctx = nullptr;             // [E * Bd, L, Dc], concept-major
-  const cd_sega_concept* concepts = nullptr;   // [E], host
-  int E = 0;
-  float s_m = 0.f, beta = 0.f;
-  float* tau_out = nullptr;   // [K, Bd, E] or NULL
-  int32_t* kept_out = nullptr;  // [K, Bd, E] or NULL
-  float* mask_out = nullptr;  // [Bd, E, C, H, W] or NULL
-};
 
 struct SamplerState {
   UNet* u = nullptr;
@@ -577,7 +530,7 @@ int cd_dpm_encode(cd_handle h, int net, int sched_kind, const float* x0, const f
 static void ddim_decode_impl(cd_handle h, int net, int sched_kind, const float* z, int z_slots, int n_eps,
                              const float* ctx_c, const float* ctx_uc, int ctx_len, float guidance, const float* gvec,
                              int B, int K, const cd_step_coef* coef_host, const float* noise_tail, uint64_t seed,
-                             float* x_out, const MaskArgs* mk = nullptr) {
+                             float* x_out, const cd_keep_mask* mk = nullptr) {
   CD_CHECK(h && z && coef_host && x_out && B > 0 && K > 0 && n_eps <= z_slots - 1, "bad argument");
   check_stream_band(noise_tail, K, "decode: noise_tail");
   if (mk && mk->source == CD_MASK_QSAMPLE) check_stream_band(mk->noise, K, "keep-mask: mask_noise");
@@ -600,7 +553,7 @@ static void ddim_decode_impl(cd_handle h, int net, int sched_kind, const float* 
   HIP_CHECK(hipMemcpy2DAsync(s.xt, chw * 4, z, zbs * 4, chw * 4, B, hipMemcpyDeviceToDevice, h->st));
   const float2* qtab = nullptr;
   if (mk) {  // img = q_sample(x0, ts) * mask + (1. - mask) * img ahead of the first forward too (ddim.py:427-430)
-    qtab = (const float2*)upload_table(h, mk->qcoef_host, (size_t)K * 2 * sizeof(float));
+    qtab = (const float2*)upload_table(h, mk->qsample_coef_host, (size_t)K * 2 * sizeof(float));
     launch_mask_blend_init(h->st, a, mask_blend_of(*mk, qtab, K - 1, 0, n));
   } else if (!s.f32) launch_nchw_to_nhwc(h->st, s.xt, s.xin, B, s.C, s.HW, s.cpad, 1.f, 0.f, s.cfg ? 1 : 0);
   for (int i = 0; i < K; ++i) {
@@ -653,7 +606,7 @@ int cd_ddim_decode_masked(cd_handle h, int net, int sched_kind, const float* z, 
   CD_API_BEGIN
   enter_engine(h);
   CD_CHECK(h, "bad argument");
-  const MaskArgs mk = mask_args_of(mask, x0, B_mask, mask_source, qsample_coef_host, mask_noise, mask_seed);
+  const cd_keep_mask mk = {mask, x0, B_mask, mask_source, qsample_coef_host, mask_noise, mask_seed};
   if (guidance_per_sample) CD_CHECK(ctx_c && ctx_uc, "cd_ddim_decode_masked: a guidance vector needs both contexts");
   ddim_decode_impl(h, net, sched_kind, z, z_slots, n_eps, ctx_c, ctx_uc, ctx_len, guidance_per_sample ? 2.0f : guidance,
                    guidance_per_sample, B, K, coef_host, noise_tail, seed, x_out, &mk);
@@ -698,59 +651,62 @@ int cd_ddim_invert(cd_handle h, int net, int sched_kind, const float* x0, const 
 //   [ encoder rows (B, or uncond B | cond B under encoder guidance) | decoder rows (Bd = n_dec * B, or uncond Bd | cond Bd) ]
 // followed by the encoder's step kernel (x_{k-1}, eps_k -> z) and then the decoder's (consumes eps_k). 99 forwards of
 // B + 2 Bd rows instead of 99 of B and 99 of 2 Bd. Per-sample arithmetic is that of cd_dpm_encode followed by cd_ddim_decode(_v).
-static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
-                       const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
-                       float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
-                       const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                       uint64_t seed, int last_uses_x0, float* z_out, float* x_out, const MaskArgs* mk,
-                       const CtrlArgs* ck = nullptr, const BlendArgs* bk = nullptr, const SegaArgs* sk = nullptr) {
-  CD_CHECK(h && x0 && coef_enc_host && coef_dec_host && z_out && x_out && B > 0 && n_dec > 0 && K > 0, "bad argument");
-  CD_CHECK(!(sk && bk), "semantic guidance and the local blend are not built together: call cd_cycle_translate_sega without "
-                        "the blend, or cd_cycle_translate_blend without concepts");
-  check_stream_band(noise, K, "cd_cycle_translate: noise");
-  if (mk && mk->source == CD_MASK_QSAMPLE) check_stream_band(mk->noise, K, "keep-mask: mask_noise");
+// The options (include/cyclediff.h: keep-mask, cross-attention control DESIGN.md 14, local blend 18, semantic guidance 20)
+// are branches of this one body; which of them go together is decided here.
+static void cycle_translate_impl(cd_handle h, const cd_translate_args& a) {
+  const cd_keep_mask* mk = a.mask;
+  const cd_attn_ctrl* ck = a.ctrl;
+  const cd_local_blend* bk = a.blend;
+  const cd_sega* sk = a.sega;
+  CD_CHECK(h && a.x0 && a.coef_enc_host && a.coef_dec_host && a.z_out && a.x_out && a.B > 0 && a.n_dec > 0 && a.K > 0,
+           "bad argument");
+  CD_CHECK(!(sk && bk), "semantic guidance and the local blend are not built together: call without the blend, or without "
+                        "concepts");
+  check_stream_band(a.noise, a.K, "cd_cycle_translate: noise");
+  if (mk && mk->source == CD_MASK_QSAMPLE) check_stream_band(mk->noise, a.K, "keep-mask: mask_noise");
   ArenaScope arena_scope(h->arena);
-  UNet* u = get_unet(h, net);
-  const int Bd = B * n_dec;
-  if (mk) check_mask_args(*mk, u, sched_kind, B, /*coupled=*/true);
+  UNet* u = get_unet(h, a.net);
+  const int Bd = a.B * a.n_dec;
+  if (mk) check_mask_args(*mk, u, a.sched_kind, a.B, /*coupled=*/true);
   const bool ctrl_on = ck && ck->n_ctrl != 0;
-  CD_CHECK(!(mk && bk), "cd_cycle_translate_blend: a static keep-mask and the local blend exclude each other (the blend "
+  CD_CHECK(!(mk && bk), "the local blend: a static keep-mask and the local blend exclude each other (the blend "
                         "rewrites the mask after every step)");
   // what the control and the local blend both need of the call; the blend needs it for every n_ctrl
   const bool text_on = ctrl_on || bk;
   const char* what = ctrl_on ? "cross-attention control" : "the local blend";
   if (ck || bk || sk) {
     // one forward serves both passes at the timestep of the DECODER's row k: the two tables must agree on it
-    for (int k = 0; k < K; ++k)
-      CD_CHECK(coef_enc_host[k].t == coef_dec_host[k].t, "%s: the encoder's and the decoder's tables disagree "
+    for (int k = 0; k < a.K; ++k)
+      CD_CHECK(a.coef_enc_host[k].t == a.coef_dec_host[k].t, "%s: the encoder's and the decoder's tables disagree "
                "on the timestep of row %d (%d against %d)",
-               sk ? "cd_cycle_translate_sega" : bk ? "cd_cycle_translate_blend" : "cd_cycle_translate_ctrl", k,
-               coef_enc_host[k].t, coef_dec_host[k].t);
+               sk ? "semantic guidance" : bk ? "the local blend" : "cross-attention control", k,
+               a.coef_enc_host[k].t, a.coef_dec_host[k].t);
   }
   if (sk) {
     const char* sg = "semantic guidance";
     CD_CHECK(sk->E >= 1 && sk->E <= kSegaMaxConcepts, "%s: E = %d concepts outside [1, %d]", sg, sk->E, kSegaMaxConcepts);
-    CD_CHECK(sk->edit_ctx && sk->concepts, "%s: edit_ctx / concepts_host is NULL", sg);
-    CD_CHECK(sched_kind == CD_SCHED_DDIM, "%s is only defined for sched_kind = CD_SCHED_DDIM", sg);
-    CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer && u->desc.context_dim > 0 && ctx_len > 0,
+    CD_CHECK(sk->edit_ctx && sk->concepts_host, "%s: edit_ctx / concepts_host is NULL", sg);
+    CD_CHECK(a.sched_kind == CD_SCHED_DDIM, "%s is only defined for sched_kind = CD_SCHED_DDIM", sg);
+    CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer && u->desc.context_dim > 0 && a.ctx_len > 0,
              "%s needs a network with a text context: the concepts are contexts", sg);
     CD_CHECK(!u->f32, "%s is not built for precision CD_PREC_F32 / CD_PREC_F32X3 networks: use the 16-bit precision", sg);
-    check_sega_params(sk->concepts, sk->E, (int64_t)u->desc.in_channels * u->image_size * u->image_size, K, sk->s_m, sk->beta);
+    check_sega_params(sk->concepts_host, sk->E, (int64_t)u->desc.in_channels * u->image_size * u->image_size, a.K,
+                      sk->momentum_scale, sk->momentum_beta);
   }
   if (text_on) {
-    CD_CHECK(sched_kind == CD_SCHED_DDIM, "%s is only defined for sched_kind = CD_SCHED_DDIM", what);
-    CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer && (enc_ctx_c || enc_ctx_uc),
+    CD_CHECK(a.sched_kind == CD_SCHED_DDIM, "%s is only defined for sched_kind = CD_SCHED_DDIM", what);
+    CD_CHECK(u->kind() == CD_NET_UNET_OPENAI && u->desc.use_spatial_transformer && (a.enc_ctx_c || a.enc_ctx_uc),
              "%s needs a network with a text context (and the contexts of both passes)", what);
     CD_CHECK(!u->f32, "%s is not built for fp32 / fp32x3 networks (their transformer blocks run the fp32 "
                       "attention of st_f32.hip): use the 16-bit precision", what);
-    CD_CHECK(ctx_len <= kCtrlKeys, "%s: context length %d above the %d keys the kernel keeps resident", what, ctx_len,
+    CD_CHECK(a.ctx_len <= kCtrlKeys, "%s: context length %d above the %d keys the kernel keeps resident", what, a.ctx_len,
              kCtrlKeys);
   }
   if (bk) {
     const int R = u->image_size;
     CD_CHECK(bk->sel_src && bk->sel_tgt, "the local blend: sel_src / sel_tgt is NULL");
-    CD_CHECK(bk->B_sel > 0 && B % bk->B_sel == 0, "the local blend shape mismatch: %d selector entries for a batch of %d",
-             bk->B_sel, B);
+    CD_CHECK(bk->B_sel > 0 && a.B % bk->B_sel == 0, "the local blend shape mismatch: %d selector entries for a batch of %d",
+             bk->B_sel, a.B);
     CD_CHECK(bk->side > 0 && bk->side <= kBlendMaxSide, "the local blend: side = %d outside [1, %d] (both maps of a row stay "
              "in LDS)", bk->side, kBlendMaxSide);
     CD_CHECK(R % bk->side == 0, "the local blend: a %d x %d token grid does not divide the %d x %d latent", bk->side, bk->side,
@@ -759,47 +715,49 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
              bk->side);
     CD_CHECK(bk->pool >= 1 && bk->pool <= kBlendMaxPool && bk->pool % 2 == 1, "the local blend: pool = %d is not an odd number "
              "in [1, %d]", bk->pool, kBlendMaxPool);
-    CD_CHECK(bk->n_start >= 0 && bk->n_start <= K, "the local blend: n_start = %d outside [0, K = %d]", bk->n_start, K);
+    CD_CHECK(bk->n_start >= 0 && bk->n_start <= a.K, "the local blend: n_start = %d outside [0, K = %d]", bk->n_start, a.K);
     CD_CHECK(std::isfinite(bk->thr), "the local blend: the threshold is not finite");
   }
   if (ctrl_on) {
-    CD_CHECK(ck->n_ctrl > 0 && ck->n_ctrl <= K, "cross-attention control: n_ctrl = %d outside [0, K = %d]", ck->n_ctrl, K);
+    CD_CHECK(ck->n_ctrl > 0 && ck->n_ctrl <= a.K, "cross-attention control: n_ctrl = %d outside [0, K = %d]", ck->n_ctrl, a.K);
     CD_CHECK(ck->mapper && ck->alpha && ck->weight, "cross-attention control: mapper / alpha / weight is NULL");
-    CD_CHECK(ck->B_ctrl > 0 && B % ck->B_ctrl == 0, "cross-attention control shape mismatch: %d control rows for a batch of %d",
-             ck->B_ctrl, B);
+    CD_CHECK(ck->B_ctrl > 0 && a.B % ck->B_ctrl == 0, "cross-attention control shape mismatch: %d control rows for a batch "
+             "of %d", ck->B_ctrl, a.B);
   }
   const int C = u->desc.in_channels, HW = u->image_size * u->image_size, cpad = u->in_cpad, out_ld = u->out_channels;
   const bool f32 = u->f32;
-  Guidance ge = resolve_guidance(enc_ctx_c, enc_ctx_uc, enc_guidance);
-  Guidance gd = resolve_guidance(dec_ctx_c, dec_ctx_uc, dec_guidance_per_sample ? 2.0f : dec_guidance);
-  if (dec_guidance_per_sample) CD_CHECK(gd.cfg, "per-sample guidance needs the classifier-free-guidance batch (both contexts)");
+  Guidance ge = resolve_guidance(a.enc_ctx_c, a.enc_ctx_uc, a.enc_guidance);
+  Guidance gd = resolve_guidance(a.dec_ctx_c, a.dec_ctx_uc, a.dec_guidance_per_sample ? 2.0f : a.dec_guidance);
+  if (a.dec_guidance_per_sample)
+    CD_CHECK(gd.cfg, "per-sample guidance needs the classifier-free-guidance batch (both contexts)");
   if (text_on)
-    CD_CHECK((ge.cfg || (enc_ctx_c && ge.ctx_single == enc_ctx_c)) && (gd.cfg || (dec_ctx_c && gd.ctx_single == dec_ctx_c)),
+    CD_CHECK((ge.cfg || (a.enc_ctx_c && ge.ctx_single == a.enc_ctx_c)) &&
+                 (gd.cfg || (a.dec_ctx_c && gd.ctx_single == a.dec_ctx_c)),
              "%s needs conditional rows in both passes (a guidance scale of 0 runs none)", what);
-  CD_CHECK(sched_kind == CD_SCHED_DDIM || (!ge.cfg && !gd.cfg), "classifier-free guidance is only implemented for sched_kind = CD_SCHED_DDIM");
-  const bool has_ctx = enc_ctx_c || enc_ctx_uc;
-  CD_CHECK(has_ctx == (dec_ctx_c || dec_ctx_uc), "cd_cycle_translate: contexts for both passes or for neither");
+  CD_CHECK(a.sched_kind == CD_SCHED_DDIM || (!ge.cfg && !gd.cfg), "classifier-free guidance is only implemented for sched_kind = CD_SCHED_DDIM");
+  const bool has_ctx = a.enc_ctx_c || a.enc_ctx_uc;
+  CD_CHECK(has_ctx == (a.dec_ctx_c || a.dec_ctx_uc), "cd_cycle_translate: contexts for both passes or for neither");
   if (sk)
     CD_CHECK(gd.cfg, "semantic guidance: dec_guidance = %g (or a missing context) leaves the decoder pass without its "
                      "unconditional or its conditional rows; the concept directions are taken against the unconditional row",
-             (double)dec_guidance);
+             (double)a.dec_guidance);
   // decoder batch rows under semantic guidance: [uncond Bd | concept 0 Bd | ... | concept E-1 Bd | cond Bd]
   const int E = sk ? sk->E : 0;
-  const int Ben = ge.cfg ? 2 * B : B, Bdn = gd.cfg ? (2 + E) * Bd : Bd, Bn = Ben + Bdn;
+  const int Ben = ge.cfg ? 2 * a.B : a.B, Bdn = gd.cfg ? (2 + E) * Bd : Bd, Bn = Ben + Bdn;
   Ctx c = h->ctx();
   if (has_ctx) {
     const int Dc = u->desc.context_dim;
-    CD_CHECK(Dc > 0 && ctx_len > 0, "network has no cross-attention but a context was given");
+    CD_CHECK(Dc > 0 && a.ctx_len > 0, "network has no cross-attention but a context was given");
     // one context tensor in batch-row order: [enc (uncond | cond) | dec (uncond | cond)]
-    void* cx = h->arena.alloc((size_t)Bn * ctx_len * Dc * (f32 ? 4 : 2));
-    auto put = [&](const float* src, int rows, size_t row0) { put_ctx(h, u, src, cx, row0, rows, ctx_len, Dc); };
-    if (ge.cfg) { put(enc_ctx_uc, B, 0); put(enc_ctx_c, B, B); } else put(ge.ctx_single, B, 0);
+    void* cx = h->arena.alloc((size_t)Bn * a.ctx_len * Dc * (f32 ? 4 : 2));
+    auto put = [&](const float* src, int rows, size_t row0) { put_ctx(h, u, src, cx, row0, rows, a.ctx_len, Dc); };
+    if (ge.cfg) { put(a.enc_ctx_uc, a.B, 0); put(a.enc_ctx_c, a.B, a.B); } else put(ge.ctx_single, a.B, 0);
     if (gd.cfg) {
-      put(dec_ctx_uc, Bd, Ben);
+      put(a.dec_ctx_uc, Bd, Ben);
       if (sk) put(sk->edit_ctx, E * Bd, Ben + Bd);  // concept-major, as the rows lie
-      put(dec_ctx_c, Bd, Ben + (size_t)(1 + E) * Bd);
+      put(a.dec_ctx_c, Bd, Ben + (size_t)(1 + E) * Bd);
     } else put(gd.ctx_single, Bd, Ben);
-    u->set_context(c, (const bf16_t*)cx, Bn, ctx_len);
+    u->set_context(c, (const bf16_t*)cx, Bn, a.ctx_len);
   } else {
     CD_CHECK(u->desc.context_dim <= 0 || !u->desc.use_spatial_transformer, "network expects a cross-attention context");
   }
@@ -808,28 +766,28 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
   AttnCtrl actl;
   if (ctrl_on) {
     actl.row0 = Bn - Bd; actl.rows = Bd;
-    actl.src_b0 = ge.cfg ? B : 0; actl.B_src = B;
+    actl.src_b0 = ge.cfg ? a.B : 0; actl.B_src = a.B;
     u->build_attn_control(c, ck->mapper, ck->alpha, ck->weight, ck->B_ctrl, actl);
   }
   const size_t esz = f32 ? 4 : 2;
-  const int64_t chw = (int64_t)C * HW, n = (int64_t)B * chw;
+  const int64_t chw = (int64_t)C * HW, n = (int64_t)a.B * chw;
   // the local blend: the running sums of the encoder's and of the decoder's conditional rows [B | Bd][side][side], collected
   // beside every forward, and the keep-mask [Bd][HW] that k_local_blend_mask rewrites from them once per step
   WordMapCollect wm;
   float *acc = nullptr, *keep = nullptr;
   if (bk) {
     const int ss = bk->side * bk->side;
-    acc = (float*)h->arena.alloc((size_t)(B + Bd) * ss * 4);
+    acc = (float*)h->arena.alloc((size_t)(a.B + Bd) * ss * 4);
     keep = (float*)h->arena.alloc((size_t)Bd * HW * 4);
-    HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)(B + Bd) * ss * 4, h->st));
+    HIP_CHECK(hipMemsetAsync(acc, 0, (size_t)(a.B + Bd) * ss * 4, h->st));
     launch_fill_f32(h->st, keep, 1.f, (int64_t)Bd * HW);
     wm.N = 1; wm.min_side = wm.max_side = bk->side;
     WordMapCollect::Range rs, rt;
-    rs.row0 = ge.cfg ? B : 0; rs.rows = B; rs.sel = bk->sel_src; rs.B_sel = bk->B_sel; rs.acc = acc;
-    rt.row0 = Bn - Bd; rt.rows = Bd; rt.sel = bk->sel_tgt; rt.B_sel = bk->B_sel; rt.acc = acc + (size_t)B * ss;
+    rs.row0 = ge.cfg ? a.B : 0; rs.rows = a.B; rs.sel = bk->sel_src; rs.B_sel = bk->B_sel; rs.acc = acc;
+    rt.row0 = Bn - Bd; rt.rows = Bd; rt.sel = bk->sel_tgt; rt.B_sel = bk->B_sel; rt.acc = acc + (size_t)a.B * ss;
     wm.ranges = {rs, rt};
   }
-  float* xt_e = (float*)h->arena.alloc((size_t)B * chw * 4);
+  float* xt_e = (float*)h->arena.alloc((size_t)a.B * chw * 4);
   float* xt_d = (float*)h->arena.alloc((size_t)Bd * chw * 4);
   char* xin = (char*)h->arena.alloc((size_t)Bn * HW * cpad * esz);
   HIP_CHECK(hipMemsetAsync(xin, 0, (size_t)Bn * HW * cpad * esz, h->st));
@@ -839,63 +797,64 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
   bf16_t* xin_d = f32 ? nullptr : (bf16_t*)(xin + (size_t)Ben * row_in);
   StepArgs enc, dec;  // the step launches of the encoder's and of the decoder's rows
   EpsHat &eh_e = enc.eh, &eh_d = dec.eh;
-  eh_e.p = eh; eh_e.sb = (int64_t)HW * out_ld; eh_e.sc = 1; eh_e.sp = out_ld; eh_e.cfg = ge.cfg ? 1 : 0; eh_e.g = enc_guidance;
-  eh_d = eh_e; eh_d.p = eh + (int64_t)Ben * HW * out_ld; eh_d.cfg = gd.cfg ? 1 : 0; eh_d.g = dec_guidance;
-  eh_d.gvec = dec_guidance_per_sample;
-  StepCoef* tab_e = upload_coef(h, coef_enc_host, K + 1);
-  StepCoef* tab_d = upload_coef(h, coef_dec_host, K);
-  const int64_t zbs = (int64_t)(K + 1) * chw;
-  enc.x0 = x0; enc.xt = xt_e;
-  enc.geom.B = B; enc.geom.C = C; enc.geom.HW = HW; enc.geom.tab = tab_e;
+  eh_e.p = eh; eh_e.sb = (int64_t)HW * out_ld; eh_e.sc = 1; eh_e.sp = out_ld; eh_e.cfg = ge.cfg ? 1 : 0; eh_e.g = a.enc_guidance;
+  eh_d = eh_e; eh_d.p = eh + (int64_t)Ben * HW * out_ld; eh_d.cfg = gd.cfg ? 1 : 0; eh_d.g = a.dec_guidance;
+  eh_d.gvec = a.dec_guidance_per_sample;
+  StepCoef* tab_e = upload_coef(h, a.coef_enc_host, a.K + 1);
+  StepCoef* tab_d = upload_coef(h, a.coef_dec_host, a.K);
+  const int64_t zbs = (int64_t)(a.K + 1) * chw;
+  enc.x0 = a.x0; enc.xt = xt_e;
+  enc.geom.B = a.B; enc.geom.C = C; enc.geom.HW = HW; enc.geom.tab = tab_e;
   enc.xin.xin = xin_e; enc.xin.cpad = cpad; enc.xin.dup = ge.cfg ? 1 : 0;
-  enc.gauss.seed = seed; enc.z.bstride = zbs;
+  enc.gauss.seed = a.seed; enc.z.bstride = zbs;
   dec.xt = xt_d;
   dec.geom.B = Bd; dec.geom.C = C; dec.geom.HW = HW; dec.geom.tab = tab_d;
   dec.xin.xin = xin_d; dec.xin.cpad = cpad; dec.xin.dup = gd.cfg ? 1 + E : 0;  // every concept row's input is the row's latent
-  dec.gauss.seed = seed; dec.eps.bstride = zbs; dec.eps.bmod = n_dec > 1 ? B : 0;
+  dec.gauss.seed = a.seed; dec.eps.bstride = zbs; dec.eps.bmod = a.n_dec > 1 ? a.B : 0;
   // semantic guidance: two launches between the forward and the decode step turn u, c and the concept rows into the eps the
   // step reads - fp32 NCHW, no combine left to do (cfg = 0); no step kernel's arithmetic changes
   SegaStep sg;
   if (sk) {
     sg.eh = eh_d;
     sg.Bd = Bd; sg.C = C; sg.HW = HW; sg.E = E;
-    sg.tab = (const SegaConcept*)upload_table(h, sk->concepts, (size_t)E * sizeof(SegaConcept));
+    sg.tab = (const SegaConcept*)upload_table(h, sk->concepts_host, (size_t)E * sizeof(SegaConcept));
     sg.abuf = (float*)h->arena.alloc((size_t)Bd * E * chw * 4);
-    sg.tau = (float*)h->arena.alloc((size_t)K * Bd * E * 4);  // [K, Bd, E]: 0 where the concept is inactive
-    sg.kept = (int*)h->arena.alloc((size_t)K * Bd * E * 4);
+    sg.tau = (float*)h->arena.alloc((size_t)a.K * Bd * E * 4);  // [K, Bd, E]: 0 where the concept is inactive
+    sg.kept = (int*)h->arena.alloc((size_t)a.K * Bd * E * 4);
     sg.nu = (float*)h->arena.alloc((size_t)Bd * chw * 4);     // zero before iteration 0, nothing kept between calls
     sg.eps = (float*)h->arena.alloc((size_t)Bd * chw * 4);
-    sg.s_m = sk->s_m; sg.beta = sk->beta;
-    HIP_CHECK(hipMemsetAsync(sg.tau, 0, (size_t)K * Bd * E * 4, h->st));
-    HIP_CHECK(hipMemsetAsync(sg.kept, 0, (size_t)K * Bd * E * 4, h->st));
+    sg.s_m = sk->momentum_scale; sg.beta = sk->momentum_beta;
+    HIP_CHECK(hipMemsetAsync(sg.tau, 0, (size_t)a.K * Bd * E * 4, h->st));
+    HIP_CHECK(hipMemsetAsync(sg.kept, 0, (size_t)a.K * Bd * E * 4, h->st));
     HIP_CHECK(hipMemsetAsync(sg.nu, 0, (size_t)Bd * chw * 4, h->st));
     if (sk->mask_out) HIP_CHECK(hipMemsetAsync(sk->mask_out, 0, (size_t)Bd * E * chw * 4, h->st));
     eh_d.p = sg.eps; eh_d.sb = chw; eh_d.sc = HW; eh_d.sp = 1; eh_d.cfg = 0; eh_d.gvec = nullptr;
   }
   // x_T (ddim.py:477-479), z[:, 0]; the decoder starts from the same tensor (sd_wrapper:153), once per decoder scale
-  enc.geom.step = K; enc.gauss.noise = noise; enc.gauss.stream = 0u; enc.z.p = z_out;
+  enc.geom.step = a.K; enc.gauss.noise = a.noise; enc.gauss.stream = 0u; enc.z.p = a.z_out;
   launch_init_xt(h->st, enc);
-  for (int j = 0; j < n_dec; ++j)
+  for (int j = 0; j < a.n_dec; ++j)
     HIP_CHECK(hipMemcpyAsync(xt_d + (int64_t)j * n, xt_e, (size_t)n * 4, hipMemcpyDeviceToDevice, h->st));
   // the keep-mask blend of level k for the decoder rows: q_sample(x0) with the draw of iteration `slot`, or - "encoder" - the
   // DPM-Encoder's own x_t of that level, which is what xt_e holds once the encoder's step kernel of the iteration has run
   const float2* qtab = nullptr;
-  if (mk && mk->source == CD_MASK_QSAMPLE) qtab = (const float2*)upload_table(h, mk->qcoef_host, (size_t)K * 2 * sizeof(float));
+  if (mk && mk->source == CD_MASK_QSAMPLE)
+    qtab = (const float2*)upload_table(h, mk->qsample_coef_host, (size_t)a.K * 2 * sizeof(float));
   auto blend_of = [&](int k, int slot) {
     MaskBlend b = mask_blend_of(*mk, qtab, k, slot, (int64_t)Bd * chw);
-    if (mk->source == CD_MASK_ENCODER) { b.src = xt_e; b.src_bmod = B; }
+    if (mk->source == CD_MASK_ENCODER) { b.src = xt_e; b.src_bmod = a.B; }
     return b;
   };
-  if (mk) launch_mask_blend_init(h->st, dec, blend_of(K - 1, 0));
+  if (mk) launch_mask_blend_init(h->st, dec, blend_of(a.K - 1, 0));
   else if (!f32) launch_nchw_to_nhwc(h->st, xt_d, xin_d, Bd, C, HW, cpad, 1.f, 0.f, gd.cfg ? 1 + E : 0);
   // rows that repeat the rows just ahead of them (the decoder's cond half repeats its uncond half): the network computes
   // everything ahead of the first cross-attention once for them - only when the encoder half has no such pair of its own
   // (not under semantic guidance: the shared prefix covers one pair of halves, not the concept rows between them)
   const int dup_tail = (gd.cfg && !ge.cfg && !sk) ? Bd : 0;
-  for (int i = 0; i < K; ++i) {
-    const int k = K - 1 - i;
+  for (int i = 0; i < a.K; ++i) {
+    const int k = a.K - 1 - i;
     if (f32) {
-      put_net_input(h, u, xt_e, xin, B, C, HW, cpad, 1.f, ge.cfg);
+      put_net_input(h, u, xt_e, xin, a.B, C, HW, cpad, 1.f, ge.cfg);
       put_net_input(h, u, xt_d, xin + (size_t)Ben * row_in, Bd, C, HW, cpad, 1.f, gd.cfg);
     }
     UNetIO io;
@@ -905,148 +864,57 @@ static void cycle_translate_impl(cd_handle h, int net, int sched_kind, const flo
     io.maps = bk ? &wm : nullptr;
     io.out = eh; io.out_ld = out_ld;
     u->forward(c, io);
-    const int is_last = (last_uses_x0 && k == 0) ? 1 : 0;
-    const float* nz = (noise && !is_last) ? noise + (int64_t)(1 + i) * n : nullptr;
-    float* zslot = z_out + (1 + i) * chw;
+    const int is_last = (a.last_uses_x0 && k == 0) ? 1 : 0;
+    const float* nz = (a.noise && !is_last) ? a.noise + (int64_t)(1 + i) * n : nullptr;
+    float* zslot = a.z_out + (1 + i) * chw;
     enc.geom.step = k; enc.is_last = is_last;
     enc.gauss.noise = nz; enc.gauss.stream = (uint32_t)(1 + i); enc.z.p = zslot;
-    launch_encode_step(h->st, sched_kind, enc);
+    launch_encode_step(h->st, a.sched_kind, enc);
     dec.geom.step = k; dec.eps.p = zslot; dec.gauss.stream = (uint32_t)(0x1000 + i);
     if (sk) {
       SegaStep it = sg;
-      it.active = sega_active_mask(sk->concepts, E, i);
+      it.active = sega_active_mask(sk->concepts_host, E, i);
       it.tau = sg.tau + (size_t)i * Bd * E; it.kept = sg.kept + (size_t)i * Bd * E;
       it.mask_out = it.active ? sk->mask_out : nullptr;  // the mask of the last iteration in which a concept was active
       launch_sega_guidance(h->st, it);
     }
     if (mk) {
       const MaskBlend next = blend_of(k - 1, i + 1);
-      launch_decode_step(h->st, sched_kind, dec, &next, /*blend=*/k > 0);
+      launch_decode_step(h->st, a.sched_kind, dec, &next, /*blend=*/k > 0);
     } else if (bk && i >= bk->n_start) {
       // the mask of this step from the sums so far, then the step and - the last step included - the blend with the
       // encoder's x of the level just arrived at (xt_e after the encoder's step kernel above)
       LocalBlendMask lm;
-      lm.acc_src = acc; lm.acc_tgt = acc + (size_t)B * bk->side * bk->side; lm.keep = keep;
-      lm.B = B; lm.Bd = Bd; lm.side = bk->side; lm.f = u->image_size / bk->side; lm.pool = bk->pool; lm.thr = bk->thr;
+      lm.acc_src = acc; lm.acc_tgt = acc + (size_t)a.B * bk->side * bk->side; lm.keep = keep;
+      lm.B = a.B; lm.Bd = Bd; lm.side = bk->side; lm.f = u->image_size / bk->side; lm.pool = bk->pool; lm.thr = bk->thr;
       launch_local_blend_mask(h->st, lm);
       MaskBlend lb;
-      lb.mask = keep; lb.mask_bmod = Bd; lb.src = xt_e; lb.src_bmod = B;
-      launch_decode_step(h->st, sched_kind, dec, &lb, /*blend=*/true);
+      lb.mask = keep; lb.mask_bmod = Bd; lb.src = xt_e; lb.src_bmod = a.B;
+      launch_decode_step(h->st, a.sched_kind, dec, &lb, /*blend=*/true);
     } else {
-      launch_decode_step(h->st, sched_kind, dec);
+      launch_decode_step(h->st, a.sched_kind, dec);
     }
     h->pacer.tick(h->st);
   }
-  HIP_CHECK(hipMemcpyAsync(x_out, xt_d, (size_t)Bd * chw * 4, hipMemcpyDeviceToDevice, h->st));
+  HIP_CHECK(hipMemcpyAsync(a.x_out, xt_d, (size_t)Bd * chw * 4, hipMemcpyDeviceToDevice, h->st));
   if (sk && sk->tau_out)
-    HIP_CHECK(hipMemcpyAsync(sk->tau_out, sg.tau, (size_t)K * Bd * E * 4, hipMemcpyDeviceToDevice, h->st));
+    HIP_CHECK(hipMemcpyAsync(sk->tau_out, sg.tau, (size_t)a.K * Bd * E * 4, hipMemcpyDeviceToDevice, h->st));
   if (sk && sk->kept_out)
-    HIP_CHECK(hipMemcpyAsync(sk->kept_out, sg.kept, (size_t)K * Bd * E * 4, hipMemcpyDeviceToDevice, h->st));
+    HIP_CHECK(hipMemcpyAsync(sk->kept_out, sg.kept, (size_t)a.K * Bd * E * 4, hipMemcpyDeviceToDevice, h->st));
   if (bk && bk->acc_out)
-    HIP_CHECK(hipMemcpyAsync(bk->acc_out, acc, (size_t)(B + Bd) * bk->side * bk->side * 4, hipMemcpyDeviceToDevice, h->st));
+    HIP_CHECK(hipMemcpyAsync(bk->acc_out, acc, (size_t)(a.B + Bd) * bk->side * bk->side * 4, hipMemcpyDeviceToDevice, h->st));
   if (bk && bk->keep_out)
     HIP_CHECK(hipMemcpyAsync(bk->keep_out, keep, (size_t)Bd * HW * 4, hipMemcpyDeviceToDevice, h->st));
 }
 
-int cd_cycle_translate(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
-                       const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
-                       float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
-                       const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                       uint64_t seed, int last_uses_x0, float* z_out, float* x_out) {
+int cd_cycle_translate(cd_handle h, const cd_translate_args* a) {
   CD_API_BEGIN
+  CD_CHECK(a, "cd_cycle_translate: the argument struct is NULL");
+  CD_CHECK(a->size == sizeof(cd_translate_args), "cd_cycle_translate: the argument struct says size = %u, this library's "
+           "sizeof(cd_translate_args) is %zu: built against another version of cyclediff.h?", (unsigned)a->size,
+           sizeof(cd_translate_args));
   enter_engine(h);
-  cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
-                       dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
-                       z_out, x_out, nullptr);
-  CD_API_END
-}
-
-// The coupled loop with a keep-mask on its decoder rows. mask_source = CD_MASK_ENCODER keeps the region on the source image's
-// OWN trajectory: the encoder's x_t of every level is live in the same iteration (the reference's "deterministic forward
-// pass?" TODO, ddim.py:429), no extra noise is drawn.
-int cd_cycle_translate_masked(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
-                              const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
-                              float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
-                              const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                              uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
-                              int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
-                              float* z_out, float* x_out) {
-  CD_API_BEGIN
-  enter_engine(h);
-  const MaskArgs mk = mask_args_of(mask, mask_x0, B_mask, mask_source, qsample_coef_host, mask_noise, mask_seed);
-  cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
-                       dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
-                       z_out, x_out, &mk);
-  CD_API_END
-}
-
-// The coupled loop with cross-attention control on its first n_ctrl iterations, with or without a keep-mask.
-int cd_cycle_translate_ctrl(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
-                            const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
-                            float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
-                            const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                            uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
-                            int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
-                            const float* mapper, const float* alpha, const float* weight, int B_ctrl, int n_ctrl,
-                            float* z_out, float* x_out) {
-  CD_API_BEGIN
-  enter_engine(h);
-  const MaskArgs mk = mask_args_of(mask, mask_x0, B_mask, mask_source, qsample_coef_host, mask_noise, mask_seed);
-  CtrlArgs ck;
-  ck.mapper = mapper; ck.alpha = alpha; ck.weight = weight; ck.B_ctrl = B_ctrl; ck.n_ctrl = n_ctrl;
-  cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
-                       dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
-                       z_out, x_out, mask ? &mk : nullptr, &ck);
-  CD_API_END
-}
-
-// The coupled loop with prompt-to-prompt's local blend: the word maps of the encoder's and of the decoder's
-// conditional rows are collected beside every forward, and from iteration n_start on the decoder's latent is held to the
-// encoder's outside the region the maps mark, the mask rebuilt after every step. With or without cross-attention control.
-int cd_cycle_translate_blend(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
-                             const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
-                             float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
-                             const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                             uint64_t seed, int last_uses_x0, const float* mapper, const float* alpha, const float* weight,
-                             int B_ctrl, int n_ctrl, const float* sel_src, const float* sel_tgt, int B_sel, int side, int pool,
-                             float thr, int n_start, float* acc_out, float* keep_out, float* z_out, float* x_out) {
-  CD_API_BEGIN
-  enter_engine(h);
-  CtrlArgs ck;
-  ck.mapper = mapper; ck.alpha = alpha; ck.weight = weight; ck.B_ctrl = B_ctrl; ck.n_ctrl = n_ctrl;
-  BlendArgs bk;
-  bk.sel_src = sel_src; bk.sel_tgt = sel_tgt; bk.B_sel = B_sel; bk.side = side; bk.pool = pool; bk.thr = thr;
-  bk.n_start = n_start; bk.acc_out = acc_out; bk.keep_out = keep_out;
-  cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
-                       dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
-                       z_out, x_out, nullptr, &ck, &bk);
-  CD_API_END
-}
-
-// The coupled loop with semantic guidance on its decoder rows: E concept rows per decoder row ride in the same
-// forward, and k_sega_threshold / k_sega_combine (sega.hip) build the eps of the unchanged decode step from them. With or
-// without a keep-mask and cross-attention control.
-int cd_cycle_translate_sega(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
-                            const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
-                            float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
-                            const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                            uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
-                            int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
-                            const float* mapper, const float* alpha, const float* weight, int B_ctrl, int n_ctrl,
-                            const float* edit_ctx, const cd_sega_concept* concepts_host, int E, float momentum_scale,
-                            float momentum_beta, float* tau_out, int32_t* kept_out, float* mask_out, float* z_out,
-                            float* x_out) {
-  CD_API_BEGIN
-  enter_engine(h);
-  const MaskArgs mk = mask_args_of(mask, mask_x0, B_mask, mask_source, qsample_coef_host, mask_noise, mask_seed);
-  CtrlArgs ck;
-  ck.mapper = mapper; ck.alpha = alpha; ck.weight = weight; ck.B_ctrl = B_ctrl; ck.n_ctrl = n_ctrl;
-  SegaArgs sk;
-  sk.edit_ctx = edit_ctx; sk.concepts = concepts_host; sk.E = E; sk.s_m = momentum_scale; sk.beta = momentum_beta;
-  sk.tau_out = tau_out; sk.kept_out = kept_out; sk.mask_out = mask_out;
-  cycle_translate_impl(h, net, sched_kind, x0, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc, dec_guidance,
-                       dec_guidance_per_sample, ctx_len, B, n_dec, K, coef_enc_host, coef_dec_host, noise, seed, last_uses_x0,
-                       z_out, x_out, mask ? &mk : nullptr, &ck, nullptr, &sk);
+  cycle_translate_impl(h, *a);
   CD_API_END
 }
 

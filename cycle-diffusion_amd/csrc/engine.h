@@ -330,7 +330,7 @@ struct WordMapCollect {
   float* acc = nullptr;            // [rows][N][h][w] sums over the included layers, in the forward's order
   int B = 0, n_chunk = 0;          // rows = n_chunk * B: sample b of draw i uses selector entry b % B_sel
   mutable int layers = 0;          // blocks included so far in this forward
-  // The ranged form (cd_cycle_translate_blend): instead of all rows of the forward, the map kernel runs once
+  // The ranged form (cd_local_blend): instead of all rows of the forward, the map kernel runs once
   // per range on rows [row0, row0 + rows) with N = 1, row r of the range using selector entry r % B_sel, and the range's own
   // sums acc [rows][side][side] stay on the token grid. The sums run on across the forwards of a call: they start from 0 at
   // the first included block of the first forward (`seen` counts the blocks of all forwards). The batch may have repeated

@@ -599,18 +599,15 @@ class Engine:
     def _cycle_translate(self, net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
                          dec_guidance, n_dec, noise, seed, last_uses_x0, mask=None, mask_x0=None, qcoef=None, mask_noise=None,
                          mask_seed=0, mask_source="q_sample", ctrl=None, blend=None, sega=None):
-        """The marshalling of the coupled entry points: cd_cycle_translate without a mask and without `ctrl`,
-        cd_cycle_translate_masked with a mask only, cd_cycle_translate_ctrl with `ctrl` = (mapper, alpha, weight, n_ctrl) - the
-        argument list of each is the one before it plus a tail, as cycle_translate_impl serves them from one body.
-        cd_cycle_translate_blend with `blend` = (sel_src, sel_tgt, side, pool, thr, n_start) takes the control's tail (none:
-        NULL and n_ctrl = 0) without the mask's, then its own; it returns (z, x, acc, keep).
-        cd_cycle_translate_sega with `sega` = (edit_ctx, concepts, momentum_scale, momentum_beta) takes the mask's and the
-        control's tails (none: NULL / 0), then its own; it returns (z, x, tau, kept, mask)."""
+        """The marshalling of cd_cycle_translate: one cd_translate_args, and an option struct for each of the keep-mask, `ctrl` =
+        (mapper, alpha, weight, n_ctrl), `blend` = (sel_src, sel_tgt, side, pool, thr, n_start) - it returns (z, x, acc, keep) -
+        and `sega` = (edit_ctx, concepts, momentum_scale, momentum_beta) - it returns (z, x, tau, kept, mask). An option that is
+        None stays a NULL pointer; which options go together is cycle_translate_impl's decision, repeated here only where a
+        ValueError can say it earlier."""
         x0 = self._f32(x0)
         K = len(coef_dec)
         assert len(coef_enc) == K + 1
         B, Cc, H, W = x0.shape
-        Bm, src = 0, _ffi.CD_MASK_QSAMPLE
         if mask is not None:
             mask, mask_x0, Bm, src, qcoef, mask_noise = self._mask_args(mask, mask_x0, B, qcoef, mask_noise, mask_source, H, W,
                                                                         Cc, K, b_noise=n_dec * B)
@@ -623,26 +620,25 @@ class Engine:
         L = next((t.shape[1] for t in ctxs if t is not None), 0)
         for t, rows in zip(ctxs, (B, B, n_dec * B, n_dec * B)):
             assert t is None or t.shape[0] == rows, (t.shape, rows)
-        fn, tail, ctl, sels, outs = self.lib.cd_cycle_translate, [], None, None, ()
+        a = _ffi.TranslateArgs(size=C.sizeof(_ffi.TranslateArgs))
+        ctl, sels, outs = None, None, ()
         if blend is not None and mask is not None:
             raise ValueError("the local blend rewrites the keep-mask after every step: it takes no mask of the caller's")
         if blend is not None and sega is not None:
             raise ValueError("semantic guidance and the local blend are not built together")
-        if blend is None and (mask is not None or ctrl is not None or sega is not None):
-            fn = self.lib.cd_cycle_translate_masked
-            tail = [ptr(mask), ptr(mask_x0), Bm, src, C.c_void_p(qcoef.ctypes.data) if qcoef is not None else None,
-                    ptr(mask_noise), C.c_uint64(mask_seed)]
+        if mask is not None:
+            a.mask = C.pointer(_ffi.KeepMask(
+                mask=ptr(mask), x0=ptr(mask_x0), B_mask=Bm, source=src,
+                qsample_coef_host=qcoef.ctypes.data if qcoef is not None else None, noise=ptr(mask_noise), seed=mask_seed))
         if ctrl is not None:
             ctl = [torch.as_tensor(t, dtype=torch.float32).to(x0.device).contiguous() for t in ctrl[:3]]
             Bc = ctl[0].shape[0]
             if tuple(ctl[0].shape) != (Bc, L, L) or tuple(ctl[1].shape) != (Bc, L) or tuple(ctl[2].shape) != (Bc, L):
                 raise ValueError("control tensors must be mapper [B_ctrl, %d, %d], alpha / weight [B_ctrl, %d], got %s"
                                  % (L, L, L, [tuple(t.shape) for t in ctl]))
-            fn = self.lib.cd_cycle_translate_ctrl
-            tail += [ptr(ctl[0]), ptr(ctl[1]), ptr(ctl[2]), Bc, int(ctrl[3])]
+            a.ctrl = C.pointer(_ffi.AttnCtrl(mapper=ptr(ctl[0]), alpha=ptr(ctl[1]), weight=ptr(ctl[2]), B_ctrl=Bc,
+                                             n_ctrl=int(ctrl[3])))
         if sega is not None:
-            if ctrl is None:
-                tail += [None, None, None, 0, 0]
             ectx = self._f32(sega[0])
             table = np.ascontiguousarray(sega[1], dtype=_ffi.SEGA_CONCEPT_DTYPE)
             E, Bd = len(table), n_dec * B
@@ -652,14 +648,11 @@ class Engine:
             tau = torch.empty((K, Bd, E), device=x0.device, dtype=torch.float32)
             kept = torch.empty((K, Bd, E), device=x0.device, dtype=torch.int32)
             emask = torch.empty((Bd, E, Cc, H, W), device=x0.device, dtype=torch.float32)
-            fn = self.lib.cd_cycle_translate_sega
-            tail += [ptr(ectx), C.c_void_p(table.ctypes.data), E, C.c_float(sega[2]), C.c_float(sega[3]), ptr(tau), ptr(kept),
-                     ptr(emask)]
+            a.sega = C.pointer(_ffi.Sega(edit_ctx=ptr(ectx), concepts_host=table.ctypes.data, E=E, momentum_scale=sega[2],
+                                         momentum_beta=sega[3], tau_out=ptr(tau), kept_out=ptr(kept), mask_out=ptr(emask)))
             sels = (ectx, table)
             outs = (tau, kept, emask)
         if blend is not None:
-            if ctrl is None:
-                tail = [None, None, None, 0, 0]
             sels = [torch.as_tensor(t, dtype=torch.float32).to(x0.device).contiguous() for t in blend[:2]]
             Bs = sels[0].shape[0]
             if sels[0].dim() != 2 or tuple(sels[0].shape) != (Bs, L) or tuple(sels[1].shape) != (Bs, L):
@@ -670,14 +663,17 @@ class Engine:
                 raise ValueError("the local blend: side = %d is not a token grid side" % side)
             acc = torch.empty(((1 + n_dec) * B, side, side), device=x0.device, dtype=torch.float32)
             keep = torch.empty((n_dec * B, 1, H, W), device=x0.device, dtype=torch.float32)
-            fn = self.lib.cd_cycle_translate_blend
-            tail += [ptr(sels[0]), ptr(sels[1]), Bs, side, pool, C.c_float(thr), n_start, ptr(acc), ptr(keep)]
+            a.blend = C.pointer(_ffi.LocalBlend(sel_src=ptr(sels[0]), sel_tgt=ptr(sels[1]), B_sel=Bs, side=side, pool=pool,
+                                                thr=thr, n_start=n_start, acc_out=ptr(acc), keep_out=ptr(keep)))
             outs = (acc, keep)
         gvec, gscalar = self._guidance(dec_guidance, n_dec * B, "n_dec * B", x0.device)
         nz = self._f32(noise) if noise is not None else None
-        check(fn(self.h, net, kind, ptr(x0), ptr(ctxs[0]), ptr(ctxs[1]), C.c_float(enc_guidance), ptr(ctxs[2]), ptr(ctxs[3]),
-                 C.c_float(gscalar), ptr(gvec), L, B, n_dec, K, C.c_void_p(coef_enc.ctypes.data), C.c_void_p(coef_dec.ctypes.data),
-                 ptr(nz), C.c_uint64(seed), int(last_uses_x0), *tail, ptr(z), ptr(x)))
+        a.net, a.sched_kind, a.x0, a.ctx_len, a.B, a.n_dec, a.K = net, kind, ptr(x0), L, B, n_dec, K
+        a.enc_ctx_c, a.enc_ctx_uc, a.enc_guidance = ptr(ctxs[0]), ptr(ctxs[1]), enc_guidance
+        a.dec_ctx_c, a.dec_ctx_uc, a.dec_guidance, a.dec_guidance_per_sample = ptr(ctxs[2]), ptr(ctxs[3]), gscalar, ptr(gvec)
+        a.coef_enc_host, a.coef_dec_host = coef_enc.ctypes.data, coef_dec.ctypes.data
+        a.noise, a.seed, a.last_uses_x0, a.z_out, a.x_out = ptr(nz), seed, int(last_uses_x0), ptr(z), ptr(x)
+        check(self.lib.cd_cycle_translate(self.h, C.byref(a)))
         self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise, ctl, sels)  # the launches read them asynchronously
         return (z, x) + outs
 
@@ -749,7 +745,7 @@ class Engine:
                                mask_seed=0, mask_source="q_sample", enc_ctx_c=None, enc_ctx_uc=None, enc_guidance=1.0,
                                dec_ctx_c=None, dec_ctx_uc=None, dec_guidance=1.0, n_dec=1, noise=None, seed=0,
                                last_uses_x0=True):
-        """cd_cycle_translate_masked: cycle_translate with the keep-mask on the decoder rows. mask [B_mask, 1, H, W], B_mask
+        """cd_keep_mask: cycle_translate with the keep-mask on the decoder rows. mask [B_mask, 1, H, W], B_mask
         dividing B. "q_sample": mask_x0 [B_mask, C, H, W], qcoef = coef_qsample(skip), mask_noise [K, n_dec * B, C, H, W] or
         None; "encoder": the kept region follows the encoder's own x_t of every level, nothing else is passed or drawn."""
         # _f32(mask): the mask is not optional here - None is an error, never the unmasked loop
@@ -761,7 +757,7 @@ class Engine:
                              qcoef=None, mask_noise=None, mask_seed=0, mask_source="q_sample", enc_ctx_c=None, enc_ctx_uc=None,
                              enc_guidance=1.0, dec_ctx_c=None, dec_ctx_uc=None, dec_guidance=1.0, n_dec=1, noise=None, seed=0,
                              last_uses_x0=True):
-        """cd_cycle_translate_ctrl: cycle_translate (mask=None) or cycle_translate_masked with cross-attention control on the
+        """cd_attn_ctrl: cycle_translate (mask=None) or cycle_translate_masked with cross-attention control on the
         first n_ctrl iterations. mapper [B_ctrl, L, L], alpha / weight [B_ctrl, L] (attn_control.build_control), B_ctrl
         dividing B; the decoder's conditional rows take P = w * (alpha * (P_src . M) + (1 - alpha) * P_own) in every text
         cross-attention, P_src from the encoder's conditional row of the same sample in the same forward."""
@@ -772,7 +768,7 @@ class Engine:
     def cycle_translate_blend(self, net, kind, x0, coef_enc, coef_dec, sel_src, sel_tgt, side, pool=3, thr=0.3, n_start=0,
                               ctrl=None, enc_ctx_c=None, enc_ctx_uc=None, enc_guidance=1.0, dec_ctx_c=None, dec_ctx_uc=None,
                               dec_guidance=1.0, n_dec=1, noise=None, seed=0, last_uses_x0=True):
-        """cd_cycle_translate_blend: cycle_translate (or, with ctrl = (mapper, alpha, weight, n_ctrl), cycle_translate_ctrl)
+        """cd_local_blend: cycle_translate (or, with ctrl = (mapper, alpha, weight, n_ctrl), cycle_translate_ctrl)
         with prompt-to-prompt's local blend. sel_src / sel_tgt [B_sel, L] weigh the key positions of the source / target
         prompt, B_sel dividing B; the maps of the text cross-attentions of token grid `side` on them are summed over layers and
         steps, and from iteration n_start on every step is followed by x <- x_enc * keep + (1 - keep) * x with keep rebuilt from
@@ -786,7 +782,7 @@ class Engine:
                              ctrl=None, mask=None, mask_x0=None, qcoef=None, mask_noise=None, mask_seed=0,
                              mask_source="q_sample", enc_ctx_c=None, enc_ctx_uc=None, enc_guidance=1.0, dec_ctx_c=None,
                              dec_ctx_uc=None, dec_guidance=1.0, n_dec=1, noise=None, seed=0, last_uses_x0=True):
-        """cd_cycle_translate_sega: cycle_translate (or, with mask / ctrl = (mapper, alpha, weight, n_ctrl), its masked /
+        """cd_sega: cycle_translate (or, with mask / ctrl = (mapper, alpha, weight, n_ctrl), its masked /
         controlled form) with semantic guidance. edit_ctx [E * n_dec * B, L, Dc] concept-major; concepts: E rows of
         (scale, weight, lo, frac, warm, cool) (semantic_guidance.concept_table). Returns (z, x, tau [K, n_dec * B, E],
         kept [K, n_dec * B, E] int32, mask [n_dec * B, E, C, H, W] of 0 / 1 from the last iteration with an active concept)."""

@@ -59,7 +59,7 @@ def parse_concepts(spec):
 
 
 def check_concepts(concepts, momentum_scale=0.0, momentum_beta=0.0):
-    """what can be refused without the loop's length: each refusal of cd_cycle_translate_sega that concerns the concepts"""
+    """what can be refused without the loop's length: each refusal of semantic guidance (cd_sega) that concerns the concepts"""
     if not 1 <= len(concepts) <= MAX_CONCEPTS:
         raise ValueError("semantic guidance takes 1 to %d concepts, got %d" % (MAX_CONCEPTS, len(concepts)))
     for c in concepts:

@@ -220,24 +220,6 @@ int cd_ddim_invert(cd_handle h, int net, int sched_kind, const float* x0, const 
                    int ctx_len, float guidance, int B, int K, const cd_step_coef* coef_host, float* x_out,
                    float* traj_out);
 
-/* The coupled source -> target loop in ONE call: what Model.forward composes from the wrapper's encode() and forward()
- * (model/text_unsupervised_translation.py:24-40: z = gan_wrapper.encode(image, encode_text); img = gan_wrapper(z, ...)) when
- * both run on the same network over the whole chain (white_box_steps = custom_steps + 1): the DPM-Encoder step and the decode
- * step of index k evaluate the network at the same timestep, and the decode step needs eps_k only after its forward, so each
- * of the K iterations runs ONE forward over [encoder rows | decoder rows], then the encoder's step kernel (ddim.py:582-601,
- * 545-580) and the decoder's (ddim.py:603-646), which reads the eps the encoder just wrote.
- *   x0 [B,C,H,W]; enc_ctx_* [B,L,Dc] and enc_guidance as cd_dpm_encode's; the decoder runs n_dec decodes per encoder sample
- *   (the wrapper's decoder_unconditional_guidance_scales of one kind, sd_wrapper:155-166): dec_ctx_* [n_dec*B,L,Dc], decoder
- *   row j*B + b decodes the z of encoder sample b; dec_guidance (scalar) or dec_guidance_per_sample (device, n_dec*B floats,
- *   each neither 0 nor 1) as cd_ddim_decode / cd_ddim_decode_v; coef_enc_host K+1 rows, coef_dec_host K rows (the same rows
- *   0..K-1); noise [K,B,C,H,W] or NULL and last_uses_x0 as cd_dpm_encode's.
- *   z_out [B,K+1,C,H,W] (what encode() returns), x_out [n_dec*B,C,H,W] (what the decode returns). */
-int cd_cycle_translate(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
-                       const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
-                       float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
-                       const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                       uint64_t seed, int last_uses_x0, float* z_out, float* x_out);
-
 /* Region-keeping decode: DDIMSampler.sample_with_eps(..., mask=, x0=) (ddim.py:170-228; the branch at :427-430). Ahead of the
  * forward of EVERY step, the first included, the running latent is replaced by
  *     x <- src_k * m + (1 - m) * x          (fp32, in that operation order; m = 1 keeps the source, m is broadcast over C)
@@ -257,49 +239,52 @@ int cd_ddim_decode_masked(cd_handle h, int net, int sched_kind, const float* z, 
                           const float* x0, int B_mask, int mask_source, const float* qsample_coef_host,
                           const float* mask_noise, uint64_t mask_seed, float* x_out);
 
-/* cd_cycle_translate with the keep-mask on its decoder rows. Arguments up to last_uses_x0 as cd_cycle_translate's; the mask
- * arguments as cd_ddim_decode_masked's with the decoder's batch n_dec*B in the place of B (mask_noise [K,n_dec*B,C,H,W]; decoder
- * row r uses mask row r % B_mask, B a multiple of B_mask), mask_x0 [B_mask,C,H,W] the x0 of the blend.
- *   mask_source = CD_MASK_QSAMPLE: per-sample arithmetic of cd_dpm_encode followed by cd_ddim_decode_masked, bit for bit.
- *   mask_source = CD_MASK_ENCODER: src_k = the encoder's x_t at level k of encoder sample r % B, bit for bit (x_T for the first
- *   forward); no noise is drawn; qsample_coef_host and mask_noise must be NULL, mask_x0 is not read. */
-int cd_cycle_translate_masked(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
-                              const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
-                              float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
-                              const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                              uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
-                              int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
-                              float* z_out, float* x_out);
+/* ---- the coupled translate loop: cd_cycle_translate(h, &args), its options as structs of their own (NULL = off) ---------- */
 
-/* cd_cycle_translate(_masked) with cross-attention control (prompt-to-prompt on the coupled loop; the paper's "CycleDiffusion +
- * CAC") on the first n_ctrl iterations (iteration 0 = the noisiest step). Arguments up to mask_seed as
- * cd_cycle_translate_masked's, with mask = NULL for no keep-mask (the other mask arguments are then ignored). In every text
+/* The keep-mask on the decoder rows of cd_cycle_translate: the fields as the mask arguments of cd_ddim_decode_masked with the
+ * decoder's batch n_dec*B in the place of B (noise [K,n_dec*B,C,H,W]; decoder row r uses mask row r % B_mask, B a multiple of
+ * B_mask), x0 [B_mask,C,H,W] the x0 of the blend.
+ *   source = CD_MASK_QSAMPLE: per-sample arithmetic of cd_dpm_encode followed by cd_ddim_decode_masked, bit for bit.
+ *   source = CD_MASK_ENCODER: src_k = the encoder's x_t at level k of encoder sample r % B, bit for bit (x_T for the first
+ *   forward); no noise is drawn; qsample_coef_host and noise must be NULL, x0 is not read.
+ * A struct whose `mask` is NULL is refused; no keep-mask is cd_translate_args.mask = NULL. */
+typedef struct cd_keep_mask {
+  const float* mask;               /* [B_mask,1,H,W] in [0,1]; 1 keeps the source */
+  const float* x0;                 /* [B_mask,C,H,W] */
+  int B_mask;
+  int source;                      /* CD_MASK_QSAMPLE / CD_MASK_ENCODER */
+  const float* qsample_coef_host;  /* K rows of (qa, qb), row index = k */
+  const float* noise;              /* [K,n_dec*B,C,H,W] or NULL -> Philox(seed) */
+  uint64_t seed;
+} cd_keep_mask;
+
+/* Cross-attention control (prompt-to-prompt on the coupled loop; the paper's "CycleDiffusion + CAC") on the first n_ctrl
+ * iterations (iteration 0 = the noisiest step), with or without a keep-mask. In every text
  * cross-attention of those iterations, head h of decoder CONDITIONAL row r (sample b = r % B) computes
  *     P = w * (alpha * (P_src . M) + (1 - alpha) * P_own),   O = P . V_own        (rows of P are not renormalised)
  * where P_own is the row's own softmax(Q K^T * scale) and P_src that of the encoder's conditional row of sample b in the SAME
  * forward against the source context; the products with alpha [L] and w [L] run over the key axis. mapper [B_ctrl,L,L],
  * alpha / weight [B_ctrl,L] are fp32 device tensors, B a multiple of B_ctrl: sample b uses entry b % B_ctrl (members of a
  * folded ensemble share their sample's control). Encoder rows, unconditional rows and iterations >= n_ctrl run exactly the
- * kernels of cd_cycle_translate: z_out is bit-identical to the uncontrolled call's, and n_ctrl = 0 is that call.
+ * kernels of the call without control: z_out is bit-identical to the uncontrolled call's, and n_ctrl = 0 is that call.
  * Refused (error text, nothing launched): coefficient tables whose rows k < K disagree on the timestep (checked for every
  * n_ctrl), and for n_ctrl != 0: n_ctrl outside [0, K], sched_kind != CD_SCHED_DDIM, networks without a text context, networks
  * of precision CD_PREC_F32 / CD_PREC_F32X3, ctx_len > 96, B % B_ctrl != 0, a pass without conditional rows (guidance 0). */
-int cd_cycle_translate_ctrl(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
-                            const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
-                            float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
-                            const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                            uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
-                            int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
-                            const float* mapper, const float* alpha, const float* weight, int B_ctrl, int n_ctrl,
-                            float* z_out, float* x_out);
+typedef struct cd_attn_ctrl {
+  const float* mapper;  /* [B_ctrl,L,L] */
+  const float* alpha;   /* [B_ctrl,L] */
+  const float* weight;  /* [B_ctrl,L] */
+  int B_ctrl;
+  int n_ctrl;
+} cd_attn_ctrl;
 
-/* cd_cycle_translate(_ctrl) with prompt-to-prompt's LocalBlend (Hertz et al. 2022; no counterpart in the reference tree,
+/* Prompt-to-prompt's LocalBlend (Hertz et al. 2022; no counterpart in the reference tree,
  * DESIGN.md 18): the target is edited only where the word maps of this very sampling run - source branch and target branch
  * together - look at the chosen words; elsewhere the decoder's latent is held to the DPM-Encoder's own x_t of every level.
- * Arguments as cd_cycle_translate_ctrl's without the seven keep-mask arguments (n_ctrl = 0: no control), plus sel_src /
+ * With or without cross-attention control; it excludes a keep-mask and semantic guidance. sel_src /
  * sel_tgt [B_sel,L] fp32 device weights over the key positions of the source / target prompt, B a multiple of B_sel.
  * With Bd = n_dec*B, k = K-1-i, h the latent side and f = h / side, iteration i does:
- *   1. The one forward over [enc rows | dec rows] of cd_cycle_translate(_ctrl). In every text cross-attention (attn2) of a
+ *   1. The one forward over [enc rows | dec rows] of cd_cycle_translate. In every text cross-attention (attn2) of a
  *      transformer block whose token grid side equals `side`, for the encoder's CONDITIONAL rows (sample b, selector
  *      sel_src[b % B_sel]) and the decoder's CONDITIONAL rows (the last Bd rows; row r, selector sel_tgt[(r % B) % B_sel]):
  *          m[r, q] = (1/H) * sum_hd sum_j sel[j] * P_hd[q, j]   (hd ascending),   P = softmax(Q_own K_own^T * scale)
@@ -315,22 +300,26 @@ int cd_cycle_translate_ctrl(cd_handle h, int net, int sched_kind, const float* x
  *          x <- src * keep + (1 - keep) * x       (fp32, in cd_ddim_decode_masked's operation order)
  *      with src = the encoder's x of the level just arrived at (after step 3), of encoder row r % B. Unlike the keep-mask
  *      entry points the blend also follows the LAST step (under last_uses_x0 the kept cells of x_out are x0 bit for bit), and
- *      nothing is blended ahead of the first forward. Iterations i < n_start run exactly the launches of
- *      cd_cycle_translate(_ctrl).
+ *      nothing is blended ahead of the first forward. Iterations i < n_start run exactly the launches of the call without
+ *      the blend.
  * acc_out [(B + Bd),side,side] or NULL: the final sums, source rows first. keep_out [Bd,1,h,w] or NULL: the mask of the last
  * iteration, all ones if n_start == K. thr < 0 edits everywhere a map is above 0, thr >= 1 edits nowhere.
  * Refused (error text, nothing launched), for every n_ctrl: tables whose rows k < K disagree on the timestep, sched_kind !=
  * CD_SCHED_DDIM, networks without a text context, precision CD_PREC_F32 / CD_PREC_F32X3, ctx_len > 96, a pass without
  * conditional rows (guidance 0); B % B_sel != 0; side > 64, h % side != 0, a side that matches no block; pool even or outside
- * [1, 7]; n_start outside [0, K]; thr not finite; and what cd_cycle_translate_ctrl refuses of the control for n_ctrl != 0. */
-int cd_cycle_translate_blend(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
-                             const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
-                             float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
-                             const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                             uint64_t seed, int last_uses_x0, const float* mapper, const float* alpha, const float* weight,
-                             int B_ctrl, int n_ctrl, const float* sel_src, const float* sel_tgt, int B_sel, int side, int pool,
-                             float thr, int n_start, float* acc_out /* [B+n_dec*B,side,side] */,
-                             float* keep_out /* [n_dec*B,1,h,w] */, float* z_out, float* x_out);
+ * [1, 7]; n_start outside [0, K]; thr not finite; a keep-mask or concepts in the same call; and what cd_attn_ctrl refuses of
+ * the control for n_ctrl != 0. */
+typedef struct cd_local_blend {
+  const float* sel_src;  /* [B_sel,L] */
+  const float* sel_tgt;  /* [B_sel,L] */
+  int B_sel;
+  int side;
+  int pool;
+  float thr;
+  int n_start;
+  float* acc_out;        /* [B+n_dec*B,side,side] or NULL */
+  float* keep_out;       /* [n_dec*B,1,h,w] or NULL */
+} cd_local_blend;
 
 /* One edit concept of semantic guidance. Its quantile threshold q in [0, 1] over the N = C*H*W values of a latent arrives as
  * the rank and the weight of the two order statistics it lies between, computed by the caller in float64:
@@ -344,10 +333,10 @@ typedef struct cd_sega_concept {
   int32_t cool;
 } cd_sega_concept;
 
-/* cd_cycle_translate(_masked / _ctrl) with semantic guidance (SEGA; Brack et al., NeurIPS 2023; no counterpart in the
+/* Semantic guidance (SEGA; Brack et al., NeurIPS 2023; no counterpart in the
  * reference tree): E edit concepts, each a text context with its own signed scale, threshold, weight and window
- * of iterations, steer the decoder rows beside the one target prompt. Arguments up to n_ctrl as cd_cycle_translate_ctrl's
- * (mask = NULL: no keep-mask; n_ctrl = 0: no control), plus edit_ctx [E*Bd,L,Dc] fp32 device, concept-major (row e*Bd + r is
+ * of iterations, steer the decoder rows beside the one target prompt. With or without a keep-mask and cross-attention
+ * control. edit_ctx [E*Bd,L,Dc] fp32 device, concept-major (row e*Bd + r is
  * concept e for decoder row r, Bd = n_dec*B), concepts_host [E] and the momentum's scale s_m and decay beta.
  * The forward of every iteration runs over the batch rows
  *     [ enc (uncond | cond) | dec uncond Bd | dec concept 0 Bd | ... | dec concept E-1 Bd | dec cond Bd ]
@@ -375,18 +364,64 @@ typedef struct cd_sega_concept {
  * precision CD_PREC_F32 / CD_PREC_F32X3; a decoder pass without both its unconditional and its conditional rows
  * (dec_guidance 0 or 1, a missing context); lo outside [0, N-1]; frac outside [0, 1); warm / cool outside
  * 0 <= warm <= cool <= K; a non-finite scale, weight, momentum_scale or momentum_beta; momentum_beta outside [0, 1]; tables
- * whose rows k < K disagree on the timestep; and what cd_cycle_translate_masked / _ctrl refuse of a mask or a control. The
- * local blend of cd_cycle_translate_blend is not built together with concepts. */
-int cd_cycle_translate_sega(cd_handle h, int net, int sched_kind, const float* x0, const float* enc_ctx_c,
-                            const float* enc_ctx_uc, float enc_guidance, const float* dec_ctx_c, const float* dec_ctx_uc,
-                            float dec_guidance, const float* dec_guidance_per_sample, int ctx_len, int B, int n_dec, int K,
-                            const cd_step_coef* coef_enc_host, const cd_step_coef* coef_dec_host, const float* noise,
-                            uint64_t seed, int last_uses_x0, const float* mask, const float* mask_x0, int B_mask,
-                            int mask_source, const float* qsample_coef_host, const float* mask_noise, uint64_t mask_seed,
-                            const float* mapper, const float* alpha, const float* weight, int B_ctrl, int n_ctrl,
-                            const float* edit_ctx, const cd_sega_concept* concepts_host, int E, float momentum_scale,
-                            float momentum_beta, float* tau_out /* [K,n_dec*B,E] */, int32_t* kept_out /* [K,n_dec*B,E] */,
-                            float* mask_out /* [n_dec*B,E,C,H,W] */, float* z_out, float* x_out);
+ * whose rows k < K disagree on the timestep; and what cd_keep_mask / cd_attn_ctrl refuse of a mask or a control. The
+ * local blend (cd_local_blend) is not built together with concepts. */
+typedef struct cd_sega {
+  const float* edit_ctx;                 /* [E*n_dec*B,L,Dc], concept-major */
+  const cd_sega_concept* concepts_host;  /* [E] */
+  int E;
+  float momentum_scale;
+  float momentum_beta;
+  float* tau_out;                        /* [K,n_dec*B,E] or NULL */
+  int32_t* kept_out;                     /* [K,n_dec*B,E] or NULL */
+  float* mask_out;                       /* [n_dec*B,E,C,H,W] or NULL */
+} cd_sega;
+
+/* The coupled source -> target loop in ONE call: what Model.forward composes from the wrapper's encode() and forward()
+ * (model/text_unsupervised_translation.py:24-40: z = gan_wrapper.encode(image, encode_text); img = gan_wrapper(z, ...)) when
+ * both run on the same network over the whole chain (white_box_steps = custom_steps + 1): the DPM-Encoder step and the decode
+ * step of index k evaluate the network at the same timestep, and the decode step needs eps_k only after its forward, so each
+ * of the K iterations runs ONE forward over [encoder rows | decoder rows], then the encoder's step kernel (ddim.py:582-601,
+ * 545-580) and the decoder's (ddim.py:603-646), which reads the eps the encoder just wrote.
+ *   x0 [B,C,H,W]; enc_ctx_* [B,L,Dc] and enc_guidance as cd_dpm_encode's; the decoder runs n_dec decodes per encoder sample
+ *   (the wrapper's decoder_unconditional_guidance_scales of one kind, sd_wrapper:155-166): dec_ctx_* [n_dec*B,L,Dc], decoder
+ *   row j*B + b decodes the z of encoder sample b; dec_guidance (scalar) or dec_guidance_per_sample (device, n_dec*B floats,
+ *   each neither 0 nor 1) as cd_ddim_decode / cd_ddim_decode_v; coef_enc_host K+1 rows, coef_dec_host K rows (the same rows
+ *   0..K-1); noise [K,B,C,H,W] or NULL and last_uses_x0 as cd_dpm_encode's.
+ *   z_out [B,K+1,C,H,W] (what encode() returns), x_out [n_dec*B,C,H,W] (what the decode returns).
+ * The caller sets `size` to sizeof(cd_translate_args): a call built against another layout of the struct is refused before
+ * anything is read from it. mask / ctrl / blend / sega: NULL = the feature is off; each struct says what it adds and what is
+ * refused with it. The structs are read during the call only. */
+typedef struct cd_translate_args {
+  uint32_t size;
+  int net;
+  int sched_kind;
+  const float* x0;
+  const float* enc_ctx_c;
+  const float* enc_ctx_uc;
+  float enc_guidance;
+  const float* dec_ctx_c;
+  const float* dec_ctx_uc;
+  float dec_guidance;
+  const float* dec_guidance_per_sample;
+  int ctx_len;
+  int B;
+  int n_dec;
+  int K;
+  const cd_step_coef* coef_enc_host;
+  const cd_step_coef* coef_dec_host;
+  const float* noise;
+  uint64_t seed;
+  int last_uses_x0;
+  float* z_out;
+  float* x_out;
+  const cd_keep_mask* mask;
+  const cd_attn_ctrl* ctrl;
+  const cd_local_blend* blend;
+  const cd_sega* sega;
+} cd_translate_args;
+
+int cd_cycle_translate(cd_handle h, const cd_translate_args* a);
 
 /* ILVR (Choi et al., ICCV 2021: Iterative Latent Variable Refinement), the reference-image-conditioned sampler of the
  * paper's unpaired table; no counterpart in the reference tree. cd_ddim_decode's loop on an unconditional
@@ -595,7 +630,7 @@ int cd_op_gauss(cd_handle h, uint64_t seed, uint32_t stream, int64_t first, int6
  * map_out [B,1,H,W] (or NULL), mean_out [B] (or NULL), keep_out [B,1,H,W]; refused as cd_automask refuses n, ratio, thr, dilate */
 int cd_op_automask_reduce(cd_handle h, const float* eps_src, const float* eps_tgt, int n, int B, int C, int H, int W,
                           float ratio, float thr, int dilate, float* map_out, float* mean_out, float* keep_out);
-/* one launch of cd_cycle_translate_blend's mask kernel (k_local_blend_mask, step 4 of its definition) on caller-built sums:
+/* one launch of the local blend's (cd_local_blend) mask kernel (k_local_blend_mask, step 4 of its definition) on caller-built sums:
  * acc_src [B,side,side], acc_tgt [Bd,side,side] fp32 device, Bd a multiple of B -> keep_out [Bd,1,side*f,side*f] of 0 / 1.
  * Refused: side outside [1, 64], f < 1, pool even or outside [1, 7], Bd % B != 0. */
 int cd_op_local_blend_mask(cd_handle h, const float* acc_src, const float* acc_tgt, int B, int Bd, int side, int f, int pool,
@@ -608,12 +643,12 @@ int cd_op_sched_step_masked(cd_handle h, int mode, const cd_step_coef* coef_host
                             float guidance, const float* eps_in, const float* mask, const float* src, int B_mask,
                             int mask_source, float qa, float qb, const float* mask_noise, int blend, int B, int C, int HW,
                             void* xin16_out, int cfg_dup);
-/* one iteration of cd_cycle_translate_sega's guidance - its two launches, k_sega_threshold and k_sega_combine - on caller
+/* one iteration of semantic guidance (cd_sega) - its two launches, k_sega_threshold and k_sega_combine - on caller
  * tensors (bit-exact checks). eps_all [(2+E)*Bd,C,HW] fp32 device NCHW in batch-row order uncond | concept 0 .. E-1 | cond; the
  * op stages it to the form the network writes, fp32 NHWC with row stride ld >= C, and the kernels read that. guidance, or
  * guidance_per_sample [Bd] (device) when not NULL; concepts_host [E]; iteration: the i that warm / cool are held against;
  * nu [Bd,C,HW] in / out. Outputs: eps_out [Bd,C,HW]; tau_out [Bd,E], kept_out [Bd,E] (0 for an inactive concept); mask_out
- * [Bd,E,C,HW] or NULL. Refused as cd_cycle_translate_sega refuses the concept rows and the momentum, and ld < C. */
+ * [Bd,E,C,HW] or NULL. Refused as cd_sega refuses the concept rows and the momentum, and ld < C. */
 int cd_op_sega_guidance(cd_handle h, const float* eps_all, int Bd, int C, int HW, int E, int ld, float guidance,
                         const float* guidance_per_sample, const cd_sega_concept* concepts_host, int iteration,
                         float momentum_scale, float momentum_beta, float* nu, float* eps_out, float* tau_out,

@@ -1,4 +1,4 @@
-"""Torch restatement of the cross-attention control (include/cyclediff.h cd_cycle_translate_ctrl), in its
+"""Torch restatement of the cross-attention control (include/cyclediff.h cd_attn_ctrl), in its
 literal form: P = w * (alpha * (P_src . M) + (1 - alpha) * P_own), O = P . V_own - NOT the engine's V_a / V_b form, so the
 linear rewrite is under test too. Three layers:
   ctrl_attention_ref   one controlled cross-attention on explicit tensors (float64)
@@ -86,7 +86,7 @@ def controlled_mha(ctrl):
 
 
 def coupled_translate(sd, cfg, x0, c_src, c_tgt, uc, dec_g, S, skip, eta, noises, ctrl=None, n_ctrl=0):
-    """The coupled loop of cd_cycle_translate(_ctrl) on the oracle network, encoder guidance 1 and a guided decoder: one
+    """The coupled loop of cd_cycle_translate (cd_attn_ctrl) on the oracle network, encoder guidance 1 and a guided decoder: one
     forward per step over [encoder cond | decoder uncond | decoder cond], then the DPM-Encoder step and the decode step on the
     eps it just recorded - the arithmetic of oracle.samplers.latent_encode / latent_decode, line for line. noises: the list
     latent_encode takes. ctrl = (M, alpha, w), applied on iterations i < n_ctrl. Returns (z list, x)."""

@@ -2,6 +2,9 @@
 cycle_translate_ctrl / ddim_decode_masked on a stand-in library and writes down which C symbol each reaches and with which
 argument list. Integers, c_float and c_uint64 are recorded by value; a pointer as None, as the name of the input tensor it
 points at, as "out:<i>" for the i-th returned tensor, or - a host table - as the sha1 of the table's bytes.
+The fixture dates from the time when the coupled loop had one entry point per feature, each with a positional list. The one
+cd_cycle_translate(h, &args) of today is recorded in that form: the stand-in names the form from the option pointers that are
+set (FORMS) and flattens the struct back to that form's positional list through its field-order table.
 `python tests/_engine_translate_args.py --write` regenerates tests/golden/engine_translate_args.json."""
 import ctypes as C
 import hashlib
@@ -21,14 +24,41 @@ from cycle_diffusion_amd.engine import Engine  # noqa: E402
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "engine_translate_args.json")
 SYMBOLS = ("cd_cycle_translate", "cd_cycle_translate_masked", "cd_cycle_translate_ctrl", "cd_ddim_decode_masked")
+# the positional lists of the former entry points as (struct, field) rows; "z_out", "x_out" close each of them
+_BASE = [("", f) for f in ("net sched_kind x0 enc_ctx_c enc_ctx_uc enc_guidance dec_ctx_c dec_ctx_uc dec_guidance "
+                           "dec_guidance_per_sample ctx_len B n_dec K coef_enc_host coef_dec_host noise seed "
+                           "last_uses_x0").split()]
+_MASK = [("mask", f) for f in "mask x0 B_mask source qsample_coef_host noise seed".split()]
+_CTRL = [("ctrl", f) for f in "mapper alpha weight B_ctrl n_ctrl".split()]
+_OUT = [("", "z_out"), ("", "x_out")]
+FORMS = {"cd_cycle_translate": _BASE + _OUT, "cd_cycle_translate_masked": _BASE + _MASK + _OUT,
+         "cd_cycle_translate_ctrl": _BASE + _MASK + _CTRL + _OUT}
+
+
+def flatten(h, args):
+    """(former symbol, its positional arguments) of one cd_cycle_translate(h, byref(args)) call; an absent option struct
+    flattens to the zeros / NULLs the positional form passed in its place"""
+    a = args._obj
+    assert isinstance(a, _ffi.TranslateArgs) and a.size == C.sizeof(_ffi.TranslateArgs)
+    assert not a.blend and not a.sega, "the fixture has no such form"
+    sym = "cd_cycle_translate_ctrl" if a.ctrl else "cd_cycle_translate_masked" if a.mask else "cd_cycle_translate"
+    out = [h]
+    for opt, field in FORMS[sym]:
+        p = getattr(a, opt) if opt else None
+        st = a if not opt else p.contents if p else type(p)._type_()
+        v, ctype = getattr(st, field), dict(type(st)._fields_)[field]
+        out.append(v if ctype is C.c_int else None if ctype is C.c_void_p and v is None else ctype(v))
+    return sym, tuple(out)
+
+
 B, CH, HW, L, DC, K = 2, 4, 2, 3, 5, 3
 
 
 class RecordingLib:
     def __init__(self):
         self.calls = []
-        for sym in SYMBOLS:
-            setattr(self, sym, lambda *a, _sym=sym: self.calls.append((_sym, a)) or 0)
+        self.cd_ddim_decode_masked = lambda *a: self.calls.append(("cd_ddim_decode_masked", a)) or 0
+        self.cd_cycle_translate = lambda h, args: self.calls.append(flatten(h, args)) or 0
 
 
 class HostEngine(Engine):

@@ -1,4 +1,4 @@
-"""Torch restatement of the local blend on the coupled loop (include/cyclediff.h cd_cycle_translate_blend /
+"""Torch restatement of the local blend on the coupled loop (include/cyclediff.h cd_local_blend /
 cd_op_local_blend_mask). Three layers:
   mask_ref              step 4 of the definition on explicit sums: attn_control.blend_mask on either map, then the union;
                         ratios() gives every p / mx beside it (the distance of a fixture from the threshold)

@@ -1,4 +1,4 @@
-"""Torch restatement of semantic guidance (include/cyclediff.h cd_cycle_translate_sega / cd_op_sega_guidance).
+"""Torch restatement of semantic guidance (include/cyclediff.h cd_sega / cd_op_sega_guidance).
   guidance_step          one iteration's guidance on explicit tensors, in the operation order of the header, in the dtype of
                          its inputs (fp32: the bit-exact reference of cd_op_sega_guidance); order statistics from torch.sort
   coupled_translate_sega _attn_control_ref.coupled_translate extended by the concept rows, the guidance and the momentum

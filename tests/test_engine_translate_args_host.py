@@ -1,6 +1,7 @@
 """Engine.cycle_translate / cycle_translate_masked / cycle_translate_ctrl / ddim_decode_masked marshal their arguments into
 the C entry points as tests/golden/engine_translate_args.json records (no GPU, a stand-in library: tests/_engine_translate_args.py).
-The fixture was recorded while each of the three coupled forms carried its own copy of the marshalling."""
+The fixture was recorded while each of the three coupled forms had its own C entry point and its own copy of the marshalling;
+the stand-in flattens today's one argument struct back to those positional lists."""
 import json
 
 import pytest

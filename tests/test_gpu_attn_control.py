@@ -1,4 +1,4 @@
-"""Cross-attention control on the coupled translate loop (include/cyclediff.h cd_cycle_translate_ctrl /
+"""Cross-attention control on the coupled translate loop (include/cyclediff.h cd_attn_ctrl /
 cd_op_cross_attention_ctrl; csrc/attn.hip k_cross_attention_ctrl).
 
   1. the kernel against float64 torch on 16-bit-rounded inputs, at the bound of tests/test_gpu_ops.py::test_attention

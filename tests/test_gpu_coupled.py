@@ -99,6 +99,39 @@ def test_coupled_loop_refuses_what_it_cannot_do(engine):
     assert torch.isfinite(x).all()  # the engine is usable after the refusals
 
 
+def test_entry_point_refuses_a_missing_or_differently_sized_argument_struct(engine):
+    """cd_cycle_translate(h, NULL) and a struct whose `size` is not this library's sizeof(cd_translate_args) are refused on
+    the host before anything is read or launched; every other field of the struct is that of a call that would run"""
+    import ctypes as C
+    from cycle_diffusion_amd._ffi import ptr
+    fx = gu.load("latent_cycle_tiny")
+    net, _sd = _load(engine, tiny_sd_desc(), fx)
+    x0, c, uc, c2 = (t[:1].contiguous().cuda() for t in gu.latent_cycle_inputs())
+    B, K = 1, 2
+    sch = schedule.DDIMSchedule(schedule.latent_alphas_cumprod(), K, 0.1)
+    ce, cd = np.ascontiguousarray(sch.coef_encode(0)), np.ascontiguousarray(sch.coef_decode(0))
+    noise = torch.stack(gu.latent_noise(79, x0.shape, K), 0).cuda()
+    z = torch.full((B, K + 1, 4, 16, 16), -7.0, device="cuda")
+    x = torch.full((B, 4, 16, 16), -7.0, device="cuda")
+    lib, full = engine.lib, C.sizeof(_ffi.TranslateArgs)
+    a = _ffi.TranslateArgs(
+        size=full - 8, net=net, sched_kind=_ffi.CD_SCHED_DDIM, x0=ptr(x0), enc_ctx_c=ptr(c), enc_ctx_uc=ptr(uc), enc_guidance=1.0,
+        dec_ctx_c=ptr(c2), dec_ctx_uc=ptr(uc), dec_guidance=3.0, ctx_len=c.shape[1], B=B, n_dec=1, K=K,
+        coef_enc_host=ce.ctypes.data, coef_dec_host=cd.ctypes.data, noise=ptr(noise), seed=0, last_uses_x0=1, z_out=ptr(z),
+        x_out=ptr(x))
+    assert lib.cd_cycle_translate(engine.h, None) != 0
+    assert "NULL" in lib.cd_last_error().decode()
+    assert lib.cd_cycle_translate(engine.h, C.byref(a)) != 0
+    err = lib.cd_last_error().decode()
+    assert str(full - 8) in err and str(full) in err, err
+    engine.synchronize()
+    assert bool((x == -7.0).all()) and bool((z == -7.0).all())  # nothing ran
+    a.size = full
+    assert lib.cd_cycle_translate(engine.h, C.byref(a)) == 0, lib.cd_last_error().decode()  # the engine is usable after them
+    engine.synchronize()
+    assert torch.isfinite(x).all() and torch.isfinite(z).all() and not bool((x == -7.0).any())
+
+
 def _tiny_wrapper(**kw):
     from test_gpu_wrappers import _make
     return _make(True, **kw)

@@ -1,4 +1,4 @@
-"""Prompt-to-prompt's local blend on the coupled translate loop (include/cyclediff.h cd_cycle_translate_blend /
+"""Prompt-to-prompt's local blend on the coupled translate loop (include/cyclediff.h cd_local_blend /
 cd_op_local_blend_mask; csrc/automask.hip k_local_blend_mask).
 
   1. the mask kernel against the torch rule (attn_control.blend_mask on either map, then the union): exact equality
@@ -236,12 +236,15 @@ def test_blend_entry_point_refuses_what_it_cannot_do(engine, tiny):
     ce, cd = np.ascontiguousarray(t["ce"]), np.ascontiguousarray(t["cd"])
 
     def entry(net=t["net"], kind=DDIM, ctx=c, enc_g=1.0, dec_g=3.0, cd_=cd, B_sel=1, side=8, pool=3, thr=0.3, n_start=0):
-        return lib.cd_cycle_translate_blend(
-            h, net, kind, ptr(x0), ptr(ctx) if ctx is not None else None, ptr(uc) if ctx is not None else None,
-            C.c_float(enc_g), None if ctx is None else ptr(c2 if ctx is c else ctx),
-            ptr(uc) if ctx is not None else None, C.c_float(dec_g), None, 0 if ctx is None else ctx.shape[1], B, 1, K,
-            C.c_void_p(ce.ctypes.data), C.c_void_p(cd_.ctypes.data), ptr(nz), C.c_uint64(0), 1, None, None, None, 0, 0, ptr(sel),
-            ptr(sel), B_sel, side, pool, C.c_float(thr), n_start, None, None, ptr(z), ptr(x))
+        has = ctx is not None
+        blend = _ffi.LocalBlend(sel_src=ptr(sel), sel_tgt=ptr(sel), B_sel=B_sel, side=side, pool=pool, thr=thr, n_start=n_start)
+        a = _ffi.TranslateArgs(
+            size=C.sizeof(_ffi.TranslateArgs), net=net, sched_kind=kind, x0=ptr(x0), enc_ctx_c=ptr(ctx) if has else None,
+            enc_ctx_uc=ptr(uc) if has else None, enc_guidance=enc_g, dec_ctx_c=ptr(c2 if ctx is c else ctx) if has else None,
+            dec_ctx_uc=ptr(uc) if has else None, dec_guidance=dec_g, ctx_len=ctx.shape[1] if has else 0, B=B, n_dec=1, K=K,
+            coef_enc_host=ce.ctypes.data, coef_dec_host=cd_.ctypes.data, noise=ptr(nz), seed=0, last_uses_x0=1, z_out=ptr(z),
+            x_out=ptr(x), blend=C.pointer(blend))
+        return lib.cd_cycle_translate(h, C.byref(a))
 
     err = lambda: lib.cd_last_error().decode()
     d = tiny_sd_desc()

@@ -1,4 +1,4 @@
-"""The region-keeping decode (include/cyclediff.h cd_ddim_decode_masked / cd_cycle_translate_masked / cd_op_sched_step_masked;
+"""The region-keeping decode (include/cyclediff.h cd_ddim_decode_masked / cd_keep_mask / cd_op_sched_step_masked;
 wrapper forward(mask=) / translate(mask=)): DDIMSampler.sample_with_eps(mask=, x0=) (ddim.py:427-430) on the engine, and the
 "encoder" mode of the coupled loop. Bit-exact wherever two paths do the same fp32 arithmetic; the reference fixture
 (tests/golden/masked_latent.npz, scripts/gen_golden_masked.py) within the bounds tests/test_gpu_baselines.py holds the SDEdit
@@ -294,10 +294,13 @@ def test_masked_entry_points_refuse_what_they_cannot_do(engine):
                                          ptr(x0), b_mask, source, qp, ptr(mn), C.c_uint64(0), ptr(x))
 
     def coupled(source, qtab, nzp):
-        return lib.cd_cycle_translate_masked(h, net, DDIM, ptr(x0), ptr(c), ptr(uc), C.c_float(1.0), ptr(c2), ptr(uc),
-                                             C.c_float(3.0), None, 77, B, 1, K, C.c_void_p(ce.ctypes.data),
-                                             C.c_void_p(cd.ctypes.data), ptr(noise), C.c_uint64(0), 1, ptr(mask), ptr(x0), B, source,
-                                             qtab, nzp, C.c_uint64(0), ptr(zo), ptr(x))
+        keep = _ffi.KeepMask(mask=ptr(mask), x0=ptr(x0), B_mask=B, source=source, qsample_coef_host=qtab, noise=nzp, seed=0)
+        a = _ffi.TranslateArgs(
+            size=C.sizeof(_ffi.TranslateArgs), net=net, sched_kind=DDIM, x0=ptr(x0), enc_ctx_c=ptr(c), enc_ctx_uc=ptr(uc),
+            enc_guidance=1.0, dec_ctx_c=ptr(c2), dec_ctx_uc=ptr(uc), dec_guidance=3.0, ctx_len=77, B=B, n_dec=1, K=K,
+            coef_enc_host=ce.ctypes.data, coef_dec_host=cd.ctypes.data, noise=ptr(noise), seed=0, last_uses_x0=1, z_out=ptr(zo),
+            x_out=ptr(x), mask=C.pointer(keep))
+        return lib.cd_cycle_translate(h, C.byref(a))
 
     err = lambda: lib.cd_last_error().decode()
     assert decode(_ffi.CD_SCHED_DDPM, net, z, B) != 0 and "CD_SCHED_DDIM" in err()

@@ -333,8 +333,9 @@ def test_a_loop_that_leaves_its_stream_band_is_refused(engine, toy):
     refused_for_the_band(mdec(p, None), "mask_noise")
     past_the_band(mdec(p, p), "pixel")
     # cd_cycle_translate
-    cyc = lambda nz, ctx: lib.cd_cycle_translate(h, toy, DDIM, p, ctx, None, f1, None, None, f1, None, 1, B, 1, K, cp, cp, nz,
-                                                 u0, 0, p, p)
+    cyc = lambda nz, ctx: lib.cd_cycle_translate(h, C.byref(_ffi.TranslateArgs(
+        size=C.sizeof(_ffi.TranslateArgs), net=toy, sched_kind=DDIM, x0=p, enc_ctx_c=ctx, enc_guidance=1.0, dec_guidance=1.0,
+        ctx_len=1, B=B, n_dec=1, K=K, coef_enc_host=cp, coef_dec_host=cp, noise=nz, seed=0, last_uses_x0=0, z_out=p, x_out=p)))
     refused_for_the_band(cyc(None, None), "noise")
     past_the_band(cyc(p, p), "contexts for both passes")
     # cd_pix_refine: nothing later refuses a call on the toy network, so the pair runs on a network that does not exist

@@ -1,4 +1,4 @@
-"""Semantic guidance on the coupled translate loop (include/cyclediff.h cd_cycle_translate_sega / cd_op_sega_guidance;
+"""Semantic guidance on the coupled translate loop (include/cyclediff.h cd_sega / cd_op_sega_guidance;
 csrc/sega.hip k_sega_threshold, k_sega_combine).
 
   1. the two kernels against the fp32 torch restatement (tests/_sega_ref.py guidance_step), bit for bit
@@ -310,12 +310,14 @@ def test_entry_point_refuses_what_it_cannot_do(su):
         tab = sr.e2e_table("two").copy() if tab is None else tab
         for k, v in row.items():
             tab[k][1] = v
-        return lib.cd_cycle_translate_sega(
-            eng.h, net, kind, ptr(x0), ptr(kw["enc_ctx_c"]), ptr(kw["enc_ctx_uc"]), C.c_float(1.0), ptr(kw["dec_ctx_c"]),
-            ptr(kw["dec_ctx_uc"]), C.c_float(dec_g), None, 77, B, 1, K, C.c_void_p(su.ce.ctypes.data), C.c_void_p(cd.ctypes.data),
-            ptr(kw["noise"]), C.c_uint64(0), 1, None, None, 0, 0, None, None, C.c_uint64(0), None, None, None, 0, 0,
-            ptr(ectx), C.c_void_p(tab.ctypes.data), len(tab) if E is None else E, C.c_float(s_m), C.c_float(beta), None, None,
-            None, ptr(z), ptr(x))
+        sega = _ffi.Sega(edit_ctx=ptr(ectx), concepts_host=tab.ctypes.data, E=len(tab) if E is None else E, momentum_scale=s_m,
+                         momentum_beta=beta)
+        a = _ffi.TranslateArgs(
+            size=C.sizeof(_ffi.TranslateArgs), net=net, sched_kind=kind, x0=ptr(x0), enc_ctx_c=ptr(kw["enc_ctx_c"]),
+            enc_ctx_uc=ptr(kw["enc_ctx_uc"]), enc_guidance=1.0, dec_ctx_c=ptr(kw["dec_ctx_c"]), dec_ctx_uc=ptr(kw["dec_ctx_uc"]),
+            dec_guidance=dec_g, ctx_len=77, B=B, n_dec=1, K=K, coef_enc_host=su.ce.ctypes.data, coef_dec_host=cd.ctypes.data,
+            noise=ptr(kw["noise"]), seed=0, last_uses_x0=1, z_out=ptr(z), x_out=ptr(x), sega=C.pointer(sega))
+        return lib.cd_cycle_translate(eng.h, C.byref(a))
 
     cd_bad = su.cd.copy()
     cd_bad["t"][1] += 1

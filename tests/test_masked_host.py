@@ -15,7 +15,7 @@ from cycle_diffusion_amd import _ffi, schedule
 from oracle import nets
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ["cd_ddim_decode_masked", "cd_cycle_translate_masked", "cd_op_sched_step_masked"]
+NEW_SYMBOLS = ["cd_ddim_decode_masked", "cd_op_sched_step_masked"]
 
 
 def _sched(p):
@@ -102,6 +102,13 @@ def test_new_symbols_in_header_ffi_and_library():
         assert s in _ffi.SIGNATURES and hasattr(lib, s), s
         n_args = len(re.search(r"\b%s\s*\((.*?)\)" % s, txt, flags=re.S).group(1).split(","))
         assert n_args == len(_ffi.SIGNATURES[s]), (s, n_args)
+    # the coupled loop takes its keep-mask as an option struct of cd_cycle_translate: in the header and in _ffi with equal
+    # fields (tests/test_abi.py holds their types and offsets to the header's)
+    body = re.search(r"typedef\s+struct\s+cd_keep_mask\s*\{(.*?)\}\s*cd_keep_mask\s*;", txt, flags=re.S).group(1)
+    names = [re.search(r"(\w+)$", d.strip()).group(1) for d in body.split(";") if d.strip()]
+    assert names == [f for f, _ in _ffi.KeepMask._fields_]
+    assert names == ["mask", "x0", "B_mask", "source", "qsample_coef_host", "noise", "seed"]
+    assert dict(_ffi.TranslateArgs._fields_)["mask"]._type_ is _ffi.KeepMask
     assert _ffi.MASK_SOURCES == {"q_sample": 0, "encoder": 1}
     assert "CD_MASK_QSAMPLE = 0" in txt and "CD_MASK_ENCODER = 1" in txt
 
