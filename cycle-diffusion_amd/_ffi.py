@@ -75,7 +75,8 @@ class TranslateArgs(C.Structure):
                 ("K", C.c_int), ("coef_enc_host", C.c_void_p), ("coef_dec_host", C.c_void_p), ("noise", C.c_void_p),
                 ("seed", C.c_uint64), ("last_uses_x0", C.c_int), ("z_out", C.c_void_p), ("x_out", C.c_void_p),
                 ("mask", C.POINTER(KeepMask)), ("ctrl", C.POINTER(AttnCtrl)), ("blend", C.POINTER(LocalBlend)),
-                ("sega", C.POINTER(Sega))]
+                ("sega", C.POINTER(Sega)), ("canvas_h", C.c_int), ("canvas_w", C.c_int), ("n_win", C.c_int),
+                ("win_host", C.c_void_p)]
 
 
 SEGA_CONCEPT_DTYPE = np.dtype([("scale", "<f4"), ("weight", "<f4"), ("lo", "<i4"), ("frac", "<f4"), ("warm", "<i4"),
@@ -112,6 +113,8 @@ SIGNATURES = {
     "cd_lpips_tap": [_VP, _I, _VP, _I, _I, _I, _I, _VP],
     "cd_vae_encode": [_VP, _I, _VP, _VP, _U64, _I, _I, _I, _F, _VP],
     "cd_vae_decode": [_VP, _I, _VP, _I, _I, _F, _F, _F, _VP],
+    "cd_vae_encode_hw": [_VP, _I, _VP, _VP, _U64, _I, _I, _I, _I, _F, _VP],
+    "cd_vae_decode_hw": [_VP, _I, _VP, _I, _I, _I, _F, _F, _F, _VP],
     "cd_dpm_encode": [_VP, _I, _I, _VP, _VP, _VP, _I, _F, _I, _I, _VP, _VP, _U64, _I, _VP],
     "cd_ddim_decode": [_VP, _I, _I, _VP, _I, _I, _VP, _VP, _I, _F, _I, _I, _VP, _VP, _U64, _VP],
     "cd_ddim_decode_v": [_VP, _I, _I, _VP, _I, _I, _VP, _VP, _I, _VP, _I, _I, _VP, _VP, _U64, _VP],
@@ -156,6 +159,8 @@ SIGNATURES = {
     "cd_op_local_blend_mask": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _F, _VP],
     "cd_op_sched_step_masked": [_VP, _I, _VP, _VP, _VP, _I, _F, _VP, _VP, _VP, _I, _I, _F, _F, _VP, _I, _I, _I, _I, _VP, _I],
     "cd_op_sega_guidance": [_VP, _VP, _I, _I, _I, _I, _I, _F, _VP, _VP, _I, _F, _F, _VP, _VP, _VP, _VP, _VP],
+    "cd_op_window_gather": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP],
+    "cd_op_window_fuse": [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, _I, _VP],
     "cd_op_layout": [_VP, _I, _VP, _VP, _I, _I, _I, _I, _I, _F, _F, _I],
     "cd_op_resample16": [_VP, _I, _VP, _VP, _I, _I, _I, _I],
     "cd_op_copy_rows16": [_VP, _VP, _I, _VP, _I, _I64, _I],

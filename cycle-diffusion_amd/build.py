@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libcyclediff.so")
-SOURCES = ["sched.hip", "sega.hip", "ilvr.hip", "automask.hip", "elementwise.hip", "norm.hip", "conv_gemm.hip", "lin_stream.hip", "attn.hip", "f32_path.hip", "st_f32.hip", "diag.hip", "engine.hip",
+SOURCES = ["sched.hip", "sega.hip", "ilvr.hip", "automask.hip", "windows.hip", "elementwise.hip", "norm.hip", "conv_gemm.hip", "lin_stream.hip", "attn.hip", "f32_path.hip", "st_f32.hip", "diag.hip", "engine.hip",
            "unet_openai.hip", "nets_ho_vae.hip", "clip_text.hip", "inception.hip", "lpips.hip",
            "capi.hip", "capi_ops.hip"]
 HEADERS = ["common.h", "kernels.h", "sched_elem.h", "gauss.h", "engine.h", "capi_internal.h", os.path.join("..", "..", "include", "cyclediff.h")]
@@ -56,7 +56,7 @@ def build(force=False, verbose=False, variant=None):
         obj = os.path.join(objdir, s.replace(".hip", ".o"))
         objs.append(obj)
         if force or _stale(obj, [src] + hdrs):
-            extra = ["-ffp-contract=off"] if s in ("sched.hip", "sega.hip", "ilvr.hip", "automask.hip") else []  # scheduler math: reference op order, no FMA
+            extra = ["-ffp-contract=off"] if s in ("sched.hip", "sega.hip", "ilvr.hip", "automask.hip", "windows.hip") else []  # scheduler math: reference op order, no FMA
             if s == "conv_gemm.hip":  # the register epilogue of the 256x320 tile is 10 fully unrolled 32x32 blocks
                 extra = ["-mllvm", "-pragma-unroll-threshold=1048576"]
             jobs.append([hipcc] + FLAGS + defines + extra + ["-c", src, "-o", obj])

@@ -246,6 +246,29 @@ StepCoef* upload_coef(cd_engine* h, const cd_step_coef* host, int n) {
   return (StepCoef*)upload_table(h, host, (size_t)n * sizeof(StepCoef));
 }
 
+// the geometry of a set of fused windows, checked on the host before any launch: capi_ops.hip calls it too
+void check_window_grid(const int32_t* win_host, int n_win, int Hc, int Wc, int S) {
+  const char* fw = "fused windows";
+  CD_CHECK(n_win >= 1 && n_win <= kMaxWindows, "%s: n_win = %d outside [0, %d]", fw, n_win, kMaxWindows);
+  CD_CHECK(win_host, "%s: win_host is NULL", fw);
+  CD_CHECK(S > 0 && Hc >= S && Wc >= S, "%s: a canvas of %d x %d is smaller than the network's %d x %d input", fw, Hc, Wc, S, S);
+  CD_CHECK((int64_t)Hc * Wc <= (int64_t)kMaxWindows * S * S, "%s: no window covers every cell of a %d x %d canvas: %d windows "
+           "hold fewer cells", fw, Hc, Wc, kMaxWindows);
+  std::vector<uint8_t> covered((size_t)Hc * Wc, 0);
+  for (int w = 0; w < n_win; ++w) {
+    const int y = win_host[2 * w], x = win_host[2 * w + 1];
+    CD_CHECK(y >= 0 && x >= 0 && y <= Hc - S && x <= Wc - S, "%s: window %d at (%d, %d) lies outside the %d x %d canvas", fw, w,
+             y, x, Hc, Wc);
+    for (int v = 0; v < w; ++v)
+      CD_CHECK(win_host[2 * v] != y || win_host[2 * v + 1] != x, "%s: windows %d and %d are equal, both at (%d, %d)", fw, v, w,
+               y, x);
+    for (int yy = y; yy < y + S; ++yy)
+      for (int xx = x; xx < x + S; ++xx) covered[(size_t)yy * Wc + xx] = 1;
+  }
+  for (int i = 0; i < Hc * Wc; ++i)
+    CD_CHECK(covered[i], "%s: no window covers canvas cell (%d, %d)", fw, i / Wc, i % Wc);
+}
+
 namespace {
 
 // The generator's streams are banded by loop, 4096 streams to a band (tests/_philox_ref.py STREAMS):
@@ -452,45 +475,57 @@ int cd_clip_image_features(cd_handle h, int net, const float* img, int B, float*
   CD_API_END
 }
 
-int cd_vae_encode(cd_handle h, int net, const float* img, const float* noise, uint64_t seed, int B, int R,
-                  int sample, float scale, float* z0) {
+int cd_vae_encode_hw(cd_handle h, int net, const float* img, const float* noise, uint64_t seed, int B, int H, int W,
+                     int sample, float scale, float* z0) {
   CD_API_BEGIN
   enter_engine(h);
   VAE* v = get_vae(h, net);
-  CD_CHECK(img && z0 && B > 0 && R % v->factor == 0, "bad argument");
+  CD_CHECK(img && z0 && B > 0 && H > 0 && W > 0, "bad argument");
+  CD_CHECK(H % v->factor == 0 && W % v->factor == 0, "first stage: an image of %d x %d is no multiple of the factor %d", H, W,
+           v->factor);
   ArenaScope arena_scope(h->arena);
   Ctx c = h->ctx();
-  const int cin = v->desc.in_channels, cp = round_up(cin, 32), hl = R / v->factor;
+  const int cin = v->desc.in_channels, cp = round_up(cin, 32), hl = H / v->factor, wl = W / v->factor;
   // 16-bit rows, or - first stage in fp32 / in the split mode - fp32 rows / fp16 pairs (the same bytes)
-  bf16_t* xin = (bf16_t*)h->arena.alloc((size_t)B * R * R * cp * (v->f32 ? 4 : 2));
-  put_net_input(h, v, img, xin, B, cin, R * R, cp, 1.f, false);
+  bf16_t* xin = (bf16_t*)h->arena.alloc((size_t)B * H * W * cp * (v->f32 ? 4 : 2));
+  put_net_input(h, v, img, xin, B, cin, H * W, cp, 1.f, false);
   const int mch = v->moments_channels;
-  float* mom = (float*)h->arena.alloc((size_t)B * hl * hl * mch * 4);
-  v->encode_moments(c, xin, B, R, mom);
+  float* mom = (float*)h->arena.alloc((size_t)B * hl * wl * mch * 4);
+  v->encode_moments(c, xin, B, H, W, mom);
   // VQ first stage: no distribution, the encoding is the quant_conv output itself (ddpm.py get_first_stage_encoding)
   const bool vq = v->codebook != nullptr;
-  launch_posterior_sample(h->st, mom, mch, noise, seed, z0, B, v->desc.embed_dim, hl * hl, scale, (sample && !vq) ? 0 : 1);
+  launch_posterior_sample(h->st, mom, mch, noise, seed, z0, B, v->desc.embed_dim, hl * wl, scale, (sample && !vq) ? 0 : 1);
+  CD_API_END
+}
+
+int cd_vae_encode(cd_handle h, int net, const float* img, const float* noise, uint64_t seed, int B, int R,
+                  int sample, float scale, float* z0) {
+  return cd_vae_encode_hw(h, net, img, noise, seed, B, R, R, sample, scale, z0);
+}
+
+int cd_vae_decode_hw(cd_handle h, int net, const float* z0, int B, int hl, int wl, float scale, float out_mul,
+                     float out_add, float* img) {
+  CD_API_BEGIN
+  enter_engine(h);
+  VAE* v = get_vae(h, net);
+  CD_CHECK(z0 && img && B > 0 && hl > 0 && wl > 0, "bad argument");
+  ArenaScope arena_scope(h->arena);
+  Ctx c = h->ctx();
+  const int zc = v->desc.embed_dim, cp = round_up(zc, 32), H = hl * v->factor, W = wl * v->factor, co = v->desc.out_channels;
+  bf16_t* zin = (bf16_t*)h->arena.alloc((size_t)B * hl * wl * cp * (v->f32 ? 4 : 2));
+  if (v->codebook)  // VQModelInterface.decode: quantise to the codebook first (autoencoder.py:274-280)
+    launch_vq_quantize(h->st, z0, 1.0f / scale, v->codebook, v->n_embed, zc, B, hl * wl, zin, cp);
+  else
+    put_net_input(h, v, z0, zin, B, zc, hl * wl, cp, 1.0f / scale, false);  // z = 1/scale * z (ddpm.py:705)
+  float* o = (float*)h->arena.alloc((size_t)B * H * W * co * 4);
+  v->decode(c, zin, B, hl, wl, o);
+  launch_nhwc_to_nchw(h->st, o, 1, co, img, B, co, H * W, out_mul, out_add);
   CD_API_END
 }
 
 int cd_vae_decode(cd_handle h, int net, const float* z0, int B, int hlat, float scale, float out_mul,
                   float out_add, float* img) {
-  CD_API_BEGIN
-  enter_engine(h);
-  VAE* v = get_vae(h, net);
-  CD_CHECK(z0 && img && B > 0 && hlat > 0, "bad argument");
-  ArenaScope arena_scope(h->arena);
-  Ctx c = h->ctx();
-  const int zc = v->desc.embed_dim, cp = round_up(zc, 32), R = hlat * v->factor, co = v->desc.out_channels;
-  bf16_t* zin = (bf16_t*)h->arena.alloc((size_t)B * hlat * hlat * cp * (v->f32 ? 4 : 2));
-  if (v->codebook)  // VQModelInterface.decode: quantise to the codebook first (autoencoder.py:274-280)
-    launch_vq_quantize(h->st, z0, 1.0f / scale, v->codebook, v->n_embed, zc, B, hlat * hlat, zin, cp);
-  else
-    put_net_input(h, v, z0, zin, B, zc, hlat * hlat, cp, 1.0f / scale, false);  // z = 1/scale * z (ddpm.py:705)
-  float* o = (float*)h->arena.alloc((size_t)B * R * R * co * 4);
-  v->decode(c, zin, B, hlat, o);
-  launch_nhwc_to_nchw(h->st, o, 1, co, img, B, co, R * R, out_mul, out_add);
-  CD_API_END
+  return cd_vae_decode_hw(h, net, z0, B, hlat, hlat, scale, out_mul, out_add, img);
 }
 
 int cd_dpm_encode(cd_handle h, int net, int sched_kind, const float* x0, const float* ctx_c,
@@ -651,8 +686,23 @@ int cd_ddim_invert(cd_handle h, int net, int sched_kind, const float* x0, const 
 //   [ encoder rows (B, or uncond B | cond B under encoder guidance) | decoder rows (Bd = n_dec * B, or uncond Bd | cond Bd) ]
 // followed by the encoder's step kernel (x_{k-1}, eps_k -> z) and then the decoder's (consumes eps_k). 99 forwards of
 // B + 2 Bd rows instead of 99 of B and 99 of 2 Bd. Per-sample arithmetic is that of cd_dpm_encode followed by cd_ddim_decode(_v).
-// The options (include/cyclediff.h: keep-mask, cross-attention control DESIGN.md 14, local blend 18, semantic guidance 20)
-// are branches of this one body; which of them go together is decided here.
+// The options (include/cyclediff.h: keep-mask, cross-attention control DESIGN.md 14, local blend 18, semantic guidance 20,
+// fused windows 21) are branches of this one body; which of them go together is decided here.
+// fused windows of cd_cycle_translate (include/cyclediff.h cd_translate_args)
+static void check_windows(const cd_translate_args& a, const UNet* u) {
+  const char* fw = "fused windows";
+  CD_CHECK(a.n_win >= 0 && a.n_win <= kMaxWindows, "%s: n_win = %d outside [0, %d]", fw, a.n_win, kMaxWindows);
+  if (a.n_win == 0) {
+    CD_CHECK(a.canvas_h == 0 && a.canvas_w == 0 && !a.win_host, "%s: n_win = 0 (off) takes canvas_h = canvas_w = 0 and "
+             "win_host = NULL", fw);
+    return;
+  }
+  check_window_grid(a.win_host, a.n_win, a.canvas_h, a.canvas_w, u->image_size);
+  CD_CHECK(!u->f32, "%s are not built for precision CD_PREC_F32 / CD_PREC_F32X3 networks: use the 16-bit precision", fw);
+  CD_CHECK(!a.mask && !a.ctrl && !a.blend && !a.sega, "%s are not built together with a keep-mask, cross-attention control, the "
+           "local blend or concepts yet: call without them", fw);
+}
+
 static void cycle_translate_impl(cd_handle h, const cd_translate_args& a) {
   const cd_keep_mask* mk = a.mask;
   const cd_attn_ctrl* ck = a.ctrl;
@@ -666,6 +716,8 @@ static void cycle_translate_impl(cd_handle h, const cd_translate_args& a) {
   if (mk && mk->source == CD_MASK_QSAMPLE) check_stream_band(mk->noise, a.K, "keep-mask: mask_noise");
   ArenaScope arena_scope(h->arena);
   UNet* u = get_unet(h, a.net);
+  const int nw = a.n_win;  // fused windows: 0 = off, every launch below is the one of the call without them
+  check_windows(a, u);
   const int Bd = a.B * a.n_dec;
   if (mk) check_mask_args(*mk, u, a.sched_kind, a.B, /*coupled=*/true);
   const bool ctrl_on = ck && ck->n_ctrl != 0;
@@ -724,7 +776,10 @@ static void cycle_translate_impl(cd_handle h, const cd_translate_args& a) {
     CD_CHECK(ck->B_ctrl > 0 && a.B % ck->B_ctrl == 0, "cross-attention control shape mismatch: %d control rows for a batch "
              "of %d", ck->B_ctrl, a.B);
   }
-  const int C = u->desc.in_channels, HW = u->image_size * u->image_size, cpad = u->in_cpad, out_ld = u->out_channels;
+  // HW: the cells of the running latent - the network's own S x S, or the canvas; HWn: the tokens of one network row; W: the
+  // network rows per latent row
+  const int C = u->desc.in_channels, HWn = u->image_size * u->image_size, HW = nw ? a.canvas_h * a.canvas_w : HWn;
+  const int cpad = u->in_cpad, out_ld = u->out_channels, W = nw ? nw : 1;
   const bool f32 = u->f32;
   Guidance ge = resolve_guidance(a.enc_ctx_c, a.enc_ctx_uc, a.enc_guidance);
   Guidance gd = resolve_guidance(a.dec_ctx_c, a.dec_ctx_uc, a.dec_guidance_per_sample ? 2.0f : a.dec_guidance);
@@ -749,15 +804,18 @@ static void cycle_translate_impl(cd_handle h, const cd_translate_args& a) {
     const int Dc = u->desc.context_dim;
     CD_CHECK(Dc > 0 && a.ctx_len > 0, "network has no cross-attention but a context was given");
     // one context tensor in batch-row order: [enc (uncond | cond) | dec (uncond | cond)]
-    void* cx = h->arena.alloc((size_t)Bn * a.ctx_len * Dc * (f32 ? 4 : 2));
-    auto put = [&](const float* src, int rows, size_t row0) { put_ctx(h, u, src, cx, row0, rows, a.ctx_len, Dc); };
+    // (with windows every part is window-major: the part's contexts once per window, in row order)
+    void* cx = h->arena.alloc((size_t)Bn * W * a.ctx_len * Dc * (f32 ? 4 : 2));
+    auto put = [&](const float* src, int rows, size_t row0) {
+      for (int w = 0; w < W; ++w) put_ctx(h, u, src, cx, row0 * W + (size_t)w * rows, rows, a.ctx_len, Dc);
+    };
     if (ge.cfg) { put(a.enc_ctx_uc, a.B, 0); put(a.enc_ctx_c, a.B, a.B); } else put(ge.ctx_single, a.B, 0);
     if (gd.cfg) {
       put(a.dec_ctx_uc, Bd, Ben);
       if (sk) put(sk->edit_ctx, E * Bd, Ben + Bd);  // concept-major, as the rows lie
       put(a.dec_ctx_c, Bd, Ben + (size_t)(1 + E) * Bd);
     } else put(gd.ctx_single, Bd, Ben);
-    u->set_context(c, (const bf16_t*)cx, Bn, a.ctx_len);
+    u->set_context(c, (const bf16_t*)cx, Bn * W, a.ctx_len);
   } else {
     CD_CHECK(u->desc.context_dim <= 0 || !u->desc.use_spatial_transformer, "network expects a cross-attention context");
   }
@@ -789,17 +847,35 @@ static void cycle_translate_impl(cd_handle h, const cd_translate_args& a) {
   }
   float* xt_e = (float*)h->arena.alloc((size_t)a.B * chw * 4);
   float* xt_d = (float*)h->arena.alloc((size_t)Bd * chw * 4);
-  char* xin = (char*)h->arena.alloc((size_t)Bn * HW * cpad * esz);
-  HIP_CHECK(hipMemsetAsync(xin, 0, (size_t)Bn * HW * cpad * esz, h->st));
-  float* eh = (float*)h->arena.alloc((size_t)Bn * HW * out_ld * 4);
-  const size_t row_in = (size_t)HW * cpad * esz;  // bytes of one sample of the network input
+  char* xin = (char*)h->arena.alloc((size_t)Bn * W * HWn * cpad * esz);
+  HIP_CHECK(hipMemsetAsync(xin, 0, (size_t)Bn * W * HWn * cpad * esz, h->st));
+  float* eh = (float*)h->arena.alloc((size_t)Bn * W * HWn * out_ld * 4);
+  const size_t row_in = (size_t)HWn * cpad * esz;  // bytes of one sample of the network input
   bf16_t* xin_e = f32 ? nullptr : (bf16_t*)xin;
-  bf16_t* xin_d = f32 ? nullptr : (bf16_t*)(xin + (size_t)Ben * row_in);
+  bf16_t* xin_d = f32 ? nullptr : (bf16_t*)(xin + (size_t)Ben * W * row_in);
   StepArgs enc, dec;  // the step launches of the encoder's and of the decoder's rows
   EpsHat &eh_e = enc.eh, &eh_d = dec.eh;
-  eh_e.p = eh; eh_e.sb = (int64_t)HW * out_ld; eh_e.sc = 1; eh_e.sp = out_ld; eh_e.cfg = ge.cfg ? 1 : 0; eh_e.g = a.enc_guidance;
-  eh_d = eh_e; eh_d.p = eh + (int64_t)Ben * HW * out_ld; eh_d.cfg = gd.cfg ? 1 : 0; eh_d.g = a.dec_guidance;
+  eh_e.p = eh; eh_e.sb = (int64_t)HWn * out_ld; eh_e.sc = 1; eh_e.sp = out_ld; eh_e.cfg = ge.cfg ? 1 : 0; eh_e.g = a.enc_guidance;
+  eh_d = eh_e; eh_d.p = eh + (int64_t)Ben * HWn * out_ld; eh_d.cfg = gd.cfg ? 1 : 0; eh_d.g = a.dec_guidance;
   eh_d.gvec = a.dec_guidance_per_sample;
+  // fused windows: the step kernels read the fused eps of the canvas, fp32 NCHW with the [uncond | cond] halves intact (the
+  // combine stays theirs), and write no network input - the gathers ahead of every forward do
+  WindowGather wg_e, wg_d;
+  WindowFuse wf_e, wf_d;
+  if (nw) {
+    const int* win = (const int*)upload_table(h, a.win_host, (size_t)nw * 2 * sizeof(int32_t));
+    float* ehc_e = (float*)h->arena.alloc((size_t)Ben * C * HW * 4);
+    float* ehc_d = (float*)h->arena.alloc((size_t)Bdn * C * HW * 4);
+    wg_e.x = xt_e; wg_e.y = xin_e; wg_e.win = win; wg_e.Bp = a.B; wg_e.C = C; wg_e.Hc = a.canvas_h; wg_e.Wc = a.canvas_w;
+    wg_e.S = u->image_size; wg_e.n_win = nw; wg_e.cpad = cpad; wg_e.dup = ge.cfg ? 1 : 0;
+    wg_d = wg_e; wg_d.x = xt_d; wg_d.y = xin_d; wg_d.Bp = Bd; wg_d.dup = gd.cfg ? 1 : 0;
+    wf_e.e = eh; wf_e.out = ehc_e; wf_e.win = win; wf_e.Bp = a.B; wf_e.C = C; wf_e.Hc = a.canvas_h; wf_e.Wc = a.canvas_w;
+    wf_e.S = u->image_size; wf_e.n_win = nw; wf_e.ld = out_ld; wf_e.parts = ge.cfg ? 2 : 1;
+    wf_d = wf_e; wf_d.e = eh + (int64_t)Ben * W * HWn * out_ld; wf_d.out = ehc_d; wf_d.Bp = Bd; wf_d.parts = gd.cfg ? 2 : 1;
+    eh_e.p = ehc_e; eh_e.sb = (int64_t)C * HW; eh_e.sc = HW; eh_e.sp = 1;
+    eh_d.p = ehc_d; eh_d.sb = (int64_t)C * HW; eh_d.sc = HW; eh_d.sp = 1;
+    xin_e = xin_d = nullptr;  // what the step kernels see
+  }
   StepCoef* tab_e = upload_coef(h, a.coef_enc_host, a.K + 1);
   StepCoef* tab_d = upload_coef(h, a.coef_dec_host, a.K);
   const int64_t zbs = (int64_t)(a.K + 1) * chw;
@@ -846,24 +922,26 @@ static void cycle_translate_impl(cd_handle h, const cd_translate_args& a) {
     return b;
   };
   if (mk) launch_mask_blend_init(h->st, dec, blend_of(a.K - 1, 0));
-  else if (!f32) launch_nchw_to_nhwc(h->st, xt_d, xin_d, Bd, C, HW, cpad, 1.f, 0.f, gd.cfg ? 1 + E : 0);
+  else if (!f32 && !nw) launch_nchw_to_nhwc(h->st, xt_d, xin_d, Bd, C, HW, cpad, 1.f, 0.f, gd.cfg ? 1 + E : 0);
   // rows that repeat the rows just ahead of them (the decoder's cond half repeats its uncond half): the network computes
   // everything ahead of the first cross-attention once for them - only when the encoder half has no such pair of its own
   // (not under semantic guidance: the shared prefix covers one pair of halves, not the concept rows between them)
-  const int dup_tail = (gd.cfg && !ge.cfg && !sk) ? Bd : 0;
+  const int dup_tail = (gd.cfg && !ge.cfg && !sk) ? Bd * W : 0;
   for (int i = 0; i < a.K; ++i) {
     const int k = a.K - 1 - i;
     if (f32) {
       put_net_input(h, u, xt_e, xin, a.B, C, HW, cpad, 1.f, ge.cfg);
       put_net_input(h, u, xt_d, xin + (size_t)Ben * row_in, Bd, C, HW, cpad, 1.f, gd.cfg);
     }
+    if (nw) { launch_window_gather(h->st, wg_e); launch_window_gather(h->st, wg_d); }
     UNetIO io;
-    io.xin = (const bf16_t*)xin; io.B = Bn; io.tab = tab_d; io.step = k; io.t_shared = true;  // rows k of both tables carry the same t
+    io.xin = (const bf16_t*)xin; io.B = Bn * W; io.tab = tab_d; io.step = k; io.t_shared = true;  // rows k of both tables carry the same t
     io.dup_tail = dup_tail;
     io.ctrl = (ctrl_on && i < ck->n_ctrl) ? &actl : nullptr;
     io.maps = bk ? &wm : nullptr;
     io.out = eh; io.out_ld = out_ld;
     u->forward(c, io);
+    if (nw) { launch_window_fuse(h->st, wf_e); launch_window_fuse(h->st, wf_d); }
     const int is_last = (a.last_uses_x0 && k == 0) ? 1 : 0;
     const float* nz = (a.noise && !is_last) ? a.noise + (int64_t)(1 + i) * n : nullptr;
     float* zslot = a.z_out + (1 + i) * chw;

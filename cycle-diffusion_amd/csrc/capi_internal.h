@@ -164,6 +164,8 @@ void check_lowpass_geometry(int R, int down_n);
 void check_automask_params(int n_draws, float ratio, float thr, int dilate);
 // semantic guidance's concept rows and momentum; K < 0: no loop length to hold warm / cool against
 void check_sega_params(const cd_sega_concept* concepts_host, int E, int64_t N, int K, float momentum_scale, float momentum_beta);
+// fused windows: n_win in [1, 64], the canvas at least S x S, every window inside it, no two equal, every cell covered
+void check_window_grid(const int32_t* win_host, int n_win, int Hc, int Wc, int S);
 inline uint32_t sega_active_mask(const cd_sega_concept* cp, int E, int i) {  // bit e: warm_e <= i < cool_e
   uint32_t m = 0;
   for (int e = 0; e < E; ++e) m |= (cp[e].warm <= i && i < cp[e].cool) ? 1u << e : 0u;

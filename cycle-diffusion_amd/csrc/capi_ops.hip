@@ -616,6 +616,43 @@ int cd_op_local_blend_mask(cd_handle h, const float* acc_src, const float* acc_t
   CD_API_END
 }
 
+// one launch of k_window_gather on a caller's canvas; the 16-bit rows come back as fp32
+int cd_op_window_gather(cd_handle h, const float* x, const int32_t* win_host, int n_win, int Bp, int C, int Hc, int Wc, int S,
+                        int cpad, int dup, float* y_out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && x && y_out && Bp > 0 && C > 0 && cpad >= C && cpad % 8 == 0 && (dup == 0 || dup == 1), "bad argument");
+  check_window_grid(win_host, n_win, Hc, Wc, S);
+  ArenaScope arena_scope(h->arena);
+  const int64_t n = (int64_t)(1 + dup) * n_win * Bp * S * S * cpad;
+  CD_CHECK(n < (1ll << 31), "window gather op: %lld values", (long long)n);
+  WindowGather g;
+  g.x = x; g.y = (bf16_t*)h->arena.alloc((size_t)n * 2);
+  g.win = (const int*)upload_table(h, win_host, (size_t)n_win * 2 * sizeof(int32_t));
+  g.Bp = Bp; g.C = C; g.Hc = Hc; g.Wc = Wc; g.S = S; g.n_win = n_win; g.cpad = cpad; g.dup = dup;
+  launch_window_gather(h->st, g);
+  launch_nhwc_to_nchw(h->st, g.y, 0, 1, y_out, 1, 1, (int)n, 1.f, 0.f);  // the values as they lie, widened
+  HIP_CHECK(hipStreamSynchronize(h->st));
+  CD_API_END
+}
+
+// one launch of k_window_fuse (the C = ld = 4 form where it applies) on a caller's network output rows
+int cd_op_window_fuse(cd_handle h, const float* e, const int32_t* win_host, int n_win, int Bp, int C, int Hc, int Wc, int S,
+                      int ld, int parts, float* out) {
+  CD_API_BEGIN
+  enter_engine(h);
+  CD_CHECK(h && e && out && Bp > 0 && C > 0 && ld >= C && parts >= 1, "bad argument");
+  check_window_grid(win_host, n_win, Hc, Wc, S);
+  ArenaScope arena_scope(h->arena);
+  WindowFuse f;
+  f.e = e; f.out = out;
+  f.win = (const int*)upload_table(h, win_host, (size_t)n_win * 2 * sizeof(int32_t));
+  f.Bp = Bp; f.C = C; f.Hc = Hc; f.Wc = Wc; f.S = S; f.n_win = n_win; f.ld = ld; f.parts = parts;
+  launch_window_fuse(h->st, f);
+  HIP_CHECK(hipStreamSynchronize(h->st));
+  CD_API_END
+}
+
 // the masked step kernels on explicit tensors: mode 0 = k_mask_blend_init, 2 = k_decode_step_ddim<true> (blend = 0: last step)
 int cd_op_sched_step_masked(cd_handle h, int mode, const cd_step_coef* coef_host, float* x, const float* eps_hat, int cfg,
                             float guidance, const float* eps_in, const float* mask, const float* src, int B_mask,

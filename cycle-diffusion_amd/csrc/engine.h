@@ -396,8 +396,10 @@ std::unique_ptr<UNet> make_unet_ho(const cd_net_desc& d);
 class VAE : public Net {
  public:
   int kind() const override { return CD_NET_VAE_KL; }
-  virtual void encode_moments(Ctx& c, const bf16_t* img_nhwc, int B, int R, float* moments) = 0;  // fp32 [B*h*w][2*zc]
-  virtual void decode(Ctx& c, const bf16_t* z_nhwc, int B, int h, float* img) = 0;                 // fp32 [B*R*R][3]
+  // img H x W pixels, z h x w latent cells; either extent a multiple of `factor` / any (the convolutions are fully
+  // convolutional and the mid attention runs over the h * w tokens it is given)
+  virtual void encode_moments(Ctx& c, const bf16_t* img_nhwc, int B, int H, int W, float* moments) = 0;  // fp32 [B*h*w][2*zc]
+  virtual void decode(Ctx& c, const bf16_t* z_nhwc, int B, int h, int w, float* img) = 0;                // fp32 [B*H*W][3]
   int z_channels = 4, factor = 8;
   int moments_channels = 8;          // channels of encode_moments' output: 2 * embed_dim (KL) or embed_dim (VQ)
   const float* codebook = nullptr;   // VQ first stage: [n_embed][embed_dim] fp32, else null

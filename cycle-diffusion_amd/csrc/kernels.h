@@ -223,6 +223,27 @@ struct LocalBlendMask {
 };
 void launch_local_blend_mask(hipStream_t st, const LocalBlendMask& a);
 
+// ---------------------------------------------------------------- fused windows (windows.hip)
+// The latent lives on a canvas [Hc, Wc] >= the network's S x S; window w is the S x S crop at win[w] = (y_w, x_w), inside the
+// canvas (the callers check it on the host). Network rows are window-major inside a part: row d * n_win * Bp + w * Bp + b.
+constexpr int kMaxWindows = 64;
+struct WindowGather {  // y[d][w][b][S * S][cpad] 16-bit NHWC <- x[b][:, y_w : y_w + S, x_w : x_w + S], channels C.. zero
+  const float* x = nullptr;  // [Bp][C][Hc][Wc] fp32
+  bf16_t* y = nullptr;       // (1 + dup) parts, every part the same values (the [uncond | cond] rows of one latent)
+  const int* win = nullptr;  // [n_win][2] device
+  int Bp = 0, C = 0, Hc = 0, Wc = 0, S = 0, n_win = 0, cpad = 0, dup = 0;
+};
+void launch_window_gather(hipStream_t st, const WindowGather& a);
+// out[d * Bp + b][c][y][x] = (e_{w_first} + e_w + ...) / (float)count over the windows covering (y, x), ascending w, fp32, no
+// contraction; acc starts from the first covering value, so one covering window returns its value bit for bit
+struct WindowFuse {
+  const float* e = nullptr;  // [parts][n_win][Bp][S * S][ld] fp32, the first C of ld channels are read
+  float* out = nullptr;      // [parts * Bp][C][Hc][Wc] fp32
+  const int* win = nullptr;  // [n_win][2] device
+  int Bp = 0, C = 0, Hc = 0, Wc = 0, S = 0, n_win = 0, ld = 0, parts = 1;
+};
+void launch_window_fuse(hipStream_t st, const WindowFuse& a);
+
 // ---------------------------------------------------------------- implicit-GEMM conv / GEMM (conv_gemm.hip)
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_GELU = 2, ACT_GEGLU = 3, ACT_QGELU = 4, ACT_RELU = 5 };  // QGELU: x*sigmoid(1.702x) (CLIP)
 // RELU: max(x, 0) (the BasicConv2d units of the FID Inception-v3, inception.hip)

@@ -43,8 +43,8 @@ AttnW mk_at(ParamStore& ps, const std::string& pfx, int C) {
 class VAEKL : public VAE {
  public:
   explicit VAEKL(const cd_net_desc& d);
-  void encode_moments(Ctx& c, const bf16_t* img, int B, int R, float* moments) override;
-  void decode(Ctx& c, const bf16_t* z, int B, int h, float* img) override;
+  void encode_moments(Ctx& c, const bf16_t* img, int B, int H, int W, float* moments) override;
+  void decode(Ctx& c, const bf16_t* z, int B, int h, int w, float* img) override;
  private:
   int ch_, nres_, nlev_;
   std::vector<int> mult_;
@@ -120,11 +120,11 @@ VAEKL::VAEKL(const cd_net_desc& d) {
   d_out_ = make_conv(params, "decoder.conv_out", out_ch_, bin, 3);
 }
 
-void VAEKL::encode_moments(Ctx& c, const bf16_t* img, int B, int R, float* moments) {
+void VAEKL::encode_moments(Ctx& c, const bf16_t* img, int B, int H, int W, float* moments) {
   const size_t mk = c.arena->mark();
   PrecisionScope prec(c, f32, x3);
   const size_t esz = f32 ? 4 : 2;
-  const Act x = net_input_act(img, B, R, R, round_up(in_ch_, 32), f32, x3);
+  const Act x = net_input_act(img, B, H, W, round_up(in_ch_, 32), f32, x3);
   ConvOpts o3; o3.want_stats = true;
   Act h = conv_fwd(c, *e_in_, x, nullptr, o3);
   for (int l = 0; l < nlev_; ++l) {
@@ -146,12 +146,12 @@ void VAEKL::encode_moments(Ctx& c, const bf16_t* img, int B, int R, float* momen
   c.arena->release(mk);
 }
 
-void VAEKL::decode(Ctx& c, const bf16_t* z, int B, int hl, float* img) {
+void VAEKL::decode(Ctx& c, const bf16_t* z, int B, int hl, int wl, float* img) {
   const size_t mk = c.arena->mark();
   PrecisionScope prec(c, f32, x3);
-  const Act x = net_input_act(z, B, hl, hl, round_up(embed_, 32), f32, x3);
+  const Act x = net_input_act(z, B, hl, wl, round_up(embed_, 32), f32, x3);
   const int cp = round_up(z_channels, 32);
-  Act zq = alloc_act(c, B, hl, hl, cp);
+  Act zq = alloc_act(c, B, hl, wl, cp);
   HIP_CHECK(hipMemsetAsync(zq.p, 0, (size_t)zq.rows() * cp * (f32 ? 4 : 2), c.st));
   ConvOpts oq; oq.pad = 0; oq.out = zq.p; oq.out_ld = cp;
   conv_fwd(c, *pq_, x, nullptr, oq);

@@ -19,19 +19,40 @@ def center_crop_long_edge(img):
     return img.crop((left, top, left + s, top + s))
 
 
+def center_crop_aspect(img, H, W):
+    """the largest centred rectangle of aspect H : W (integer arithmetic; a square H = W is center_crop_long_edge's crop)"""
+    w, h = img.size
+    if w * H >= h * W:  # too wide: keep the height
+        cw, ch = max(1, (h * W) // H), h
+    else:
+        cw, ch = w, max(1, (w * H) // W)
+    left, top = int(round((w - cw) / 2.0)), int(round((h - ch) / 2.0))
+    return img.crop((left, top, left + cw, top + ch))
+
+
+def _crop_resize(img, resolution):
+    """resolution: an int (the reference's square: CenterCropLongEdge, Resize) or (H, W) (the largest centred rectangle of
+    that aspect, then the same bilinear resize)"""
+    if isinstance(resolution, (tuple, list)):
+        H, W = int(resolution[0]), int(resolution[1])
+        img = center_crop_aspect(img, H, W)
+    else:
+        H = W = int(resolution)
+        img = center_crop_long_edge(img)
+    if img.size != (W, H):
+        img = img.resize((W, H), Image.BILINEAR)  # transforms.Resize default for PIL images
+    return img
+
+
 def load_image(path, resolution):
-    img = Image.open(path).convert("RGB")  # utils/file_utils.pil_loader
-    img = center_crop_long_edge(img)
-    if img.size != (resolution, resolution):
-        img = img.resize((resolution, resolution), Image.BILINEAR)  # transforms.Resize default for PIL images
+    """-> [3, R, R] for an int resolution, [3, H, W] for (H, W)"""
+    img = _crop_resize(Image.open(path).convert("RGB"), resolution)  # utils/file_utils.pil_loader
     return torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0).permute(2, 0, 1).contiguous()  # ToTensor
 
 
 def load_mask(path, resolution):
-    """grey keep-mask -> [1, R, R] in [0, 1] (white = keep): the image's centre crop and bilinear resize"""
-    img = center_crop_long_edge(Image.open(path).convert("L"))
-    if img.size != (resolution, resolution):
-        img = img.resize((resolution, resolution), Image.BILINEAR)
+    """grey keep-mask -> [1, R, R] (or [1, H, W]) in [0, 1] (white = keep): the image's centre crop and bilinear resize"""
+    img = _crop_resize(Image.open(path).convert("L"), resolution)
     return torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0)[None].contiguous()
 
 

@@ -505,25 +505,36 @@ class Engine:
         return out
 
     def vae_encode(self, net, img, noise=None, seed=0, sample=True, scale=0.18215):
+        """img [B, 3, H, W], H and W multiples of the first-stage factor f -> z [B, zc, H / f, W / f]; a square image takes
+        cd_vae_encode, a rectangle cd_vae_encode_hw"""
         img = self._f32(img)
         d = self._descs[net]
-        B, _, R, _ = img.shape
+        B, _, H, W = img.shape
         f = 2 ** (d.n_mult - 1)
-        z = torch.empty((B, d.embed_dim, R // f, R // f), device=img.device, dtype=torch.float32)
+        z = torch.empty((B, d.embed_dim, H // f, W // f), device=img.device, dtype=torch.float32)
         if noise is not None:
             noise = self._f32(noise)
-        check(self.lib.cd_vae_encode(self.h, net, ptr(img), ptr(noise), C.c_uint64(seed), B, R, int(sample),
-                                     C.c_float(scale), ptr(z)))
+        if H == W:
+            check(self.lib.cd_vae_encode(self.h, net, ptr(img), ptr(noise), C.c_uint64(seed), B, H, int(sample),
+                                         C.c_float(scale), ptr(z)))
+        else:
+            check(self.lib.cd_vae_encode_hw(self.h, net, ptr(img), ptr(noise), C.c_uint64(seed), B, H, W, int(sample),
+                                            C.c_float(scale), ptr(z)))
         return z
 
     def vae_decode(self, net, z, scale=0.18215, out_mul=1.0, out_add=0.0):
+        """z [B, zc, h, w] -> img [B, 3, h * f, w * f]; a square latent takes cd_vae_decode, a rectangle cd_vae_decode_hw"""
         z = self._f32(z)
         d = self._descs[net]
-        B, _, hl, _ = z.shape
+        B, _, hl, wl = z.shape
         f = 2 ** (d.n_mult - 1)
-        img = torch.empty((B, d.out_channels, hl * f, hl * f), device=z.device, dtype=torch.float32)
-        check(self.lib.cd_vae_decode(self.h, net, ptr(z), B, hl, C.c_float(scale), C.c_float(out_mul),
-                                     C.c_float(out_add), ptr(img)))
+        img = torch.empty((B, d.out_channels, hl * f, wl * f), device=z.device, dtype=torch.float32)
+        if hl == wl:
+            check(self.lib.cd_vae_decode(self.h, net, ptr(z), B, hl, C.c_float(scale), C.c_float(out_mul),
+                                         C.c_float(out_add), ptr(img)))
+        else:
+            check(self.lib.cd_vae_decode_hw(self.h, net, ptr(z), B, hl, wl, C.c_float(scale), C.c_float(out_mul),
+                                            C.c_float(out_add), ptr(img)))
         return img
 
     def dpm_encode(self, net, kind, x0, coef, ctx_c=None, ctx_uc=None, guidance=1.0, noise=None, seed=0,
@@ -588,17 +599,20 @@ class Engine:
         return (x, traj) if trajectory else x
 
     def cycle_translate(self, net, kind, x0, coef_enc, coef_dec, enc_ctx_c=None, enc_ctx_uc=None, enc_guidance=1.0,
-                        dec_ctx_c=None, dec_ctx_uc=None, dec_guidance=1.0, n_dec=1, noise=None, seed=0, last_uses_x0=True):
+                        dec_ctx_c=None, dec_ctx_uc=None, dec_guidance=1.0, n_dec=1, noise=None, seed=0, last_uses_x0=True,
+                        windows=None):
         """The coupled loop (cd_cycle_translate): dpm_encode and ddim_decode of the same network over the whole chain with ONE
         forward per step over [encoder rows | decoder rows]. x0 [B, C, H, W]; dec_ctx_* [n_dec * B, L, Dc] (decoder row
         j * B + b decodes encoder sample b); dec_guidance one scale or n_dec * B of them (none 0 or 1).
+        `windows` (int32 [n, 2] of (y, x), windows.window_grid): fused windows - x0 / noise are then a canvas [.., Hc, Wc] at
+        least as large as the network's S x S, covered by the n windows; the forward runs n x the rows.
         Returns (z [B, K+1, C, H, W], x [n_dec * B, C, H, W])."""
         return self._cycle_translate(net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
-                                     dec_guidance, n_dec, noise, seed, last_uses_x0)
+                                     dec_guidance, n_dec, noise, seed, last_uses_x0, windows=windows)
 
     def _cycle_translate(self, net, kind, x0, coef_enc, coef_dec, enc_ctx_c, enc_ctx_uc, enc_guidance, dec_ctx_c, dec_ctx_uc,
                          dec_guidance, n_dec, noise, seed, last_uses_x0, mask=None, mask_x0=None, qcoef=None, mask_noise=None,
-                         mask_seed=0, mask_source="q_sample", ctrl=None, blend=None, sega=None):
+                         mask_seed=0, mask_source="q_sample", ctrl=None, blend=None, sega=None, windows=None):
         """The marshalling of cd_cycle_translate: one cd_translate_args, and an option struct for each of the keep-mask, `ctrl` =
         (mapper, alpha, weight, n_ctrl), `blend` = (sel_src, sel_tgt, side, pool, thr, n_start) - it returns (z, x, acc, keep) -
         and `sega` = (edit_ctx, concepts, momentum_scale, momentum_beta) - it returns (z, x, tau, kept, mask). An option that is
@@ -668,13 +682,19 @@ class Engine:
             outs = (acc, keep)
         gvec, gscalar = self._guidance(dec_guidance, n_dec * B, "n_dec * B", x0.device)
         nz = self._f32(noise) if noise is not None else None
+        win = None
+        if windows is not None:  # the canvas is x0's own extent; what the table may hold is cd_cycle_translate's to refuse
+            win = np.ascontiguousarray(windows, dtype=np.int32)
+            if win.ndim != 2 or win.shape[1] != 2:
+                raise ValueError("windows must be [n, 2] (y, x) pairs, got shape %s" % (win.shape,))
+            a.canvas_h, a.canvas_w, a.n_win, a.win_host = H, W, win.shape[0], win.ctypes.data
         a.net, a.sched_kind, a.x0, a.ctx_len, a.B, a.n_dec, a.K = net, kind, ptr(x0), L, B, n_dec, K
         a.enc_ctx_c, a.enc_ctx_uc, a.enc_guidance = ptr(ctxs[0]), ptr(ctxs[1]), enc_guidance
         a.dec_ctx_c, a.dec_ctx_uc, a.dec_guidance, a.dec_guidance_per_sample = ptr(ctxs[2]), ptr(ctxs[3]), gscalar, ptr(gvec)
         a.coef_enc_host, a.coef_dec_host = coef_enc.ctypes.data, coef_dec.ctypes.data
         a.noise, a.seed, a.last_uses_x0, a.z_out, a.x_out = ptr(nz), seed, int(last_uses_x0), ptr(z), ptr(x)
         check(self.lib.cd_cycle_translate(self.h, C.byref(a)))
-        self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise, ctl, sels)  # the launches read them asynchronously
+        self._keep = (gvec, ctxs, nz, mask, mask_x0, mask_noise, ctl, sels, win)  # the launches read them asynchronously
         return (z, x) + outs
 
     @staticmethod

@@ -18,7 +18,7 @@ None of these classes has a translate(): Model.forward runs encode() then forwar
 """
 import torch
 
-from .. import _ffi, attn_control, auto_mask, schedule, semantic_guidance
+from .. import _ffi, attn_control, auto_mask, schedule, semantic_guidance, windows
 from .ddpm_ddim_wrapper import DDPMDDIMWrapper
 from .latent_text_wrapper import LatentDiffStochasticTextWrapper, SDStochasticTextWrapper
 
@@ -93,6 +93,7 @@ class _LatentDDIBText(_LatentBaseline):
         auto_mask.refuse(kw, "DDIB")
         attn_control.refuse_local_blend(kw, "DDIB")
         semantic_guidance.refuse(kw, "DDIB")
+        windows.refuse(kw, "DDIB")
         kw.setdefault("encoder_unconditional_guidance_scales", [1.0])
         kw.setdefault("decoder_unconditional_guidance_scales", [1.0])
         super().__init__(source_model_type, custom_steps, 0.0, -1, list(skip_steps), n_trials=1, couple=False, **kw)
@@ -145,6 +146,7 @@ class _LatentSDEditText(_LatentBaseline):
         auto_mask.refuse(kw, "SDEdit")
         attn_control.refuse_local_blend(kw, "SDEdit")
         semantic_guidance.refuse(kw, "SDEdit")
+        windows.refuse(kw, "SDEdit")
         kw.setdefault("decoder_unconditional_guidance_scales", [1.0])
         super().__init__(source_model_type, custom_steps, eta, -1, [0], encoder_unconditional_guidance_scales=[1.0],
                          n_trials=n_trials or 1, couple=False, **kw)
@@ -283,6 +285,7 @@ class DDPMILVRWrapper(_NoCoupledLoop, DDPMDDIMWrapper):
         auto_mask.refuse(kw, "ILVR")
         attn_control.refuse_local_blend(kw, "ILVR")
         semantic_guidance.refuse(kw, "ILVR")
+        windows.refuse(kw, "ILVR")
         for name, v, lo in (("ilvr_down_n", ilvr_down_n, 1), ("ilvr_range_t", ilvr_range_t, 0)):
             if isinstance(v, bool) or not isinstance(v, int) or v < lo:
                 raise ValueError("%s must be an integer >= %d, got %r" % (name, lo, v))

@@ -27,6 +27,7 @@ import torch
 from .. import _ffi, attn_control, schedule
 from .. import semantic_guidance as sgm
 from .. import auto_mask as am
+from .. import windows as wnd
 from ..engine import kl_f8_vae_desc, ldm_text_unet_desc, sd_v1_unet_desc
 from ..runtime import get_engine, load_or_init_weights, read_checkpoint, synthetic_allowed
 
@@ -82,8 +83,17 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
                  mask_source="q_sample", cac_steps=0.0, cac_mode="refine", auto_mask=None, auto_mask_draws=10,
                  auto_mask_strength=0.5, auto_mask_ratio=3.0, auto_mask_threshold=0.5, auto_mask_dilate=0, auto_mask_seed=0,
                  local_blend=None, local_blend_threshold=0.3, local_blend_pool=3, local_blend_side=0, local_blend_start=0.2,
-                 edit_concepts="", edit_momentum_scale=0.3, edit_momentum_beta=0.6):
+                 edit_concepts="", edit_momentum_scale=0.3, edit_momentum_beta=0.6, window_stride=0):
         super().__init__()
+        # `[gan] window_stride` (latent cells; 0 = off, the default): fused windows (MultiDiffusion) - translate()
+        # takes images larger than the network, [B, 3, H, W] with H and W multiples of the first-stage factor and a latent of
+        # at least image_size x image_size; the coupled loop runs the network on the windows window_grid() lays over the latent
+        self.window_stride = int(window_stride)
+        if self.window_stride < 0:
+            raise ValueError("window_stride must be a number of latent cells (0: off), got %r" % (window_stride,))
+        if self.window_stride and str(precision) in ("fp32", "fp32x3"):
+            raise ValueError("window_stride needs the 16-bit precision: the fused windows are not built for the fp32 / fp32x3 "
+                             "networks")
         # `[gan] edit_concepts = "+glasses:5:0.9; -smile"` (default: none): semantic guidance on the coupled loop -
         # each item `[+|-]text[:scale[:threshold]]` is an edit concept that steers every sample of a translate() call towards
         # (+) or away from (-) its text beside the target prompt; `edit_momentum_scale` / `edit_momentum_beta`: the momentum
@@ -230,11 +240,12 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
     def _schedule(self):
         return schedule.DDIMSchedule(self.alphas_cumprod, self.custom_steps, self.eta)
 
-    def _vae_batch(self):
-        """images per first-stage call (fp32 / split-mode activations are twice the bytes of the 16-bit ones)"""
+    def _vae_batch(self, pixels=None):
+        """images per first-stage call (fp32 / split-mode activations are twice the bytes of the 16-bit ones); `pixels`: of
+        one image, when it is not the wrapper's square resolution"""
         px = self.VAE_MAX_PIXELS if getattr(self, "precision", "fp16") == "fp16" else self.VAE_MAX_PIXELS // 2
         res = getattr(self, "resolution", None) or self.RESOLUTION or 512
-        return max(1, px // (res * res))
+        return max(1, px // (pixels or res * res))
 
     def _randn(self, shape, cpu=None):
         """One noise draw. `noise_source` (a callable shape -> CPU tensor; parity tests) replaces the generator: it lets
@@ -274,15 +285,16 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
     def _first_stage(self, image):
         """z0 = scale * E(2 * image - 1), the posterior sampled (its noise drawn first, on the CPU) or its mean"""
         image = (image - 0.5) * 2.0
-        assert image.shape[2] == image.shape[3] == self.resolution
+        if not getattr(self, "window_stride", 0):
+            assert image.shape[2] == image.shape[3] == self.resolution
         image = image.to(self.device, torch.float32)
         bsz = image.shape[0]
         noise = None
         if self.SAMPLE_POSTERIOR:
             # DiagonalGaussianDistribution.sample draws on the CPU and moves (distributions.py:36)
-            h = self.resolution // self.vae_factor
-            noise = self._randn((bsz, self.channels, h, h), cpu=True)
-        per = self._vae_batch()
+            h, w = image.shape[2] // self.vae_factor, image.shape[3] // self.vae_factor
+            noise = self._randn((bsz, self.channels, h, w), cpu=True)
+        per = self._vae_batch(image.shape[2] * image.shape[3])
         x0 = torch.cat([self.engine.vae_encode(self.vae, image[i:i + per], noise=None if noise is None else noise[i:i + per],
                                                sample=self.SAMPLE_POSTERIOR, scale=self.SCALE_FACTOR)
                         for i in range(0, bsz, per)], 0)
@@ -315,6 +327,9 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         return x0, c, uc, members
 
     def encode(self, image, encode_text):
+        if getattr(self, "window_stride", 0):
+            raise ValueError("window_stride needs translate(): the fused windows run on the coupled loop, which encode() + "
+                             "forward() do not take; use translate(image, encode_text, decode_text)")
         x0, c, uc, members = self._encode_front(image, encode_text)
         return self._encode_members(x0, c, uc, members)
 
@@ -573,7 +588,12 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         every sample of the call. ALWAYS the coupled loop, in chunks of samples past COUPLE_MAX_TOKENS (the concept rows are
         counted); composes with a keep-mask and with cac_steps / attn_ctrl, not with local_blend. last_edit_masks: per
         candidate the kept elements [B, E, C, h, w] of the last iteration with an active concept, last_edit_taus the
-        thresholds [K, B, E]. Without concepts nothing below changes."""
+        thresholds [K, B, E]. Without concepts nothing below changes.
+        `[gan] window_stride > 0`: fused windows - `image` is [B, 3, H, W], any H and W that are multiples of
+        the first-stage factor with a latent of at least image_size x image_size; see _translate_windows. With window_stride =
+        0 nothing below changes."""
+        if getattr(self, "window_stride", 0):
+            return self._translate_windows(image, encode_text, decode_text, mask, attn_ctrl, local_blend, edit_concepts)
         concepts = list(edit_concepts) if edit_concepts is not None else list(getattr(self, "edit_concepts", None) or [])
         sega = len(concepts) > 0
         blend = local_blend is not None or getattr(self, "local_blend", "none") != "none"
@@ -746,6 +766,79 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         img_ensemble = self.generate(z_ensemble, decode_text, latents=latents, mask_noise=mask_noise, **masked)
         return self._select(img_ensemble, image, encode_text, decode_text)
 
+    def _translate_windows(self, image, encode_text, decode_text, mask=None, attn_ctrl=None, local_blend=None,
+                           edit_concepts=None):
+        """translate() with `[gan] window_stride > 0`: the latent of a [B, 3, H, W] image is a canvas [H / f, W / f] on which
+        the noise prediction of a cell is the average over the image_size x image_size windows that cover it
+        (windows.window_grid, cd_translate_args.n_win). Same draws in the same order as translate() on the canvas's shape,
+        same member order. ALWAYS the coupled loop, in chunks of samples so that rows x windows x tokens stays within
+        COUPLE_MAX_TOKENS; the whole chain and every decoder scale riding in the loop are required. The keep-mask, cross-
+        attention control, the local blend and semantic guidance are not built together with windows yet."""
+        given = [n for n, on in (("mask=", mask is not None), ("auto_mask", self._auto_mask_on()),
+                                 ("attn_ctrl=", attn_ctrl is not None), ("cac_steps", self.cac_steps > 0),
+                                 ("local_blend", local_blend is not None or getattr(self, "local_blend", "none") != "none"),
+                                 ("edit_concepts", bool(edit_concepts) or (edit_concepts is None and
+                                                                           bool(getattr(self, "edit_concepts", None))))) if on]
+        if given:
+            raise ValueError("window_stride is not built together with %s yet: switch the windows or %s off"
+                             % (", ".join(given), "it" if len(given) == 1 else "them"))
+        f, S = self.vae_factor, self.image_size
+        if image.dim() != 4 or image.shape[2] % f or image.shape[3] % f or image.shape[2] // f < S or image.shape[3] // f < S:
+            raise ValueError("window_stride: the image must be [B, 3, H, W] with H and W multiples of %d and at least %d, got %s"
+                             % (f, f * S, tuple(image.shape)))
+        Hc, Wc = image.shape[2] // f, image.shape[3] // f
+        win = wnd.window_grid(Hc, Wc, S, self.window_stride)
+        sch = self._schedule()
+        bsz, n_win = image.shape[0], len(win)
+        if not all(self._white_box_loop(len(sch) - sk, sk) == len(sch) - sk for sk in self.skip_steps):
+            raise ValueError("window_stride needs the DPM-Encoder over the whole chain (white_box_steps = custom_steps + 1): the "
+                             "fused windows live in the coupled loop")
+        dec_scales = [float(sc) for sc in self.decoder_unconditional_guidance_scales]
+        n_dec = len(dec_scales)
+        kinds = [self._kind(sc) for sc in dec_scales]
+        main = "cfg" if "cfg" in kinds else kinds[0]
+        if any(k != main for k in kinds) or (main != "cfg" and len(set(dec_scales)) > 1):
+            raise ValueError("window_stride: every decoder scale must ride in the coupled loop (all guided, or one unguided "
+                             "scale) - a candidate decoded from z afterwards would run the network without windows")
+        enc_kinds = [self._kind(float(sc)) for sc in self.encoder_unconditional_guidance_scales]
+        rows1 = ((2 if "cfg" in enc_kinds else 1) + n_dec * (2 if main == "cfg" else 1)) * n_win  # network rows of one sample
+        tokens = S * S
+        self.last_translate_coupled = True
+        x0, c_src, uc, members = self._encode_front(image, encode_text)
+        c_tgt = self.get_condition(decode_text, bsz)[0]
+        bc = max(1, min(bsz, self.couple_max_tokens // (rows1 * tokens)))  # samples per coupled call
+        per_call = max(1, min(self.MAX_FOLD // (bc * (1 + n_dec)), self.couple_max_tokens // (bc * rows1 * tokens)))
+        z_parts, lat_parts = [[] for _ in members], {}
+        for s0 in range(0, bsz, bc):
+            sl = slice(s0, min(bsz, s0 + bc))
+            nb = sl.stop - sl.start
+            for grp in self._groups([(mm[0], mm[1]) for mm in members]):
+                enc_scale, skip = members[grp[0]][0], members[grp[0]][1]
+                for idx in self._chunks(grp, per_call):
+                    n = len(idx)
+                    if main == "cfg" and len(set(dec_scales)) > 1:
+                        guidance = torch.tensor([sc for sc in dec_scales for _ in range(n * nb)], dtype=torch.float32)
+                    else:
+                        guidance = dec_scales[0]
+                    z, x = self.engine.cycle_translate(
+                        self.unet, _ffi.CD_SCHED_DDIM, x0[sl].repeat(n, 1, 1, 1), sch.coef_encode(skip), sch.coef_decode(skip),
+                        enc_ctx_c=c_src[sl].repeat(n, 1, 1), enc_ctx_uc=uc[sl].repeat(n, 1, 1), enc_guidance=enc_scale,
+                        dec_ctx_c=c_tgt[sl].repeat(n * n_dec, 1, 1), dec_ctx_uc=uc[sl].repeat(n * n_dec, 1, 1),
+                        dec_guidance=guidance, n_dec=n_dec, last_uses_x0=True,
+                        noise=torch.cat([members[i][2][:, sl] for i in idx], dim=1).contiguous(), windows=win)
+                    for mi, i in enumerate(idx):
+                        z_parts[i].append(z[mi * nb:(mi + 1) * nb].reshape(nb, -1))
+                        for j in range(n_dec):
+                            lat_parts.setdefault(i * n_dec + j, []).append(x[(j * n + mi) * nb:(j * n + mi + 1) * nb])
+        self.last_z_ensemble = [p[0] if len(p) == 1 else torch.cat(p, 0) for p in z_parts]
+        self.last_latents = [lat_parts[k][0] if len(lat_parts[k]) == 1 else torch.cat(lat_parts[k], 0)
+                             for k in range(len(members) * n_dec)]
+        lat = torch.cat(self.last_latents, 0)
+        per = self._vae_batch(image.shape[2] * image.shape[3])
+        img = torch.cat([self.engine.vae_decode(self.vae, lat[i:i + per].contiguous(), scale=self.SCALE_FACTOR,
+                                                out_mul=0.5, out_add=0.5) for i in range(0, lat.shape[0], per)], 0)
+        return self._select([img[k * bsz:(k + 1) * bsz] for k in range(len(self.last_latents))], image, encode_text, decode_text)
+
     def _control_ids(self, texts):
         """token ids [B, L] of the prompts and the id that ends a prompt, from the text encoder's own tokenizer; a conditioning
         stage without one (a callable embedder) falls back to the whitespace hash tokenizer, padded to the context length"""
@@ -762,6 +855,9 @@ class _LatentStochasticTextWrapper(torch.nn.Module):
         family's encode() samples. Only mask_source 'q_sample' exists on this two-call path: the encoder's trajectory is gone
         once encode() has returned. The decoded image is not pasted over in pixel space: the kept region goes through the
         first stage like the rest."""
+        if getattr(self, "window_stride", 0):
+            raise ValueError("window_stride needs translate(): the fused windows run on the coupled loop, which encode() + "
+                             "forward() do not take; use translate(image, encode_text, decode_text)")
         if getattr(self, "cac_steps", 0.0) > 0:
             raise ValueError("cac_steps > 0 needs translate(): in encode() + forward() the source rows whose attention maps the "
                              "control injects no longer exist; use translate(image, encode_text, decode_text)")

@@ -174,6 +174,13 @@ int cd_vae_encode(cd_handle h, int net, const float* img, const float* noise, ui
  * post_process (x+1)/2 (sd_wrapper:135-137) is out_mul=0.5, out_add=0.5. */
 int cd_vae_decode(cd_handle h, int net, const float* z0, int B, int hlat, float scale, float out_mul,
                   float out_add, float* img);
+/* The same two on a rectangle (the first stage is fully convolutional; its one attention block runs over the h*w tokens it is
+ * given): img [B,3,H,W], H and W multiples of the first-stage factor f (refused otherwise), z0 / noise [B,zc,H/f,W/f]; decode:
+ * z0 [B,zc,hl,wl] -> img [B,3,hl*f,wl*f]. The square entry points are these with H = W = R, bit for bit. */
+int cd_vae_encode_hw(cd_handle h, int net, const float* img, const float* noise, uint64_t seed, int B, int H, int W,
+                     int sample, float scale, float* z0);
+int cd_vae_decode_hw(cd_handle h, int net, const float* z0, int B, int hl, int wl, float scale, float out_mul,
+                     float out_add, float* img);
 
 /* DPM-Encoder: DDIMSampler.ddpm_ddim_encoding / _ddpm_ddim_encoding (ddim.py:230-286, 450-501)
  * and DDPMDDIMWrapper.encode's loop (ddpm_ddim_wrapper.py:483-520).
@@ -391,7 +398,23 @@ typedef struct cd_sega {
  *   z_out [B,K+1,C,H,W] (what encode() returns), x_out [n_dec*B,C,H,W] (what the decode returns).
  * The caller sets `size` to sizeof(cd_translate_args): a call built against another layout of the struct is refused before
  * anything is read from it. mask / ctrl / blend / sega: NULL = the feature is off; each struct says what it adds and what is
- * refused with it. The structs are read during the call only. */
+ * refused with it. The structs are read during the call only.
+ *
+ * Fused windows (MultiDiffusion, Bar-Tal et al. 2023; no counterpart in the reference tree): images larger than
+ * the network. n_win > 0 puts the running latents on a canvas of canvas_h x canvas_w latent cells (each >= S = image_size)
+ * covered by n_win S x S windows, win_host [n_win, 2] int32 HOST pairs (y, x) of their top-left cells. x0, noise, z_out and
+ * x_out then have canvas_h x canvas_w in the place of H x W, and so have the element indices of the counter-based generator.
+ * Each iteration crops every window of the encoder's and of the decoder's latent into network rows (window-major inside each
+ * [uncond | cond] part, the contexts repeated per window), runs the ONE forward over n_win x the rows of the call without
+ * windows, and defines the noise prediction of a canvas cell, per part, as
+ *     acc = e_{w_first};  acc = acc + e_w  (the other windows that cover the cell, ascending w);  eps = acc / (float)count
+ * in fp32 without contraction; the guidance combine and the step arithmetic are those of the call without windows, on the
+ * canvas. Encoder and decoder share the fused prediction, so z_out and the decode are the unchanged arithmetic on a bigger
+ * tensor and the cycle of the same prompt at guidance 1 still closes. One window (0, 0) on an S x S canvas is the call without
+ * windows, bit for bit. n_win = 0 is off: canvas_h, canvas_w must be 0 and win_host NULL.
+ * Refused (error text, nothing launched): n_win outside [0, 64]; a canvas smaller than S; a window outside the canvas; two
+ * equal windows; a canvas cell that no window covers; precision CD_PREC_F32 / CD_PREC_F32X3; a keep-mask, control, blend or
+ * concepts in the same call - windows are not built together with mask / ctrl / blend / sega yet. */
 typedef struct cd_translate_args {
   uint32_t size;
   int net;
@@ -419,6 +442,10 @@ typedef struct cd_translate_args {
   const cd_attn_ctrl* ctrl;
   const cd_local_blend* blend;
   const cd_sega* sega;
+  int canvas_h;
+  int canvas_w;
+  int n_win;
+  const int32_t* win_host;
 } cd_translate_args;
 
 int cd_cycle_translate(cd_handle h, const cd_translate_args* a);
@@ -635,6 +662,16 @@ int cd_op_automask_reduce(cd_handle h, const float* eps_src, const float* eps_tg
  * Refused: side outside [1, 64], f < 1, pool even or outside [1, 7], Bd % B != 0. */
 int cd_op_local_blend_mask(cd_handle h, const float* acc_src, const float* acc_tgt, int B, int Bd, int side, int f, int pool,
                            float thr, float* keep_out);
+/* the two kernels of the fused windows (cd_translate_args.n_win) on caller tensors. win_host [n_win,2] int32 HOST pairs (y, x),
+ * checked as cd_cycle_translate checks them. gather: x [Bp,C,Hc,Wc] fp32 -> y_out [(1+dup)*n_win*Bp, S*S, cpad], the 16-bit
+ * rows of the network input widened to fp32: row d*n_win*Bp + w*Bp + b is x[b, :, y_w:y_w+S, x_w:x_w+S] rounded to the format
+ * of cd_act_format(), channels C..cpad-1 zero; dup 0 or 1, cpad a multiple of 8. fuse: e [parts*n_win*Bp, S*S, ld] fp32 (row
+ * d*n_win*Bp + w*Bp + b, the first C of ld channels) -> out [parts*Bp,C,Hc,Wc]: per cell acc = e_{w_first}, acc = acc + e_w over
+ * the covering windows in ascending w, out = acc / (float)count. */
+int cd_op_window_gather(cd_handle h, const float* x, const int32_t* win_host, int n_win, int Bp, int C, int Hc, int Wc, int S,
+                        int cpad, int dup, float* y_out);
+int cd_op_window_fuse(cd_handle h, const float* e, const int32_t* win_host, int n_win, int Bp, int C, int Hc, int Wc, int S,
+                      int ld, int parts, float* out);
 /* the masked step kernels on explicit tensors (bit-exact checks). mode 0: x <- blend(x) (the blend ahead of the first forward);
  * mode 2: the CD_SCHED_DDIM decode step of cd_op_sched_step followed, when blend != 0, by the blend. src [B_mask,C,HW] is x0
  * (CD_MASK_QSAMPLE: src_k = qa*x0 + qb*mask_noise, mask_noise [B,C,HW] required) or the source latent itself (CD_MASK_ENCODER);

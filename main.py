@@ -156,7 +156,18 @@ def main(argv=None):
     ap.add_argument("--word_maps", action="store_true",
                     help="text tasks: also write every sample's cross-attention heat map of the words its target prompt "
                          "introduces (against the source prompt), on the source image, as word_maps/<id>.png")
+    ap.add_argument("--canvas", default=None, metavar="HxW",
+                    help="`[gan] window_stride > 0` (fused windows): load every image as H x W pixels - the largest centred "
+                         "rectangle of that aspect, resized - instead of the wrapper's square resolution, e.g. 512x768")
     a = ap.parse_args(argv)
+    canvas = None
+    if a.canvas is not None:
+        try:
+            canvas = tuple(int(v) for v in a.canvas.lower().split("x"))
+        except ValueError:
+            canvas = ()
+        if len(canvas) != 2 or min(canvas) <= 0:
+            ap.error("--canvas takes HxW in pixels, e.g. 512x768, got %r" % (a.canvas,))
     if a.synthetic_weights:
         os.environ["CYCLEDIFF_SYNTHETIC_WEIGHTS"] = "1"
 
@@ -179,7 +190,10 @@ def main(argv=None):
     model = get_model(args.model.name)(args).eval()
     wrapper = getattr(model, "gan_wrapper", None) or model.source_gan_wrapper
     start, end = a.range if a.range else (0, None)
-    ds = TripletDataset(a.data, wrapper.resolution, start, end)
+    if canvas is not None and not getattr(wrapper, "window_stride", 0):
+        raise SystemExit("--canvas needs a [gan] window_stride > 0 (fused windows): without it the wrapper takes its square "
+                         "resolution only")
+    ds = TripletDataset(a.data, canvas or wrapper.resolution, start, end)
     os.makedirs(a.output_dir, exist_ok=True)
     dev = torch.device("cuda", local)
     rows, grid_pairs = [], []
